@@ -18,7 +18,10 @@ lba_wait), concurrently with the frame loop, exactly as the reference runs Local
 single-GPU part: 1280x720, 2000 features, 50-KF local BA) or mono (the monocular agents of configs[4]: host image ->
 ORBextractor::operator() with the lapping area of S/Frame.cc:289 -> Frame upload -> the two searches -> mono-edge LBA).
 
-Besides `value` the line carries value_device_images (images already in HBM), value_sync_ctor_host_images (the constructor an
+A plain run sets up, pre-warms, warms up, times --steps steps, writes the last step's outputs if --dump-outputs DIR is given
+and prints the line.  Everything else is behind --full (repeated main regions, secondary regions, the kernel census and
+roofline, copy bandwidth, the drop-in benchmark, the CPU baseline, the in-job parity gates):
+with --full, besides `value` the line carries value_device_images (images already in HBM), value_sync_ctor_host_images (the constructor an
 UNCHANGED Tracking thread calls: synchronous, host images), value_with_pose_opt (the two PoseOptimization calls of Tracking
 per frame included) and fps_formula (BASELINE.md's 1/(t_frontend + t_LBA/K)), each from a shorter timed region,
 p50 / p95 of the per-step times, the measured device-copy bandwidth, and the host CPU.  An internal untimed pre-warm
@@ -502,10 +505,10 @@ def main():
     ap.add_argument("--first-agent", type=int, default=0,
                     help="agent id of rank 0 (rank r runs agent first-agent + r: its own scene / local-BA seeds); a 1-rank run with --first-agent a "
                          "reproduces agent a of a multi-rank run (tests compare parity.agent_digests)")
-    ap.add_argument("--parity-frames", type=int, default=20,
+    ap.add_argument("--parity-frames", type=int, default=None,
                     help="in-job parity gate (SURVEY.md 8d): this many frames of the timed sequence go through the product loop once more, "
                          "outside the timed region, and every output is compared with the CPU oracle; the process exits with code 3 on a "
-                         "violation (0: no gate, the line then carries parity: null)")
+                         "violation (0: no gate, the line then carries parity: null; default 20 with --full, 0 without)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the value_host_images / value_with_pose_opt regions")
     ap.add_argument("--secondary-steps", type=int, default=300)
     ap.add_argument("--separate-calls", action="store_true",
@@ -536,16 +539,17 @@ def main():
                     help="SearchByProjection(Current, Last): resident = mLastFrame's view is uploaded when the tracking of that frame ends "
                          "(orbm_lastview_upload, inside the step) and the next frame's search reads it from HBM; inplace = the search kernel "
                          "reads the view from pinned host memory over PCIe (the form of rounds 1-3)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the main K-step region is run this many times back to back; value = the FIRST one, value_min / _median / _max "
-                         "over all of them are reported next to it (1: no repeats)")
+                         "over all of them are reported next to it (1: no repeats; default 5 with --full, 1 without)")
     ap.add_argument("--no-dropin", action="store_true",
                     help="skip tests/cpp/dropin_bench (the per-frame path and the local BA timed through the reference-signature glue "
                          "over mock Frame / KeyFrame / MapPoint objects; reported as value_dropin)")
-    ap.add_argument("--closed-loop-frames", type=int, default=200,
+    ap.add_argument("--closed-loop-frames", type=int, default=None,
                     help="in-job closed-loop parity (tests/cpp/closed_loop, rank 0, config C2): this many frames of a stereo agent through the "
                          "reference-signature glue, product and oracle each feeding on their own outputs, every product call shadowed on "
-                         "the oracle; reported as parity.closed_loop, a violation fails the job like the open-loop gate (0: skip)")
+                         "the oracle; reported as parity.closed_loop, a violation fails the job like the open-loop gate (0: skip; default "
+                         "200 with --full, 0 without)")
     ap.add_argument("--profile-stages", action="store_true", help="bracket every extractor stage with HIP events")
     ap.add_argument("--no-numa-pin", action="store_true",
                     help="do not restrict the process to the CPUs of the GPU's NUMA node (default: like numactl --cpunodebind)")
@@ -558,7 +562,22 @@ def main():
     ap.add_argument("--server-tick", action="store_true",
                     help="also time the server-side exchange (RCCL all-gather of KF wire blocks -> rebuilt KeyFrame -> "
                          "SearchByProjection(KF, Scw, map)) for 2 and 8 KF blocks; reported under config.server_tick")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the repeated main regions, the secondary regions, the kernel census and "
+                         "roofline, the copy bandwidth, the drop-in benchmark, the CPU baseline and the in-job parity gates.  Without it "
+                         "the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (features, map-point matches, the last "
+                         "local BA's result) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    # a plain run does what the headline needs and nothing else: one main region, no secondary regions, no drop-in or CPU
+    # baseline legs, no parity gates unless asked for by their own options (the census, roofline, copy bandwidth and pose-opt
+    # figures are --full only, below)
+    for name, full_default, plain_default in (("repeats", 5, 1), ("parity_frames", 20, 0), ("closed_loop_frames", 200, 0)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else plain_default)
+    if not args.full:
+        args.no_secondary, args.no_dropin, args.no_cpu_baseline = True, True, True
     # ---- N > 1 launched the way the driver launches N = 1 (`python bench.py --gpus N`, no RANK in the environment): this process
     # starts the N rank processes itself -- fresh children, decided BEFORE anything here touches the GPU -- and relays their exit code
     if args.gpus < 1:
@@ -721,6 +740,7 @@ def main():
             self.tail = (0.0, 0.0, 0.0)
             self.worst_step = None                           # (ms, [extract, match_frame, match_map, pose_opt, map_upload, lba, last_view] us, index in the region) of the slowest step
             self.timeline = np.zeros((0, 5), np.float32)     # per constructor: queue / pack / enqueue / wait / latency [us] (orbx_get_ctor_timeline)
+            self.last = None                                 # (step index, left-image features) of the last timed step
 
     def collect_async(reg):
         if reg.async_t0 is None:
@@ -846,6 +866,7 @@ def main():
                 for key in reg.kern:
                     reg.kern[key] += tm[key]
             reg.stats["kp"] += nl + nr; reg.stats["m_frame"] += n1; reg.stats["m_map"] += n2
+            reg.last = (i, nl)
             if slot is not None:
                 reg.step_s[slot] = time.perf_counter() - t0
 
@@ -959,6 +980,7 @@ def main():
             reg.stage[key] = st.stage_s[j]
         reg.stats.update(kp=st.kp, m_frame=st.m_frame, m_map=st.m_map, lba_iters=st.lba_iters, lba_calls=st.lba_calls, lba_s=st.lba_s)
         reg.step_s = step_s
+        reg.last = (base + n_steps - 1, int(st.last_nl))
         reg.worst_step = (round(1e3 * st.worst_step_s, 3), [round(1e6 * st.worst_stage_s[q], 1) for q in range(7)], int(st.worst_step_index - base))
         reg.timeline = np.concatenate([e.ctor_timeline() for e in exs])
         return reg, elapsed
@@ -1035,12 +1057,32 @@ def main():
         e.set_profile_interval(FAST_BRACKET_EVERY, reset=True)       # every handle brackets every 4th of ITS frames: one frame in four overall,
                                                                       # whatever the size of the ring (an event pair holds the stream for ~2 x 10 us)
     opt.set_profiling(True, reset=True)
-    reg, elapsed = run_region(args.steps, args.warmup, args.pose_opt, host_images, pipeline, prewarm_done)
+    # C++ loop: the main region starts at a multiple of the sequence-and-keyframe period minus --warmup, so that its steps are the
+    # same frames with the same local maps (kf_views: periodic in the step index) whatever the length of the time-based pre-warm, and
+    # what --dump-outputs writes is the same run to run.  The Python loop goes on where the pre-warm stopped: its last step has
+    # handed the next frame to a constructor, and its local map follows the history of LocalMaps.visit()
+    main_first = prewarm_done
+    if use_cxx:
+        main_first += (-(prewarm_done + args.warmup)) % int(np.lcm(len(seq), FRAMES_PER_KF))
+    reg, elapsed = run_region(args.steps, args.warmup, args.pose_opt, host_images, pipeline, main_first)
+    if args.dump_outputs and rank == 0:
+        i_last, nl_last = reg.last
+        outs = {}
+        if feature_outputs is not None:
+            o_ = feature_outputs[i_last % (loop.c.ring if use_cxx else 2)]
+            outs.update(kps=o_["kps"][:nl_last], desc=o_["desc"][:nl_last], uright=o_["uright"][:nl_last], depth=o_["depth"][:nl_last])
+            if not stereo:
+                outs["kps_un"] = o_["kps_un"][:nl_last]
+        outs["map_point_match"] = (loop.amp if use_cxx else amp_buf)[:nl_last]
+        outs["map_point_obs"] = (loop.aob if use_cxx else aob_buf)[:nl_last]
+        outs.update(lba_poses=lba_out.poses, lba_points=lba_out.points, lba_edge_chi2=lba_out.edge_chi2, lba_edge_outlier=lba_out.edge_outlier,
+                    lba_chi2=np.array(lba_out.chi2, np.float64), lba_iters=np.array(lba_out.iters, np.float64))
+        dump_outputs(args.dump_outputs, outs)
     # what the shared host did to the region: involuntary context switches of this process's threads inside it, and how busy
     # OTHER tenants keep the hardware threads of the agent's cores right after it (this process sleeps during the sample)
     host_noise = {"nonvoluntary_ctxt_switches_in_region": reg.stats.get("nonvoluntary_ctxt_switches"),
                   "cgroup_throttled_us_in_region": reg.stats.get("cgroup_throttled_us"), "cgroup_cpu_quota": harness.cgroup_cpu_quota()}
-    if core_pair is not None:
+    if core_pair is not None and args.full:
         try:
             busy = harness._cpu_busy(0.1)
             host_noise["agent_cores_busy_after_region"] = {str(t): round(busy.get(t, 0.0), 2) for c in core_pair for t in sorted(c)}
@@ -1051,7 +1093,7 @@ def main():
     repeat_values = [world * args.steps / elapsed]
     repeat_detail = [(round(1e3 * elapsed, 4), round(1e3 * float(reg.step_s.sum()), 4), [round(1e6 * x, 1) for x in reg.tail],
                       round(1e3 * reg.stats["lba_s"] / max(reg.stats["lba_calls"], 1), 3), reg.worst_step)]
-    if not args.no_secondary and args.repeats > 1:
+    if args.repeats > 1 and not (args.full and args.no_secondary):       # (a plain run repeats only when --repeats asks for it)
         for rep in range(1, args.repeats):
             first = prewarm_done + rep * (args.steps + args.warmup + FRAMES_PER_KF)
             first += (-(first + args.warmup)) % FRAMES_PER_KF                # the first timed step is a keyframe step again
@@ -1067,7 +1109,7 @@ def main():
     # census of the other kernels of the Frame-constructor chain (event pair moved to each in turn, every frame, a few
     # dozen untimed steps): the roofline object below has to describe whichever kernel holds the most device time per step
     chain_ms = {}
-    if not args.profile_stages:
+    if not args.profile_stages and args.full:
         for kname in ("octree_kernel", "orient_desc_gpu_kernel", "pyr_tower_kernel"):
             for e in exs:
                 e.set_profile_kernel(kname)
@@ -1107,18 +1149,20 @@ def main():
                                                      "(S/Tracking.cc:2649,2712; 450 / 650 correspondences), %d timed steps" % ns)
 
     # informational: one PoseOptimization call
-    for _ in range(5):
-        opt.PoseOptimization(po1)
-    t0 = time.perf_counter()
-    for _ in range(20):
-        opt.PoseOptimization(po1)
-    pose_opt_ms = 1e3 * (time.perf_counter() - t0) / 20
+    pose_opt_ms = None
+    if args.full:
+        for _ in range(5):
+            opt.PoseOptimization(po1)
+        t0 = time.perf_counter()
+        for _ in range(20):
+            opt.PoseOptimization(po1)
+        pose_opt_ms = 1e3 * (time.perf_counter() - t0) / 20
 
     server_tick = None
     if args.server_tick:
         server_tick = run_server_tick(grp, api, views, torch, device, frames, kf_chunks, fv, LM, scene)
 
-    copy_gbs = copy_bandwidth_gbs(torch, device) if rank == 0 else None
+    copy_gbs = copy_bandwidth_gbs(torch, device) if (rank == 0 and args.full) else None
     # The drop-in child is a separate dynamically linked program: under a profiler (its preloaded library has initialised the GPU in
     # this process, and the child would inherit the preload) that fork + exec is the hop this pool forbids -- never from a profiled run.
     under_profiler = any(k.startswith(("ROCP", "ROCPROF", "ROCTRACER")) for k in os.environ) or \
@@ -1223,7 +1267,7 @@ def main():
                        "features_on_host": ("every frame: mvKeys / mDescriptors / mvuRight / mvDepth of the left image are copied into host arrays when the "
                                             "constructor is collected (orbx_set_frame_outputs), inside the step") if feature_outputs else
                                            "no: the features stay in HBM (counts only)",
-                       "pose_opt_ms_per_call_450_correspondences": round(pose_opt_ms, 4),
+                       "pose_opt_ms_per_call_450_correspondences": None if pose_opt_ms is None else round(pose_opt_ms, 4),
                        "lba_ms_per_call": round(1e3 * stats["lba_s"] / max(stats["lba_calls"], 1), 3),
                        "sequential_fps_formula": round(1.0 / (sum(v for k2, v in stage.items() if k2 != "lba") / K +
                                                              stats["lba_s"] / max(stats["lba_calls"], 1) / FRAMES_PER_KF), 3),
@@ -1235,8 +1279,9 @@ def main():
                        "frame_path_kernel": {"kernel": "fast_cells_kernel", "bound": "hbm", "achieved_GBps": round(fast_gbs, 2),
                                              "frac_of_hbm_peak": round(fast_gbs / HBM_PEAK_GBS, 5), "avg_launch_ms": round(fast_ms, 5),
                                              "event_pair_overhead_ms": round(ev_overhead_ms, 5), "bracketed_launches": int(fast_n)},
-                       "device_copy_GBps_measured": round(copy_gbs, 1), "host_cpu": host_cpu()},
-            "roofline": {"kernel": ldlt_name,
+                       "device_copy_GBps_measured": None if copy_gbs is None else round(copy_gbs, 1), "host_cpu": host_cpu()},
+        }
+        roofline = {"kernel": ldlt_name,
                          "bound": "mfma", "achieved": round(ldlt_tflops, 6), "peak": FP64_MATRIX_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(ldlt_tflops / FP64_MATRIX_PEAK_TFLOPS, 8), "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_flops_per_launch": int(ldlt_flops),
@@ -1246,8 +1291,9 @@ def main():
                          "peak_source": "AMD MI355X spec sheet, FP64 matrix 78.6 TF (MI355X_MICROARCH.md has no FP64 row); measured issue rate "
                                         "of v_mfma_f64_16x16x4_f64: 1 per 66 cycles per SIMD = 76 TF at 2.4 GHz (tools/micro/mfma_f64_latency.hip)",
                          "note": "a 120 x 120 LDL^T + solve is 0.6 MFLOP on a dependent chain of 120 pivots (one workgroup): "
-                                 "time-to-solution is the figure of merit, the FLOP fraction is reported as the contract asks"},
-        }
+                                 "time-to-solution is the figure of merit, the FLOP fraction is reported as the contract asks"}
+        if args.full:                        # (its subject is chosen by the kernel census, a --full leg)
+            line["roofline"] = roofline
         # ---- the diagnosis of THIS run as top-level scalars (nested objects do not survive into the driver's record)
         line["value_min"] = round(min(repeat_values), 3); line["value_median"] = round(float(np.median(repeat_values)), 3)
         line["value_max"] = round(max(repeat_values), 3); line["value_regions"] = len(repeat_values)
@@ -1267,8 +1313,9 @@ def main():
         line["lba_ms_per_call"] = round(1e3 * stats["lba_s"] / max(stats["lba_calls"], 1), 3)
         line["sync_tail_us"] = round(1e6 * reg.sync_tail_s, 1)
         line["config"]["regions_ms_elapsed__ms_in_steps__tail_us_drain_quiesce_sync__lba_ms__worst_step"] = repeat_detail
-        line["config"]["device_ms_per_step_by_kernel"] = {k2: round(v, 5) for k2, v in sorted(per_step.items(), key=lambda kv: -kv[1])}
-        if dominant != ldlt_name:
+        if args.full:
+            line["config"]["device_ms_per_step_by_kernel"] = {k2: round(v, 5) for k2, v in sorted(per_step.items(), key=lambda kv: -kv[1])}
+        if args.full and dominant != ldlt_name:
             # a kernel of the constructor chain holds more device time per step than the LDL^T: it is the roofline's subject
             # (the LDL^T's figures stay in the line as config.lba_solver_kernel)
             line["config"]["lba_solver_kernel"] = line["roofline"]
@@ -1440,6 +1487,19 @@ def main():
     if parity is not None and parity.get("ok") is False:
         sys.stderr.write("bench.py: PARITY VIOLATION against the oracle: %s\n" % "; ".join(parity.get("violations", []) or ["(another agent)"]))
         sys.exit(3)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32 / float64 (integers that float32 cannot hold exactly go to
+    float64; a structured array is split into out_dir/<name>_<field>.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.names:
+            dump_outputs(out_dir, {"%s_%s" % (name, f): a[f] for f in a.dtype.names})
+            continue
+        kind = np.float32 if a.dtype in (np.float32, np.uint8, np.int8, np.int16, np.uint16) else np.float64
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=kind))
 
 
 def run_dropin_bench():

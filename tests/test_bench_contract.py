@@ -25,7 +25,7 @@ def _bench(*extra, timeout=900):
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    d = _bench("--steps", "40", "--warmup", "10", "--secondary-steps", "20")
+    d = _bench("--full", "--steps", "40", "--warmup", "10", "--secondary-steps", "20")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline", "timed_region_s", "step_ms_p50", "step_ms_p95",
                 "value_device_images", "value_sync_ctor_host_images", "value_with_pose_opt", "fps_formula", "prewarm_steps", "parity"):
@@ -85,7 +85,7 @@ def test_roofline_kernel_is_the_top_row_of_a_fresh_kernel_trace():
     out = tempfile.mkdtemp(prefix="orbg_trace_")
     env = dict(os.environ, TMPDIR="/tmp")
     cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "run", "--",
-           sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--no-secondary",
+           sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "60", "--warmup", "10", "--no-cpu-baseline", "--no-secondary",
            "--lba-mode", "inline", "--no-pipeline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd="/tmp", env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
@@ -117,7 +117,7 @@ def test_roofline_kernel_is_the_top_row_of_a_fresh_kernel_trace():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["C4", "mono", "mono_dist"])
 def test_other_configurations_produce_a_line(name):
-    d = _bench("--config", name, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--secondary-steps", "10")
+    d = _bench("--full", "--config", name, "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--secondary-steps", "10")
     assert d["config"]["name"] == name and d["value"] > 0 and d["config"]["lba_ms_per_call"] > 0
     assert d["roofline"]["bracketed_launches"] >= 1
     assert d["parity"]["ok"] is True and d["parity"]["frames"] == 20          # the in-job gate runs for every configuration
@@ -230,7 +230,7 @@ def test_two_ranks_produce_one_aggregate_line():
     port = 29500 + (os.getpid() % 400)
     env = dict(os.environ, ORBG_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "10",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "40", "--warmup", "10",
                         "--no-secondary", "--no-dropin"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -264,7 +264,7 @@ def test_self_launched_ranks_and_the_in_job_parity_gate():
     """`python bench.py --gpus 2` with no launcher (how the driver starts N = 1): two rank processes on the box's one GPU
     (ORBG_BENCH_SHARE_GPU=1), ONE line with n_gpus == 2, and the in-job parity gate green for both agents."""
     env = dict({k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}, ORBG_BENCH_SHARE_GPU="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-secondary",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-secondary",
                         "--no-dropin", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -285,7 +285,7 @@ def test_eight_ranks_dry_run_of_the_c5_job_on_a_shared_gpu():
     runtime, eight rank processes come up, ONE line with n_gpus == 8 comes back, the mixed mono / stereo agent kinds of configs[4] are
     in place, every agent's in-job parity gate is green, and the line says where every rank ran (rank -> GPU -> NUMA node -> CPUs).
     The rate it prints says nothing -- eight agents share one GPU and this box's CPU quota; the code path is the 8-GPU one."""
-    common = ["--steps", "20", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1", "--prewarm-steps", "20"]
+    common = ["--full", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1", "--prewarm-steps", "20"]
     d = _run_bench(["--config", "C5", "--gpus", "8"] + common, share=True, timeout=1500)
     assert d["n_gpus"] == 8 and d["config"]["name"] == "C5" and len(d["config"]["agents"]) == 8 and set(d["config"]["agents"]) == {"stereo", "mono"}
     pr = d["parity"]
@@ -318,7 +318,7 @@ def test_c3_and_c5_two_agents_with_the_server_tick_in_the_same_job(config, agent
     then goes through gloo over host copies -- RCCL refuses two ranks on one device; the 1-rank run below goes through RCCL):
     per-rank agent kinds, the server tick's collective inside the timed region, the server's outputs equal to the oracle's, and
     SURVEY Appendix F "Multi-GPU": every agent's outputs equal the 1-rank run of the same agent (no cross-talk)."""
-    common = ["--steps", "40", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1"]
+    common = ["--full", "--steps", "40", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1"]
     d = _run_bench(["--config", config, "--gpus", "2"] + common, share=True)
     assert d["n_gpus"] == 2 and d["config"]["name"] == config
     assert d["config"]["agents"] == (["stereo", "stereo"] if config == "C3" else ["stereo", "mono"])
@@ -339,7 +339,61 @@ def test_c3_and_c5_two_agents_with_the_server_tick_in_the_same_job(config, agent
 def test_c3_server_tick_goes_through_rccl_in_the_timed_region():
     """One rank: the tick's all-gather is an RCCL collective on device memory (a single-rank group), inside the timed region, next to the
     agent; the server's results of the last tick equal the oracle's."""
-    d = _run_bench(["--config", "C3", "--steps", "60", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1"])
+    d = _run_bench(["--full", "--config", "C3", "--steps", "60", "--warmup", "5", "--no-secondary", "--no-dropin", "--no-cpu-baseline", "--repeats", "1"])
     st = d["config"]["server_tick_in_job"]
     assert "RCCL" in st["exchange"] and st["ticks"] >= 6 and st["exchange_us_per_tick"] > 0 and st["server_us_per_tick"] > 0
     assert d["parity"]["ok"] is True and d["parity"]["server_tick"]["ok"] is True and d["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_the_last_steps_outputs():
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the headline fields, exactly N timed steps, none of the --full legs;
+    --dump-outputs writes the last timed step's outputs as float32 / float64 .npy files, the same in two runs with the same arguments."""
+    import numpy as np
+    dirs = [tempfile.mkdtemp(prefix="orbg_dump_") for _ in range(2)]
+    lines = [_bench("--gpus", "1", "--steps", "30", "--warmup", "5", "--dump-outputs", dd) for dd in dirs]
+    for d in lines:
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 30 and d["warmup"] == 5 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) < 0.01 * d["value"]
+        for key in ("roofline", "cpu_baseline", "value_device_images", "value_dropin"):
+            assert key not in d, key
+        assert d["parity"] is None and d["value_regions"] == 1
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    for want in ("kps_x.npy", "desc.npy", "uright.npy", "depth.npy", "map_point_match.npy", "lba_poses.npy", "lba_points.npy"):
+        assert want in names, want
+    total = 0
+    for nm in names:
+        a, b = (np.load(os.path.join(dd, nm)) for dd in dirs)
+        assert a.dtype in (np.float32, np.float64), (nm, a.dtype)
+        assert np.array_equal(a, b), nm
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(os.path.join(dirs[0], "kps_x.npy")).size > 500 and (np.load(os.path.join(dirs[0], "map_point_match.npy")) >= 0).sum() > 100
+    # ... and they are the LAST timed step's: the C++ loop's main region starts at a multiple of the sequence period, so its last step
+    # tracks frame seq[(steps - 1) % len(seq)]; the CPU oracle on that frame's images gives the features and stereo data bit for bit
+    from multi_orbslam3_amd import synth
+    from oracle import binding as ob
+    sys.path.insert(0, ROOT)
+    import bench
+    cfg = bench.CONFIGS["C2"]
+    n_seq = lines[0]["config"]["sequence_frames"]
+    n_frames = n_seq // 2 + 1
+    seq = list(range(n_frames)) + list(range(n_frames - 2, 0, -1))
+    assert len(seq) == n_seq
+    sc = synth.Scene(cfg["W"], cfg["H"], seed=synth.SEED_IMAGES)           # agent 0
+    L, R, _ = sc.stereo_pair(seq[(30 - 1) % n_seq])
+    exL, exR = (ob.Extractor(n_features=cfg["n_features"], max_width=cfg["W"], max_height=cfg["H"]) for _ in range(2))
+    _, okl, odl, _ = exL.extract(L)
+    _, okr, odr, _ = exR.extract(R)
+    our, odp = ob.stereo_match(exL, exR, okl, odl, okr, odr, float(sc.cam["bf"]), float(sc.cam["b"]))
+    got = {nm[:-4]: np.load(os.path.join(dirs[0], nm)) for nm in names}
+    assert got["kps_x"].size == len(okl)
+    for f in okl.dtype.names:
+        assert np.array_equal(got["kps_" + f], okl[f].astype(got["kps_" + f].dtype)), f
+    assert np.array_equal(got["desc"], odl.astype(np.float32))
+    assert np.array_equal(got["uright"], our[:len(okl)]) and np.array_equal(got["depth"], odp[:len(okl)])
+    for dd in dirs:
+        shutil.rmtree(dd, ignore_errors=True)

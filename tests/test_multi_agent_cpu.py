@@ -132,11 +132,17 @@ def test_keyframe_blocks_all_gather_gloo():
     assert [len(o["tick_own"]) for o in outs] == [2, 3]
 
 
-def test_cpu_list_parsing_and_pinning_helpers_degrade_without_a_gpu():
+def test_cpu_list_parsing_and_pinning_helpers_degrade_without_a_gpu(monkeypatch):
+    import torch
     from multi_orbslam3_amd import harness
     assert harness._parse_cpulist("0-3,8,10-11\n") == {0, 1, 2, 3, 8, 10, 11}
     assert harness._parse_cpulist("") == set()
-    # no GPU / no sysfs topology here: both helpers report "not available" instead of raising
+
+    def no_device(*a, **k):
+        raise RuntimeError("no HIP device")
+    # no GPU / no sysfs topology (on a GPU box too: the device query fails as it does without one, and nothing gets pinned):
+    # both helpers report "not available" instead of raising
+    monkeypatch.setattr(torch.cuda, "get_device_properties", no_device)
     assert harness.pin_to_gpu_numa_node(0) is None
     assert harness.core_pair_for_agent(0, 0) is None
 

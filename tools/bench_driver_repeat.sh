@@ -1,8 +1,8 @@
 #!/bin/bash
-# N runs of the line exactly as the driver takes it (python bench.py --gpus 1 --steps 20 --warmup 5): value, step p50 / p95, local BA, host noise
+# N runs of the --full line at the driver's size (python bench.py --gpus 1 --steps 20 --warmup 5 --full): value, step p50 / p95, local BA, host noise
 N=${1:-6}
 for i in $(seq $N); do
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep "^{" | python -c "
+  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | grep "^{" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config']
 print('run $i value', d['value'], 'min/median/max of 5 regions', d.get('value_min'), d.get('value_median'), d.get('value_max'), 'step p50/p95/max', d['step_ms_p50'], d['step_ms_p95'], d['step_ms_max'],

@@ -13,29 +13,29 @@ OUT="$R/gpurun_out/$TAG"
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 INL="--steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$R/bench.py" $INL > "$OUT/stats.log" 2>&1 || true
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_async" -o run -- python3 "$R/bench.py" --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-dropin > "$OUT/stats_async.log" 2>&1 || true
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c4" -o run -- python3 "$R/bench.py" --config C4 --steps 40 --warmup 5 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline > "$OUT/stats_c4.log" 2>&1 || true
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 "$R/bench.py" --full $INL > "$OUT/stats.log" 2>&1 || true
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_async" -o run -- python3 "$R/bench.py" --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --no-dropin > "$OUT/stats_async.log" 2>&1 || true
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats_c4" -o run -- python3 "$R/bench.py" --full --config C4 --steps 40 --warmup 5 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline > "$OUT/stats_c4.log" 2>&1 || true
 PMC="--steps 20 --warmup 5 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 "$R/bench.py" $PMC > "$OUT/pmc_fetch.log" 2>&1 || true
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 "$R/bench.py" $PMC > "$OUT/pmc_write.log" 2>&1 || true
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 "$R/bench.py" --full $PMC > "$OUT/pmc_fetch.log" 2>&1 || true
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o run -- python3 "$R/bench.py" --full $PMC > "$OUT/pmc_write.log" 2>&1 || true
 C4PMC="--config C4 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_c4" -o run -- python3 "$R/bench.py" $C4PMC > "$OUT/pmc_fetch_c4.log" 2>&1 || true
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_c4" -o run -- python3 "$R/bench.py" $C4PMC > "$OUT/pmc_write_c4.log" 2>&1 || true
-rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/pmc_mfma" -o run -- python3 "$R/bench.py" $PMC > "$OUT/pmc_mfma.log" 2>&1 || true
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d "$OUT/pmc_sq" -o run -- python3 "$R/bench.py" $PMC > "$OUT/pmc_sq.log" 2>&1 || true
-rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/pmc_mfma_c4" -o run -- python3 "$R/bench.py" --config C4 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline > "$OUT/pmc_mfma_c4.log" 2>&1 || true
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_c4" -o run -- python3 "$R/bench.py" --full $C4PMC > "$OUT/pmc_fetch_c4.log" 2>&1 || true
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_c4" -o run -- python3 "$R/bench.py" --full $C4PMC > "$OUT/pmc_write_c4.log" 2>&1 || true
+rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/pmc_mfma" -o run -- python3 "$R/bench.py" --full $PMC > "$OUT/pmc_mfma.log" 2>&1 || true
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU --output-format csv -d "$OUT/pmc_sq" -o run -- python3 "$R/bench.py" --full $PMC > "$OUT/pmc_sq.log" 2>&1 || true
+rocprofv3 --pmc SQ_INSTS_VALU_MFMA_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES --output-format csv -d "$OUT/pmc_mfma_c4" -o run -- python3 "$R/bench.py" --full --config C4 --steps 10 --warmup 3 --no-cpu-baseline --no-secondary --no-dropin --lba-mode inline --no-pipeline > "$OUT/pmc_mfma_c4.log" 2>&1 || true
 cd "$R"
-python3 bench.py --steps 2000 --warmup 100 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_default.json" || true
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_driver_20_steps.json" || true
-python3 bench.py --steps 400 --warmup 40 --no-pipeline --no-cpu-baseline --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_sync_ctor.json" || true
-python3 bench.py --steps 400 --warmup 40 --lba-mode inline --no-pipeline --no-cpu-baseline --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_inline.json" || true
-python3 bench.py --config C4 --steps 200 --warmup 20 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c4.json" || true
-python3 bench.py --config mono --steps 2000 --warmup 100 --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_mono.json" || true
-python3 bench.py --config mono_dist --steps 2000 --warmup 100 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_mono_dist.json" || true
-python3 bench.py --config C3 --steps 2000 --warmup 100 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c3_1rank.json" || true
-ORBG_BENCH_SHARE_GPU=1 python3 bench.py --config C5 --gpus 2 --steps 200 --warmup 20 --no-secondary --no-dropin --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c5_2ranks_shared_gpu.json" || true
-python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-secondary --no-dropin --server-tick 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_server_tick.json" || true
+python3 bench.py --full --steps 2000 --warmup 100 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_default.json" || true
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_driver_20_steps.json" || true
+python3 bench.py --full --steps 400 --warmup 40 --no-pipeline --no-cpu-baseline --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_sync_ctor.json" || true
+python3 bench.py --full --steps 400 --warmup 40 --lba-mode inline --no-pipeline --no-cpu-baseline --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_inline.json" || true
+python3 bench.py --full --config C4 --steps 200 --warmup 20 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c4.json" || true
+python3 bench.py --full --config mono --steps 2000 --warmup 100 --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_mono.json" || true
+python3 bench.py --full --config mono_dist --steps 2000 --warmup 100 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_mono_dist.json" || true
+python3 bench.py --full --config C3 --steps 2000 --warmup 100 --no-secondary --no-dropin 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c3_1rank.json" || true
+ORBG_BENCH_SHARE_GPU=1 python3 bench.py --full --config C5 --gpus 2 --steps 200 --warmup 20 --no-secondary --no-dropin --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_c5_2ranks_shared_gpu.json" || true
+python3 bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-secondary --no-dropin --server-tick 2>/dev/null | grep '^{' | tail -1 > "$OUT/bench_line_server_tick.json" || true
 tests/cpp/dropin_bench 40 > "$OUT/dropin_bench.json" 2> "$OUT/dropin_bench.txt" || true
 tools/micro/fp64_latency > "$OUT/micro_fp64_issue.txt" 2>&1 || true
 [ -x tools/micro/ldlt_mfma_test_prof ] && timeout 120 tools/micro/ldlt_mfma_test_prof > "$OUT/ldlt_xcd_timeline.txt" 2>&1 || true
