@@ -1615,6 +1615,21 @@ struct LbaSwitches {
     return w;
   }
 };
+// One linearisation of the system: per edge the Jacobian products (EB), per active point Hll / bl, per free pose Hpp / bp.  The
+// handle keeps two: while the host waits for the verdict on a trial, the linearisation of the TRIAL state (= the next
+// iteration's, if the trial is accepted -- the usual case) is already running into the other set.
+struct LinSet {
+  DevBuf<double> EB, Hll, bl, Hpp, bp;
+  int reserve(int NE, int nL, int nP) {
+    int rc;
+    if ((rc = EB.reserve(std::max<size_t>((size_t)NE * kEB, 1))) || (rc = Hll.reserve(std::max<size_t>(6 * (size_t)nL, 1))) ||
+        (rc = bl.reserve(std::max<size_t>(3 * (size_t)nL, 1))) || (rc = Hpp.reserve(std::max<size_t>(21 * (size_t)nP, 1))) ||
+        (rc = bp.reserve(std::max<size_t>(6 * (size_t)nP, 1))))
+      return rc;
+    return ORBG_OK;
+  }
+  void release() { EB.release(); Hll.release(); bl.release(); Hpp.release(); bp.release(); }
+};
 struct lba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -1631,24 +1646,21 @@ struct lba_handle {
   DevBuf<int> d_pair_count;
   DevBuf<PoseQ> d_poses[2];
   DevBuf<double> d_points[2];
-  DevBuf<double> d_err, d_chi2, d_partial, d_EB, d_Hll, d_bl, d_Hpp, d_bp, d_S, d_bs, d_x;
+  DevBuf<double> d_err, d_chi2, d_partial, d_S, d_bs, d_x;
+  LinSet lin[2];
+  DevBuf<double> d_lambda0;            // lambda of a round's first trial / of the next trial, chi2 the round starts from (k_finish, k_errlin)
   DevBuf<double> d_wide;               // running / scaled right-hand side of the many-workgroup LDL^T (k_wide_*)
   DevBuf<double> d_St, d_wfac;         // reduced camera matrix as a tile image / factor scratch of the matrix-core LDL^T (ldlt_mfma.hpp)
-  DevBuf<double> d_EB2, d_Hll2, d_bl2, d_Hpp2, d_bp2, d_lambda0;   // second linearisation set (speculative next iteration)
-  DevBuf<int> d_pose_col, d_point_col, d_pt_start, d_pt_edges, d_ps_start, d_ps_edges, d_pf_start, d_pf_edges, d_pf_col;
-  DevBuf<int> d_pair_i1, d_pair_i2, d_pair_start, d_ok;
-  DevBuf<PairItem> d_items;
+  DevBuf<int> d_ok;
   PinnedBuf<HostRec> rec;
   unsigned rec_seq = 0;
   PinnedBuf<uint8_t> up_h, dl_h;               // per-call upload block (built in place) / download block
   DevBuf<uint8_t> up_d;
-  DevBuf<uint8_t> d_flags;
   DevBuf<double> d_scale_partial;
   DevBuf<unsigned> d_ticket;
   StreamSignal sig;              // completion word behind k_export (polled instead of hipStreamSynchronize)
   std::vector<int> s_pose_deg, s_point_deg, s_pose_col, s_point_col, s_pf_deg, s_f1, s_f2, s_f3, s_fill, s_row_off, s_junk;   // host scratch kept across calls
   std::vector<unsigned> s_cnt4;
-  float last_ms = 0;
   // live measurement of the dominant kernel (the LDL^T launch): one HIP event pair per solve on the handle's stream
   int prof_on = 0;
   hipEvent_t prof_ev[2] = {nullptr, nullptr};
@@ -1700,13 +1712,13 @@ extern "C" int lba_destroy(lba_handle* h) {
   }
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  h->d_edges.release(); h->edges_pin.release(); h->d_items_dev.release(); h->d_pair_count.release(); h->d_poses[0].release(); h->d_poses[1].release(); h->d_points[0].release(); h->d_points[1].release(); 
-  h->d_err.release(); h->d_chi2.release(); h->d_partial.release(); h->d_EB.release(); h->d_Hll.release(); h->d_bl.release();
-  h->d_Hpp.release(); h->d_bp.release(); h->d_S.release(); h->d_bs.release(); h->d_x.release(); h->d_St.release(); h->d_wfac.release(); h->d_xscr.release(); h->d_xflags.release(); h->ldlt_x.scr = nullptr; h->ldlt_x.flags = nullptr;
-  h->d_EB2.release(); h->d_Hll2.release(); h->d_bl2.release(); h->d_Hpp2.release(); h->d_bp2.release(); h->d_lambda0.release();
-  h->d_pose_col.release(); h->d_point_col.release(); h->d_pt_start.release(); h->d_pt_edges.release(); h->d_ps_start.release();
-  h->d_ps_edges.release(); h->d_pf_start.release(); h->d_pf_edges.release(); h->d_pf_col.release(); h->d_pair_i1.release();
-  h->d_pair_i2.release(); h->d_pair_start.release(); h->d_ok.release(); h->d_items.release(); h->rec.release(); h->up_h.release(); h->dl_h.release(); h->up_d.release(); h->d_flags.release(); h->d_scale_partial.release(); h->d_ticket.release(); h->sig.release();
+  h->d_xscr.release(); h->d_xflags.release(); h->ldlt_x.scr = nullptr; h->ldlt_x.flags = nullptr;
+  h->d_edges.release(); h->edges_pin.release(); h->d_items_dev.release(); h->d_pair_count.release();
+  for (int i = 0; i < 2; i++) { h->d_poses[i].release(); h->d_points[i].release(); }
+  h->d_err.release(); h->d_chi2.release(); h->d_partial.release(); h->d_S.release(); h->d_bs.release(); h->d_x.release();
+  for (LinSet& L : h->lin) L.release();
+  h->d_lambda0.release(); h->d_wide.release(); h->d_St.release(); h->d_wfac.release(); h->d_ok.release(); h->rec.release();
+  h->up_h.release(); h->dl_h.release(); h->up_d.release(); h->d_scale_partial.release(); h->d_ticket.release(); h->sig.release();
   for (auto& e : h->prof_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (!h->ext_stream) orbg::release_stream(h->stream);
   delete h;
@@ -1727,26 +1739,21 @@ struct TraceAcc {
 };
 static inline double now_s() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; }
 
-template <typename T>
-static int upload(DevBuf<T>& b, const std::vector<T>& v, hipStream_t st) {
-  int rc = b.reserve(std::max<size_t>(v.size(), 1));
-  if (rc) return rc;
-  if (!v.empty()) ORBG_HIP(hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return ORBG_OK;
-}
-
-// Upload of a piece of the pinned arena by a kernel of our own: every thread moves 16 bytes, all reads over PCIe are in flight
-// at once (~4 us for 150 KB).  The runtime's hipMemcpyAsync runs a blit kernel that takes ~26 us for the same bytes, three
-// times per solve, twice on the critical path of the first LM iteration.
+// Upload from pinned memory by a kernel of our own: every thread moves 16 bytes, all reads over PCIe are in flight at once
+// (~4 us for 150 KB).  The runtime's hipMemcpyAsync runs a blit kernel that takes ~26 us for the same bytes, three times per
+// solve, twice on the critical path of the first LM iteration (~50 us for the 190 KB of edges at C2).
 __global__ __launch_bounds__(256) void k_upload16(const uint4* __restrict__ src, uint4* __restrict__ dst, unsigned n16) {
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i < n16) dst[i] = src[i];
 }
+static void upload16(const uint8_t* src, uint8_t* dst, size_t bytes, hipStream_t st) {
+  const unsigned n16 = (unsigned)((bytes + 15) / 16);
+  hipLaunchKernelGGL(k_upload16, dim3((n16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(src),
+                     reinterpret_cast<uint4*>(dst), n16);
+}
 static int upload_arena(lba_handle* h, size_t off0, size_t off1, hipStream_t st) {
   if (off1 <= off0) return ORBG_OK;
-  const unsigned n16 = (unsigned)((off1 - off0 + 15) / 16);           // offsets are multiples of 64, the arena has 64 bytes of slack
-  hipLaunchKernelGGL(k_upload16, dim3((n16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(h->up_h.d + off0),
-                     reinterpret_cast<uint4*>(h->up_d.p + off0), n16);
+  upload16(h->up_h.d + off0, h->up_d.p + off0, off1 - off0, st);     // offsets are multiples of 64, the arena has 64 bytes of slack
   ORBG_HIP(hipGetLastError());
   return ORBG_OK;
 }
@@ -1754,8 +1761,6 @@ static int upload_arena(lba_handle* h, size_t off0, size_t off1, hipStream_t st)
 // internal: k_ldlt_xcd reported kOkTimedOut during this attempt (never leaves the library)
 constexpr int kRcLdltTimedOut = -70001;
 static int lba_solve_attempt(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r);
-template <class CamT>
-static int lba_solve_attempt_t(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r, const CamT& cam);
 // A launch of the eight-workgroup LDL^T whose participants were not all placed in time says so (ldlt_xcd.hpp: kOkTimedOut) instead of
 // posing as a non-positive-definite system, which the LM loop would answer with a rejected step and another trajectory than the
 // reference's.  The window is then solved again from the caller's (untouched) problem with that kernel switched off for this handle
@@ -1769,71 +1774,276 @@ static int lba_solve_impl(lba_handle* h, const lba_problem* p, StopRef stop_ref,
   rc = lba_solve_attempt(h, p, stop_ref, r);
   return rc == kRcLdltTimedOut ? ORBG_HIP_ERROR : rc;
 }
-// The kernels that evaluate edges exist twice: for the five pinhole scalars (every BASELINE configuration; unchanged code) and for
-// a problem that carries a camera rig (fisheye models, the right camera's *ToBody edges).
-static int lba_solve_attempt(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r) {
-  if (!h || !p) return ORBG_BAD_ARG;
-  const Cam cam{p->fx, p->fy, p->cx, p->cy, p->bf, p->bf};
-  if (!p->rig) return lba_solve_attempt_t(h, p, stop_ref, r, cam);
-  CamRig g;
-  if (!cam_rig_from(*p->rig, cam, &g)) return ORBG_BAD_ARG;
-  return lba_solve_attempt_t(h, p, stop_ref, r, g);
-}
-template <class CamT>
-static int lba_solve_attempt_t(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r, const CamT& cam) {
-  if (!h) return ORBG_BAD_ARG;
-  const LbaSwitches& sw = h->sw;
-  if (!h || !p || !r || p->n_poses < 0 || p->n_points < 0 || p->n_edges < 0) return ORBG_BAD_ARG;
-  if (!r->poses || !r->points) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  const int NP = p->n_poses, NX = p->n_points, NE = p->n_edges;
-  // > 0: stop (the reference's bool); < 0: stop once that many LM trials have been evaluated (deterministic test hook, orbgpu.h)
-  // INT32_MIN: raised right after the check that precedes optimize() (the -k form with k = 0)
+
+// ---------------------------------------------------------------------------------------------- one solve
+
+// g2o's termination test: > 0 stops (the reference's bool); < 0 stops once that many LM trials have been evaluated (deterministic
+// test hook, orbgpu.h); INT32_MIN is raised right after the check that precedes optimize() (the -k form with k = 0)
+struct StopCheck {
+  StopRef ref;
   int trials_done = 0;
   bool past_precheck = false;
-  auto terminate = [&]() {
-    if (stop_ref.u8) return *stop_ref.u8 != 0;
-    if (!stop_ref.i32) return false;
-    const int v = *stop_ref.i32;
+  bool operator()() const {
+    if (ref.u8) return *ref.u8 != 0;
+    if (!ref.i32) return false;
+    const int v = *ref.i32;
     if (v == INT32_MIN) return past_precheck;
     return v > 0 || (v < 0 && trials_done >= -v);
-  };
-  r->status = LBA_APPLIED; r->iters_round1 = r->iters_round2 = 0; r->n_outliers = 0; r->trace_len = 0;
-  r->chi2_initial = r->chi2_final = 0;
-  if (terminate()) {                                   // S/Optimizer.cc:2127-2129
-    r->status = LBA_ABORTED_BEFORE_OPT;
-    memcpy(r->poses, p->poses, sizeof(float) * 16 * (size_t)NP);
-    memcpy(r->points, p->points, sizeof(float) * 3 * (size_t)NX);
-    for (int k = 0; k < NE; k++) {
-      if (r->edge_chi2) r->edge_chi2[k] = 0;
-      if (r->edge_depth_pos) r->edge_depth_pos[k] = 1;
-      if (r->edge_outlier) r->edge_outlier[k] = 0;
+  }
+};
+
+// The arrays of the upload arena, at host or at device addresses
+struct Arena {
+  PoseQ* poses; double* points;
+  int *pose_col, *point_col, *pt_start, *ps_start, *pf_start;
+  int *cur_pt, *cur_ps, *cur_pf;                 // fill cursors (k_csr_fill)
+  int *pt_edges, *ps_edges, *pf_edges, *pf_col;
+  unsigned long long* lm_mask;
+  int *pair_i1, *pair_i2, *pair_start;
+  PairItem* items;
+};
+// What the structure phase produces (the analogue of BlockSolver::buildStructure, G/core/block_solver.hpp:143-295, host side):
+// the sizes, which steps of the structure the device takes over, and the layout of the upload arena.  Every array the kernels
+// need is built IN PLACE inside that one pinned block and goes to the device in at most three pieces.
+struct LbaStructure {
+  int NP = 0, NX = 0, NE = 0;      // poses, points, edges of the problem
+  int nP = 0, nL = 0;              // free poses and points with an edge: the columns of the system
+  int n = 0, n_zero = 0;           // unknowns of the reduced camera system; entries of the step vector (poses and points)
+  int n_blocks_e = 0;              // workgroups of 256 edges
+  int n_pairs_all = 0, item_cap = 0;   // pose pairs (i1 <= i2); capacity of a pair's segment of device-built items
+  int runs = 0;                    // changes of landmark along the edge list (== nL: every landmark's edges are consecutive)
+  int n_right_edges = 0;           // EdgeSE3ProjectXYZToBody edges: counted among the outliers, NOT in the 50 % rule's denominator (:2256)
+  std::vector<uint8_t> rig_secondary;   // camera rigs: the edge continues a run of edges between the same keyframe and landmark
+  bool dev_items = false;          // the device builds the pair items
+  bool dev_lists = false;          // ... and sorts the lists of free observations per landmark (k_prep / k_errlin_prep)
+  bool dev_csr = false;            // ... and fills the CSR lists itself (k_csr_fill / k_csr_sort)
+  size_t o_poses = 0, o_points = 0, o_pose_col = 0, o_point_col = 0, o_pt_start = 0, o_ps_start = 0, o_pf_start = 0, o_cur_pt = 0,
+         o_cur_ps = 0, o_cur_pf = 0, o_pt_edges = 0, o_ps_edges = 0, o_pf_edges = 0, o_pf_col = 0, o_lm_mask = 0, o_pair_i1 = 0,
+         o_pair_i2 = 0, o_pair_start = 0, o_items = 0, o_end = 0;
+  size_t off_a = 0;                // part A, the first upload: what the error / linearisation kernels read
+  Arena H{};                       // host addresses
+  Arena at(uint8_t* B) const {
+    auto I = [B](size_t o) { return reinterpret_cast<int*>(B + o); };
+    return Arena{reinterpret_cast<PoseQ*>(B + o_poses), reinterpret_cast<double*>(B + o_points), I(o_pose_col), I(o_point_col),
+                 I(o_pt_start), I(o_ps_start), I(o_pf_start), I(o_cur_pt), I(o_cur_ps), I(o_cur_pf), I(o_pt_edges), I(o_ps_edges),
+                 I(o_pf_edges), I(o_pf_col), reinterpret_cast<unsigned long long*>(B + o_lm_mask), I(o_pair_i1), I(o_pair_i2),
+                 I(o_pair_start), reinterpret_cast<PairItem*>(B + o_items)};
+  }
+};
+
+// g2o's Levenberg-Marquardt state (OptimizationAlgorithmLevenberg::solve) and the bookkeeping of what was launched ahead of the
+// host's verdict on a trial.  `version` counts LM trials; a launch made on speculation is used only while it is still valid:
+//   spec_ready          set ls ^ 1 holds the linearisation of the current estimate (the first linearisation, or the k_errlin of
+//                       the trial just accepted): the next iteration takes it instead of linearising
+//   fin_version         k_finish (the lambda init of the next round) ran on set ls ^ 1 behind trial fin_version: valid for the
+//                       round's first iteration if no later trial ran and that iteration took the speculative set
+//   solve_version       Schur complement + LDL^T of the next trial ran on set ls ^ 1 behind trial solve_version: valid for the
+//                       first trial of the next iteration if that trial is the very next one and its iteration took that set
+//   exp_version/exp_buf k_export of state buffer exp_buf ran (completion word posted) behind trial exp_version: the final export
+//                       if no later trial ran and exp_buf became the current estimate
+struct LmState {
+  int version = 0;
+  int cur = 0;                     // state buffer of the current estimate: a trial goes to (cur + 1) % 3, an accepted one becomes current
+  int ls = 0;                      // linearisation set of the current iteration
+  bool err_valid = false;          // d_err / d_chi2 hold the residuals of the current estimate
+  bool spec_ready = false;
+  int fin_version = -1, solve_version = -1, exp_version = -1, exp_buf = -1;
+  double lambda = -1, ni = 2, currentChi = 0;
+  int nBad = 0;
+  bool first_chi = true;           // r->chi2_initial not yet set
+  bool last_round = false;
+};
+
+// k_update's workgroup size: the kernel is a chain of dependent memory round trips per landmark; small workgroups spread the same
+// wavefronts over more compute units (measured at C2: 256 threads 0.499 ms per solve, 128: 0.488, 64: 0.484)
+constexpr int kUpdThreads = 64;
+
+// One attempt at a solve, phase by phase (lba_solve_attempt_t).  Every launch form of the local BA is a member, written once:
+// `buf` names one of the three state buffers (posesB / pointsB), `set` one of the two linearisation sets (h->lin).
+template <class CamT>
+struct LbaRun : LbaStructure {
+  lba_handle* const h;
+  const hipStream_t st;
+  const lba_problem* const p;
+  lba_result* const r;
+  const CamT& cam;
+  StopCheck stop;
+  LmState lm;
+  Huber hb;
+  const lba_edge* d_edges = nullptr;
+  Arena D{};                       // device addresses (NULL where the path does not read an array)
+  PoseQ* posesB[3] = {};           // the three state buffers: 0 IS the uploaded state inside the arena
+  double* pointsB[3] = {};
+  struct { uint8_t* flags; double* chi2; PoseQ* poses; double* points; } out{};   // k_export's outputs in the results block (dl_h)
+  size_t o_rflags = 0, o_rchi = 0, o_rposes = 0, o_rpoints = 0;
+  bool use_mfma = false, use_wide = false, use_xcd = false;
+  int n_blocks_u = 0;              // k_update's workgroups: also the number of its scale partials
+  bool first2 = false;             // the first iteration went out in two launches (k_errlin_prep or k_csr_sort + k_errlin, k_finish_items)
+  bool prof_this_solve = false, prof_pending = false;   // an event pair brackets one LDL^T launch of this call
+
+  LbaRun(lba_handle* h_, const lba_problem* p_, lba_result* r_, const CamT& cam_, StopRef stop_ref)
+      : h(h_), st(h_->stream), p(p_), r(r_), cam(cam_) {
+    stop.ref = stop_ref;
+    NP = p->n_poses; NX = p->n_points; NE = p->n_edges;
+    hb.delta_mono = (float)std::sqrt(5.991); hb.dsqr_mono = hb.delta_mono * hb.delta_mono;          // S/Optimizer.cc:1991-1992
+    hb.delta_stereo = (float)std::sqrt(7.815); hb.dsqr_stereo = hb.delta_stereo * hb.delta_stereo;
+  }
+
+  // ---- launch forms (kept in this order: see the explicit instantiations below)
+  // computeActiveErrors; final_mode: the last block also publishes {robust chi2, computeScale(), solver flag} to the host record
+  void errors(int buf, int final_mode) {
+    if (NE > 0)
+      hipLaunchKernelGGL(k_errors<CamT>, dim3(n_blocks_e), dim3(256), 0, st, NE, d_edges, posesB[buf], pointsB[buf], cam, hb,
+                         h->d_err.p, h->d_chi2.p, h->d_partial.p, final_mode, h->d_ticket.p, h->d_scale_partial.p, n_blocks_u,
+                         h->d_ok.p, h->rec.d, final_mode ? ++h->rec_seq : 0u);
+  }
+  // buildSystem: linearise state `buf` into set `set`
+  void linearise(int buf, int set) {
+    const LinSet& L = h->lin[set];
+    if (NE > 0 || nP > 0)
+      hipLaunchKernelGGL(k_lin_all<CamT>, dim3(nP + (NE > 0 ? n_blocks_e : 0)), dim3(256), 0, st, nP, NE, d_edges, posesB[buf],
+                         pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, L.EB.p, D.ps_start,
+                         D.ps_edges, L.Hpp.p, L.bp.p);
+    if (nL > 0)
+      hipLaunchKernelGGL(k_reduce_points, dim3((nL + 255) / 256), dim3(256), 0, st, nL, D.pt_start, D.pt_edges, L.EB.p, L.Hll.p, L.bl.p);
+  }
+  // the results of state `buf` straight into the pinned results block
+  void export_state(int buf) {
+    const int n_thr = std::max(std::max(NE, NP), 3 * NX);
+    if (n_thr > 0)
+      hipLaunchKernelGGL(k_export<CamT>, dim3((n_thr + 255) / 256), dim3(256), 0, st, NE, NP, NX, d_edges, posesB[buf], pointsB[buf], cam,
+                         h->d_chi2.p, out.flags, out.chi2, out.poses, out.points);
+  }
+  // Schur complement + LDL^T of set `set` with lambda `lam` (*lam_p where not NULL: the lambda the device computed)
+  int solve(int set, double lam, const double* lam_p) {
+    if (nP > 0) {
+      const LinSet& L = h->lin[set];
+      // (more pose pairs than compute units: the two-pass form, three workgroups per compute unit)
+      const auto schur_fn = n_pairs_all > 256 ? k_schur<2> : k_schur<1>;
+      hipLaunchKernelGGL(schur_fn, dim3(n_pairs_all), dim3(kSchurThreads), 0, st, nP, D.pair_i1, D.pair_i2, D.pair_start, D.items,
+                         L.EB.p, L.Hll.p, L.bl.p, L.Hpp.p, L.bp.p, lam, h->d_S.p, h->d_bs.p, lam_p, item_cap,
+                         dev_items ? h->d_pair_count.p : (const int*)nullptr, use_mfma ? h->d_St.p : (double*)nullptr);
+      // (two event records and an elapsed-time query cost the solve ~8 us: one solve in four is enough for an average)
+      const bool bracket = h->prof_on && !prof_pending && prof_this_solve;
+      if (bracket) ORBG_HIP(hipEventRecord(h->prof_ev[0], st));
+      if (use_xcd) {
+        const bool one_short = h->sw.ldlt_xcd_short_once;
+        h->sw.ldlt_xcd_short_once = false;
+        ORBG_HIP(ldltx::launch(h->ldlt_x, n, h->d_St.p, h->d_x.p, h->d_ok.p, st, ldltx::kMaxP, h->sw.ldlt_xcd == 2, one_short));
+      } else if (use_mfma) {
+        ORBG_HIP(ldltm::launch(n, h->d_St.p, h->d_x.p, h->d_ok.p, h->d_wfac.p, st, &h->ldlt_attr));
+      } else {
+        ORBG_HIP(launch_ldlt_wide(n, h->d_S.p, h->d_bs.p, h->d_x.p, h->d_ok.p, h->d_wide.p, st));
+      }
+      if (bracket) { ORBG_HIP(hipEventRecord(h->prof_ev[1], st)); prof_pending = true; }
+    } else {
+      ORBG_HIP(hipMemsetAsync(h->d_ok.p, 0xFF, sizeof(int), st));   // nothing to solve: ok
     }
     return ORBG_OK;
   }
-  past_precheck = true;
-  static TraceAcc tr("lba_solve_h structure (before the first launch) / upload submit / LM loop incl. pair items / export+wait / write-back / "
-                     "of the structure: edge pass + layout / CSR lists / of the LM loop: pair items + symbolic + upload");
-  const double t_a = now_s();
-  hipStream_t st = h->stream;
-  // ---- structure (the analogue of BlockSolver::buildStructure, G/core/block_solver.hpp:143-295), host side.
-  // Every array the kernels need is built IN PLACE inside one pinned block and goes to the device with ONE copy.
-  std::vector<int>& pose_deg = h->s_pose_deg; std::vector<int>& point_deg = h->s_point_deg;
-  std::vector<int>& pf_raw = h->s_f3;                      // per point: observations from poses that are not fixed
-  pose_deg.assign(NP, 0); point_deg.assign(NX, 0); pf_raw.assign(NX, 0);
-  // ONE pass over the caller's edges (360 KB at C2, cold): copy into pinned memory, validate, count degrees; the copy
-  // goes to the device at once and every later pass reads the warm pinned copy
-  if ((rc = h->edges_pin.reserve(std::max(NE, 1))) || (rc = h->d_edges.reserve(std::max(NE, 1)))) return rc;
-  lba_edge* const edges = h->edges_pin.h;
-  // Optimizer::LocalBundleAdjustment adds the edges landmark by landmark (S/Optimizer.cc:2007-2124): consecutive edges increment the
-  // SAME landmark's counters, and a read-modify-write of one word per edge is a chain of store-to-load forwards.  The landmark
-  // counters therefore rotate over four copies (k & 3: a run of up to four edges of one
-  // landmark touches four different words), both counts packed in one word (edges | edges of free poses << 16; fewer than 65536 edges);
-  // `runs` counts the changes of landmark along the list: equal to the number of observed landmarks <=> every landmark's edges are
-  // consecutive, which the list pass below exploits.
-  int runs = 0;
-  {
+  // the trial state `trial` = `from` (+) the step of set `set`
+  void update(int from, int trial, int set, double lambda, const double* lam_p) {
+    const LinSet& L = h->lin[set];
+    hipLaunchKernelGGL(k_update<kUpdThreads>, dim3(n_blocks_u), dim3(kUpdThreads), 0, st, NP, NX, nP, D.pose_col, D.point_col,
+                       posesB[from], pointsB[from], h->d_x.p, D.pf_start, D.pf_edges, D.pf_col, L.EB.p, L.Hll.p, L.bl.p, lambda,
+                       posesB[trial], pointsB[trial], L.bp.p, h->d_scale_partial.p, lam_p);
+  }
+  // residuals + record + linearisation of state `buf` into set `set` in ONE launch.  A trial's record is what the host waits for;
+  // the first linearisation's is not (no scale partials, no solver flag: it carries the sequence number the host has already seen)
+  void errlin(int buf, int set, bool trial, LmIn lmi) {
+    const LinSet& L = h->lin[set];
+    hipLaunchKernelGGL(k_errlin<CamT>, dim3(nP + n_blocks_e + errlin_tail_blocks(nL)), dim3(256), 0, st, nP, NE, d_edges, posesB[buf],
+                       pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, L.EB.p, D.ps_start, D.ps_edges, L.Hpp.p,
+                       L.bp.p, h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, trial ? n_blocks_u : 0,
+                       trial ? h->d_ok.p : (const int*)nullptr, h->rec.d, trial ? ++h->rec_seq : h->rec_seq, n_blocks_e, nL, D.pt_start,
+                       D.pt_edges, L.Hll.p, L.bl.p, lmi);
+  }
+  // the last evaluation that can run in the last round, together with the (speculative) export of state `buf`
+  void errors_export(int buf) {
+    const int n_thr = std::max(std::max(NE, NP), 3 * NX);
+    hipLaunchKernelGGL(k_errors_export<CamT>, dim3((n_thr + 255) / 256), dim3(256), 0, st, n_blocks_e, NE, d_edges, posesB[buf],
+                       pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p,
+                       n_blocks_u, h->d_ok.p, h->rec.d, ++h->rec_seq, NP, NX, out.flags, out.chi2, out.poses, out.points);
+  }
+  // the first linearisation (as errlin's first form) together with the sort of the free-observation lists, the padding of the
+  // tile image and the zeroed step vector
+  void errlin_prep(int buf, int set) {
+    const LinSet& L = h->lin[set];
+    const int n_err = nP + n_blocks_e + errlin_tail_blocks(nL), nsb = (nL + 255) / 256;
+    hipLaunchKernelGGL(k_errlin_prep<CamT>, dim3(n_err + nsb + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, n_err, nsb,
+                       D.pf_edges, D.pf_col, D.pf_start, D.lm_mask, n, use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero,
+                       nP, NE, d_edges, posesB[buf], pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, L.EB.p,
+                       D.ps_start, D.ps_edges, L.Hpp.p, L.bp.p, h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, 0,
+                       (const int*)nullptr, h->rec.d, h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, L.Hll.p, L.bl.p, LmIn{});
+  }
+  // computeLambdaInit without a host round trip: k_finish leaves lambda (and the round's chi2) in d_lambda0 for the first trial
+  void finish_lambda_init(int set) {
+    const LinSet& L = h->lin[set];
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, L.bp.p, L.bl.p, L.Hpp.p,
+                       L.Hll.p, 0.0, (int*)nullptr, 0, 1, h->rec.d, p->lambda_init, h->d_lambda0.p);
+  }
+  // ... the same with the pair items (one workgroup per pose pair) in further workgroups
+  void finish_items(int set) {
+    const LinSet& L = h->lin[set];
+    hipLaunchKernelGGL(k_finish_items, dim3(1 + n_pairs_all), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, L.bp.p, L.bl.p,
+                       L.Hpp.p, L.Hll.p, h->rec.d, p->lambda_init, h->d_lambda0.p, D.lm_mask, D.pf_start, D.pf_edges, D.pf_col,
+                       h->d_items_dev.p, item_cap, h->d_pair_count.p);
+  }
+  // without edges nothing else writes the record: k_finish computes it from set `set` (maxdiag for the lambda init, or the
+  // verdict on a trial: with_ok) and the host waits for it
+  int finish_record(int set, double lambda, int want_scale, int want_maxdiag, bool with_ok) {
+    const LinSet& L = h->lin[set];
+    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, L.bp.p, L.bl.p, L.Hpp.p,
+                       L.Hll.p, lambda, with_ok ? h->d_ok.p : (int*)nullptr, want_scale, want_maxdiag, h->rec.d, 0.0, (double*)nullptr);
+    ORBG_HIP(hipGetLastError());
+    ORBG_HIP(hipStreamSynchronize(st));
+    return with_ok && h->rec.h->ok == ldltx::kOkTimedOut ? kRcLdltTimedOut : ORBG_OK;
+  }
+  int poll_record() {
+    // the last workgroup of k_errors publishes the record and then its sequence number: spin on that word (the
+    // runtime's completion path costs ~10 us per LM trial); fall back to a stream sync if it does not arrive
+    volatile unsigned* w = &h->rec.h->seq;
+    const unsigned want = h->rec_seq;
+    bool got = false;
+    if (orbg::poll_allowed()) {              // (the policy of the thread that runs the solve: caller or local-BA worker)
+      timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+      const unsigned long long tg = rec_tag(want);
+      const volatile HostRec* hr = h->rec.h;
+      for (unsigned spins = 0; !got; spins++) {
+        if (*w == want) {
+          // ... and the three pairs of THIS record have arrived (they and seq are independent stores)
+          const double c = hr->chi2, sc = hr->scale; const int okv = hr->ok;
+          unsigned long long bc, bs; memcpy(&bc, &c, 8); memcpy(&bs, &sc, 8);
+          if ((bc ^ hr->c_chi2) == tg && (bs ^ hr->c_scale) == tg && (((unsigned long long)(unsigned)okv) ^ hr->c_ok) == tg) { got = true; break; }
+        }
+        if ((spins & 0xFFFF) == 0xFFFF) {
+          timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+          if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 50.0) break;
+        }
+      }
+      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    }
+    if (!got) ORBG_HIP(hipStreamSynchronize(st));
+    if (h->rec.h->ok == kOkPublishTimedOut) return ORBG_INTERNAL;      // (a fused linearisation's publisher never saw all edge workgroups arrive)
+    // the eight-workgroup LDL^T gave up waiting for a participant: not an LM verdict -- the caller re-solves the window (lba_solve_impl)
+    return h->rec.h->ok == ldltx::kOkTimedOut ? kRcLdltTimedOut : ORBG_OK;
+  }
+
+  // ---- structure, 1: ONE pass over the caller's edges (360 KB at C2, cold): copy into pinned memory, validate, count degrees; the
+  // copy goes to the device at once and every later pass reads the warm pinned copy
+  int edge_pass() {
+    int rc;
+    std::vector<int>& pose_deg = h->s_pose_deg; std::vector<int>& point_deg = h->s_point_deg;
+    std::vector<int>& pf_raw = h->s_f3;                      // per point: observations from poses that are not fixed
+    pose_deg.assign(NP, 0); point_deg.assign(NX, 0); pf_raw.assign(NX, 0);
+    if ((rc = h->edges_pin.reserve(std::max(NE, 1))) || (rc = h->d_edges.reserve(std::max(NE, 1)))) return rc;
+    lba_edge* const edges = h->edges_pin.h;
+    // Optimizer::LocalBundleAdjustment adds the edges landmark by landmark (S/Optimizer.cc:2007-2124): consecutive edges increment the
+    // SAME landmark's counters, and a read-modify-write of one word per edge is a chain of store-to-load forwards.  The landmark
+    // counters therefore rotate over four copies (k & 3: a run of up to four edges of one
+    // landmark touches four different words), both counts packed in one word (edges | edges of free poses << 16; fewer than 65536 edges);
+    // `runs` counts the changes of landmark along the list: equal to the number of observed landmarks <=> every landmark's edges are
+    // consecutive, which the list pass (fill_lists) exploits.
     unsigned prev_pt = ~0u;
     if (NE < 65536) {
       std::vector<unsigned>& cnt4 = h->s_cnt4;
@@ -1868,457 +2078,414 @@ static int lba_solve_attempt_t(lba_handle* h, const lba_problem* p, StopRef stop
         prev_pt = ex;
       }
     }
+    // Camera rigs: the second, third .. edge of a run of edges between the same keyframe and landmark (left and right camera, adjacent
+    // in the reference's creation order) is left out of the per-landmark lists of free observations that the Schur complement and the
+    // back-substitution walk -- the run's first edge carries the Hpl block of the vertex pair (linearize_block).
+    if constexpr (std::is_same<CamT, CamRig>::value) {
+      if (cam.has_right)
+        for (int k = 0; k < NE; k++) n_right_edges += ur_is_right(edges[k].ur) ? 1 : 0;
+      rig_secondary.assign((size_t)std::max(NE, 1), 0);
+      for (int k = 1; k < NE; k++)
+        if (edges[k].pose == edges[k - 1].pose && edges[k].point == edges[k - 1].point) {
+          rig_secondary[k] = 1;
+          if (!p->pose_fixed[edges[k].pose]) pf_raw[edges[k].point]--;
+        }
+    }
+    if (NE > 0) upload16(reinterpret_cast<const uint8_t*>(h->edges_pin.d), reinterpret_cast<uint8_t*>(h->d_edges.p), sizeof(lba_edge) * (size_t)NE, st);
+    return ORBG_OK;
   }
-  // Camera rigs: the second, third .. edge of a run of edges between the same keyframe and landmark (left and right camera, adjacent
-  // in the reference's creation order) is left out of the per-landmark lists of free observations that the Schur complement and the
-  // back-substitution walk -- the run's first edge carries the Hpl block of the vertex pair (linearize_block).
-  constexpr bool kRig = std::is_same<CamT, CamRig>::value;
-  std::vector<uint8_t> rig_secondary;
-  int n_right_edges = 0;           // EdgeSE3ProjectXYZToBody edges: counted among the outliers, NOT in the 50 % rule's denominator (:2256)
-  if constexpr (kRig) {
-    if (cam.has_right)
-      for (int k = 0; k < NE; k++) n_right_edges += ur_is_right(edges[k].ur) ? 1 : 0;
-    rig_secondary.assign((size_t)std::max(NE, 1), 0);
-    for (int k = 1; k < NE; k++)
-      if (edges[k].pose == edges[k - 1].pose && edges[k].point == edges[k - 1].point) {
-        rig_secondary[k] = 1;
-        if (!p->pose_fixed[edges[k].pose]) pf_raw[edges[k].point]--;
-      }
+  // ---- structure, 2: the columns, the CSR counts, which steps the device takes over, the arena layout
+  int layout() {
+    constexpr bool kRig = std::is_same<CamT, CamRig>::value;
+    const std::vector<int>& pose_deg = h->s_pose_deg; const std::vector<int>& point_deg = h->s_point_deg;
+    const std::vector<int>& pf_raw = h->s_f3;
+    std::vector<int>& pose_col_v = h->s_pose_col; std::vector<int>& point_col_v = h->s_point_col;
+    pose_col_v.assign(NP, -1); point_col_v.assign(NX, -1);
+    for (int i = 0; i < NP; i++) if (!p->pose_fixed[i] && pose_deg[i] > 0) pose_col_v[i] = nP++;
+    for (int i = 0; i < NX; i++) if (point_deg[i] > 0) point_col_v[i] = nL++;
+    n = 6 * nP; n_zero = n + 3 * nL;
+    n_blocks_e = (NE + 255) / 256;
+    // free-pose degree of every active point (-> number of (pose pair, landmark) items), edges per active point, edges per
+    // free pose: all of them follow from the degrees counted in the pass above (a pose with an edge has pose_deg > 0, so
+    // "not fixed" is "free" there)
+    std::vector<int>& pf_deg = h->s_pf_deg; std::vector<int>& pt_cnt = h->s_f1; std::vector<int>& ps_cnt = h->s_f2;
+    pf_deg.assign(nL + 1, 0); pt_cnt.assign(nL + 1, 0); ps_cnt.assign(nP + 1, 0);
+    int n_free_edges = 0;
+    for (int i = 0; i < NX; i++) { const int lc = point_col_v[i]; if (lc >= 0) { pt_cnt[lc] = point_deg[i]; pf_deg[lc] = pf_raw[i]; } }
+    for (int i = 0; i < NP; i++) { const int pc = pose_col_v[i]; if (pc >= 0) { ps_cnt[pc] = pose_deg[i]; n_free_edges += pose_deg[i]; } }
+    size_t n_items = 0;
+    for (int l = 0; l < nL; l++) n_items += (size_t)pf_deg[l] * (pf_deg[l] + 1) / 2;
+    n_pairs_all = nP * (nP + 1) / 2;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 63) & ~(size_t)63; return o; };
+    o_poses = take(sizeof(PoseQ) * (size_t)NP); o_points = take(24 * (size_t)NX);
+    // (what the host fills first; then the lists the device may fill itself: see off_a below)
+    o_pose_col = take(4 * (size_t)NP); o_point_col = take(4 * (size_t)NX); o_pt_start = take(4 * ((size_t)nL + 1));
+    o_ps_start = take(4 * ((size_t)nP + 1)); o_pf_start = take(4 * ((size_t)nL + 1));
+    o_cur_pt = take(4 * (size_t)nL); o_cur_ps = take(4 * (size_t)nP); o_cur_pf = take(4 * (size_t)nL);
+    o_pt_edges = take(4 * (size_t)NE); o_ps_edges = take(4 * (size_t)n_free_edges);
+    o_pf_edges = take(4 * (size_t)n_free_edges); o_pf_col = take(4 * (size_t)n_free_edges);
+    // pair items on the device when the pose masks fit one word and the fixed-capacity segments stay small
+    // (a pair's items are landmarks both poses observe: never more than the edges of either pose -- a far smaller segment than
+    // one entry per landmark, which kept the 50-keyframe window of C4 on the host path)
+    int max_pose_edges = 1;
+    for (int i = 0; i < nP; i++) max_pose_edges = std::max(max_pose_edges, ps_cnt[i]);
+    item_cap = std::min(std::max(nL, 1), max_pose_edges);
+    dev_items = nP >= 1 && nP <= 64 && (size_t)n_pairs_all * (size_t)item_cap * sizeof(PairItem) <= ((size_t)64 << 20);
+    // (the lists of free observations per landmark, still in edge order, go along when the device sorts them: k_prep / k_errlin_prep)
+    dev_lists = dev_items && nP >= 1 && ldltm::supports(6 * nP);
+    // ... and the device fills the lists itself (k_csr_fill / k_csr_sort) when a pose's list fits the sorting workgroup
+    // (measured: a wash at C2 -- 7.7 + 15.2 us of kernels for a 29 us host pass -- and -20 us at C4: used from 16 k edges on)
+    dev_csr = dev_lists && NE > 0 && nL > 0 && max_pose_edges <= kCsrPoseCap && NE >= 16384 && !kRig;
+    o_lm_mask = take(8 * (size_t)nL);
+    o_pair_i1 = take(4 * (size_t)n_pairs_all); o_pair_i2 = take(4 * (size_t)n_pairs_all); o_pair_start = take(4 * ((size_t)n_pairs_all + 1));
+    o_items = take(dev_items ? 0 : sizeof(PairItem) * n_items);
+    o_end = off;
+    // part A: host-filled arrays; + the point / pose lists when the host fills them; + the unsorted free-observation lists when
+    // the device only sorts
+    off_a = dev_csr ? o_pt_edges : dev_lists ? o_pf_col : o_pf_edges;
+    int rc;
+    if ((rc = h->up_h.reserve(off + 64)) || (rc = h->up_d.reserve(off + 64))) return rc;
+    H = at(h->up_h.h);
+    return ORBG_OK;
   }
-  if (NE > 0) {
-    // (k_upload16: the runtime's blit kernel takes ~50 us for these 190 KB)
-    const unsigned n16 = (unsigned)((sizeof(lba_edge) * (size_t)NE + 15) / 16);
-    hipLaunchKernelGGL(k_upload16, dim3((n16 + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4*>(h->edges_pin.d),
-                       reinterpret_cast<uint4*>(h->d_edges.p), n16);
-  }
-  std::vector<int>& pose_col_v = h->s_pose_col; std::vector<int>& point_col_v = h->s_point_col;
-  pose_col_v.assign(NP, -1); point_col_v.assign(NX, -1);
-  int nP = 0, nL = 0;
-  for (int i = 0; i < NP; i++) if (!p->pose_fixed[i] && pose_deg[i] > 0) pose_col_v[i] = nP++;
-  for (int i = 0; i < NX; i++) if (point_deg[i] > 0) point_col_v[i] = nL++;
-  // free-pose degree of every active point (-> number of (pose pair, landmark) items), edges per active point, edges per
-  // free pose: all of them follow from the degrees counted in the pass above (a pose with an edge has pose_deg > 0, so
-  // "not fixed" is "free" there)
-  std::vector<int>& pf_deg = h->s_pf_deg; std::vector<int>& pt_cnt = h->s_f1; std::vector<int>& ps_cnt = h->s_f2;
-  pf_deg.assign(nL + 1, 0); pt_cnt.assign(nL + 1, 0); ps_cnt.assign(nP + 1, 0);
-  int n_free_edges = 0;
-  for (int i = 0; i < NX; i++) { const int lc = point_col_v[i]; if (lc >= 0) { pt_cnt[lc] = point_deg[i]; pf_deg[lc] = pf_raw[i]; } }
-  for (int i = 0; i < NP; i++) { const int pc = pose_col_v[i]; if (pc >= 0) { ps_cnt[pc] = pose_deg[i]; n_free_edges += pose_deg[i]; } }
-  size_t n_items = 0;
-  for (int l = 0; l < nL; l++) n_items += (size_t)pf_deg[l] * (pf_deg[l] + 1) / 2;
-  const int n_pairs_all = nP * (nP + 1) / 2;
-  // arena layout
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 63) & ~(size_t)63; return o; };
-  const size_t o_poses = take(sizeof(PoseQ) * (size_t)NP), o_points = take(24 * (size_t)NX);
-  // (what the host fills first; then the lists the device may fill itself: see off_a below)
-  const size_t o_pose_col = take(4 * (size_t)NP), o_point_col = take(4 * (size_t)NX), o_pt_start = take(4 * ((size_t)nL + 1));
-  const size_t o_ps_start = take(4 * ((size_t)nP + 1)), o_pf_start = take(4 * ((size_t)nL + 1));
-  const size_t o_cur_pt = take(4 * (size_t)nL), o_cur_ps = take(4 * (size_t)nP), o_cur_pf = take(4 * (size_t)nL);   // fill cursors (k_csr_fill)
-  const size_t o_pt_edges = take(4 * (size_t)NE), o_ps_edges = take(4 * (size_t)n_free_edges);
-  const size_t o_pf_edges = take(4 * (size_t)n_free_edges), o_pf_col = take(4 * (size_t)n_free_edges);
-  // pair items on the device when the pose masks fit one word and the fixed-capacity segments stay small
-  // (a pair's items are landmarks both poses observe: never more than the edges of either pose -- a far smaller segment than
-  // one entry per landmark, which kept the 50-keyframe window of C4 on the host path)
-  int max_pose_edges = 1;
-  for (int i = 0; i < nP; i++) max_pose_edges = std::max(max_pose_edges, ps_cnt[i]);
-  const int item_cap = std::min(std::max(nL, 1), max_pose_edges);
-  const bool dev_items = nP >= 1 && nP <= 64 && (size_t)n_pairs_all * (size_t)item_cap * sizeof(PairItem) <= ((size_t)64 << 20);
-  // (the lists of free observations per landmark, still in edge order, go along when the device sorts them: k_prep / k_errlin_prep)
-  const bool dev_lists = dev_items && nP >= 1 && ldltm::supports(6 * nP);
-  // ... and the device fills the lists itself (k_csr_fill / k_csr_sort) when a pose's list fits the sorting workgroup
-  // (measured: a wash at C2 -- 7.7 + 15.2 us of kernels for a 29 us host pass -- and -20 us at C4: used from 16 k edges on)
-  const bool dev_csr = dev_lists && NE > 0 && nL > 0 && max_pose_edges <= kCsrPoseCap && NE >= 16384 && !kRig;
-  const size_t o_lm_mask = take(8 * (size_t)nL);
-  const size_t o_pair_i1 = take(4 * (size_t)n_pairs_all), o_pair_i2 = take(4 * (size_t)n_pairs_all), o_pair_start = take(4 * ((size_t)n_pairs_all + 1));
-  const size_t o_items = take(dev_items ? 0 : sizeof(PairItem) * n_items);
-  if ((rc = h->up_h.reserve(off + 64)) || (rc = h->up_d.reserve(off + 64))) return rc;
-  uint8_t* H = h->up_h.h;
-  PoseQ* poses = reinterpret_cast<PoseQ*>(H + o_poses);
-  double* points = reinterpret_cast<double*>(H + o_points);
-  int* pose_col = reinterpret_cast<int*>(H + o_pose_col); int* point_col = reinterpret_cast<int*>(H + o_point_col);
-  int* pt_start = reinterpret_cast<int*>(H + o_pt_start); int* pt_edges = reinterpret_cast<int*>(H + o_pt_edges);
-  int* ps_start = reinterpret_cast<int*>(H + o_ps_start); int* ps_edges = reinterpret_cast<int*>(H + o_ps_edges);
-  int* pf_start = reinterpret_cast<int*>(H + o_pf_start); int* pf_edges = reinterpret_cast<int*>(H + o_pf_edges);
-  int* pf_col = reinterpret_cast<int*>(H + o_pf_col);
-  int* pair_i1 = reinterpret_cast<int*>(H + o_pair_i1); int* pair_i2 = reinterpret_cast<int*>(H + o_pair_i2);
-  int* pair_start = reinterpret_cast<int*>(H + o_pair_start);
-  unsigned long long* lm_mask = reinterpret_cast<unsigned long long*>(H + o_lm_mask);
-  PairItem* items = reinterpret_cast<PairItem*>(H + o_items);
-  const double t_s1 = now_s();
-  memcpy(pose_col, pose_col_v.data(), 4 * (size_t)NP);
-  memcpy(point_col, point_col_v.data(), 4 * (size_t)NX);
-  // CSR: edges per active point (creation order); per free pose; per active point restricted to free poses (sorted by col)
-  pt_start[0] = 0; pf_start[0] = 0; ps_start[0] = 0;
-  for (int i = 0; i < nL; i++) { pt_start[i + 1] = pt_start[i] + pt_cnt[i]; pf_start[i + 1] = pf_start[i] + pf_deg[i]; }
-  for (int i = 0; i < nP; i++) ps_start[i + 1] = ps_start[i] + ps_cnt[i];
-  if (dev_csr) {
-    memcpy(H + o_cur_pt, pt_start, 4 * (size_t)nL); memcpy(H + o_cur_ps, ps_start, 4 * (size_t)nP); memcpy(H + o_cur_pf, pf_start, 4 * (size_t)nL);
-  } else {
+  // ---- structure, 3: CSR lists: edges per active point (creation order); per free pose; per active point restricted to free
+  // poses (sorted by col later: pair_items, or the device)
+  void fill_lists() {
+    constexpr bool kRig = std::is_same<CamT, CamRig>::value;
+    const Arena A = H;
+    const lba_edge* const edges = h->edges_pin.h;
+    memcpy(A.pose_col, h->s_pose_col.data(), 4 * (size_t)NP);
+    memcpy(A.point_col, h->s_point_col.data(), 4 * (size_t)NX);
+    const std::vector<int>& pt_cnt = h->s_f1; const std::vector<int>& ps_cnt = h->s_f2; const std::vector<int>& pf_deg = h->s_pf_deg;
+    A.pt_start[0] = 0; A.pf_start[0] = 0; A.ps_start[0] = 0;
+    for (int i = 0; i < nL; i++) { A.pt_start[i + 1] = A.pt_start[i] + pt_cnt[i]; A.pf_start[i + 1] = A.pf_start[i] + pf_deg[i]; }
+    for (int i = 0; i < nP; i++) A.ps_start[i + 1] = A.ps_start[i] + ps_cnt[i];
+    if (dev_csr) {
+      memcpy(A.cur_pt, A.pt_start, 4 * (size_t)nL); memcpy(A.cur_ps, A.ps_start, 4 * (size_t)nP); memcpy(A.cur_pf, A.pf_start, 4 * (size_t)nL);
+      return;
+    }
     std::vector<int>& f1 = h->s_f1; std::vector<int>& f2 = h->s_f2; std::vector<int>& f3 = h->s_f3;
     if (runs == nL && !kRig) {
       // every landmark's edges are consecutive (the reference's order): a landmark's list positions are carried in registers along
-      // its run instead of in per-landmark cursors (the same store-to-load chains as above), and the "pose is free" test selects
-      // the destination (a junk word for edges of fixed poses) instead of branching on a one-in-three condition
-      f2.assign(ps_start, ps_start + nP);
+      // its run instead of in per-landmark cursors (the same store-to-load chains as in edge_pass), and the "pose is free" test
+      // selects the destination (a junk word for edges of fixed poses) instead of branching on a one-in-three condition
+      f2.assign(A.ps_start, A.ps_start + nP);
       f2.push_back(0);                                       // [nP]: cursor of the edges of fixed poses, into junk
       std::vector<int>& junk = h->s_junk;
       if ((int)junk.size() < NE + 1) junk.resize((size_t)NE + 1);
-      int* const ps_base[2] = {junk.data(), ps_edges};
+      int* const ps_base[2] = {junk.data(), A.ps_edges};
       int* const f2p = f2.data();
       int prev = -1, pt_pos = 0, pf_pos = 0;
       for (int k = 0; k < NE; k++) {
-        const int ex = edges[k].point, lc = point_col[ex], pc = pose_col[edges[k].pose];
+        const int ex = edges[k].point, lc = A.point_col[ex], pc = A.pose_col[edges[k].pose];
         const bool ch = ex != prev;
         prev = ex;
-        pt_pos = ch ? pt_start[lc] : pt_pos;
-        pf_pos = ch ? pf_start[lc] : pf_pos;
-        pt_edges[pt_pos++] = k;
+        pt_pos = ch ? A.pt_start[lc] : pt_pos;
+        pf_pos = ch ? A.pf_start[lc] : pf_pos;
+        A.pt_edges[pt_pos++] = k;
         const int fr = pc >= 0;
         ps_base[fr][f2p[fr ? pc : nP]++] = k;
-        int* const pf_dst = fr ? pf_edges + pf_pos : junk.data() + NE;
+        int* const pf_dst = fr ? A.pf_edges + pf_pos : junk.data() + NE;
         *pf_dst = k;
         pf_pos += fr;
       }
     } else {
-      f1.assign(pt_start, pt_start + nL); f2.assign(ps_start, ps_start + nP); f3.assign(pf_start, pf_start + nL);
+      f1.assign(A.pt_start, A.pt_start + nL); f2.assign(A.ps_start, A.ps_start + nP); f3.assign(A.pf_start, A.pf_start + nL);
       for (int k = 0; k < NE; k++) {
-        const int lc = point_col[edges[k].point], pc = pose_col[edges[k].pose];
-        pt_edges[f1[lc]++] = k;
+        const int lc = A.point_col[edges[k].point], pc = A.pose_col[edges[k].pose];
+        A.pt_edges[f1[lc]++] = k;
         if (pc >= 0) {
-          ps_edges[f2[pc]++] = k;
-          if (!kRig || !rig_secondary[k]) pf_edges[f3[lc]++] = k;
+          A.ps_edges[f2[pc]++] = k;
+          if (!kRig || !rig_secondary[k]) A.pf_edges[f3[lc]++] = k;
         }
       }
     }
   }
-  const double t_s2 = now_s();
   // ---- initial state: Converter::toSE3Quat (S/Converter.cc:33-43)
-  for (int i = 0; i < NP; i++) {
-    const float* T = p->poses + 16 * (size_t)i;
-    const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
-    quat_from_R(R, poses[i].q);
-    quat_normalize(poses[i].q);
-    poses[i].t[0] = T[3]; poses[i].t[1] = T[7]; poses[i].t[2] = T[11];
-  }
-  for (size_t i = 0; i < 3 * (size_t)NX; i++) points[i] = p->points[i];
-
-  const int n = 6 * nP;
-  const int n_blocks_e = (NE + 255) / 256;
-  const double t_b = now_s();
-  // part A of the arena (edges, state, the CSR lists the error / linearisation kernels read) goes up now; the pair items
-  // the Schur kernel needs are built while the device already computes the first residuals and Jacobians
-  // part A: host-filled arrays; + the point / pose lists when the host fills them; + the unsorted free-observation lists when
-  // the device only sorts
-  const size_t off_a = dev_csr ? o_pt_edges : dev_lists ? o_pf_col : o_pf_edges;
-  if ((rc = upload_arena(h, 0, off_a, st))) return rc;
-  struct {
-    const lba_edge* edges; const int *pose_col, *point_col, *pt_start, *pt_edges, *ps_start, *ps_edges, *pf_start, *pf_edges, *pf_col,
-        *pair_i1, *pair_i2, *pair_start;
-    const PairItem* items;
-  } D;
-  {
-    const uint8_t* B = h->up_d.p;
-    D.edges = h->d_edges.p;
-    D.pose_col = reinterpret_cast<const int*>(B + o_pose_col); D.point_col = reinterpret_cast<const int*>(B + o_point_col);
-    D.pt_start = reinterpret_cast<const int*>(B + o_pt_start); D.pt_edges = reinterpret_cast<const int*>(B + o_pt_edges);
-    D.ps_start = reinterpret_cast<const int*>(B + o_ps_start); D.ps_edges = reinterpret_cast<const int*>(B + o_ps_edges);
-    D.pf_start = reinterpret_cast<const int*>(B + o_pf_start); D.pf_edges = reinterpret_cast<const int*>(B + o_pf_edges);
-    D.pf_col = reinterpret_cast<const int*>(B + o_pf_col);
-    D.pair_i1 = reinterpret_cast<const int*>(B + o_pair_i1); D.pair_i2 = reinterpret_cast<const int*>(B + o_pair_i2);
-    if (dev_lists) { D.pair_i1 = nullptr; D.pair_i2 = nullptr; }
-    D.pair_start = dev_items ? (const int*)nullptr : reinterpret_cast<const int*>(B + o_pair_start);
-    D.items = dev_items ? (const PairItem*)nullptr : reinterpret_cast<const PairItem*>(B + o_items);
-  }
-  if (dev_items) {
-    if ((rc = h->d_items_dev.reserve((size_t)n_pairs_all * item_cap)) || (rc = h->d_pair_count.reserve(std::max(n_pairs_all, 1)))) return rc;
-    D.items = h->d_items_dev.p;
-  }
-  // the three state buffers (current / trial estimate / the trial after it, written on speculation by the fused solve + update
-  // launch): buffer 0 IS the uploaded state inside the arena (part A is not written again during the solve; two device-to-device
-  // copies of a few KB cost the stream ~10 us each before the first residuals), buffers 1 and 2 allocations of their own.
-  // They rotate: trial = (cur + 1) % 3, and an accepted trial becomes the current estimate.
-  if ((rc = h->d_poses[1].reserve(std::max(NP, 1))) || (rc = h->d_points[1].reserve(std::max<size_t>(3 * (size_t)NX, 1))) ||
-      (rc = h->d_poses[0].reserve(std::max(NP, 1))) || (rc = h->d_points[0].reserve(std::max<size_t>(3 * (size_t)NX, 1))) ||
-      (rc = h->d_err.reserve(std::max<size_t>(3 * (size_t)NE, 1))) || (rc = h->d_chi2.reserve(std::max(NE, 1))) ||
-      (rc = h->d_partial.reserve(std::max(n_blocks_e, 1))) || (rc = h->d_EB.reserve(std::max<size_t>((size_t)NE * kEB, 1))) ||
-      (rc = h->d_Hll.reserve(std::max<size_t>(6 * (size_t)nL, 1))) || (rc = h->d_bl.reserve(std::max<size_t>(3 * (size_t)nL, 1))) ||
-      (rc = h->d_Hpp.reserve(std::max<size_t>(21 * (size_t)nP, 1))) || (rc = h->d_bp.reserve(std::max<size_t>(6 * (size_t)nP, 1))) ||
-      (rc = h->d_EB2.reserve(std::max<size_t>((size_t)NE * kEB, 1))) || (rc = h->d_Hll2.reserve(std::max<size_t>(6 * (size_t)nL, 1))) ||
-      (rc = h->d_bl2.reserve(std::max<size_t>(3 * (size_t)nL, 1))) || (rc = h->d_Hpp2.reserve(std::max<size_t>(21 * (size_t)nP, 1))) ||
-      (rc = h->d_bp2.reserve(std::max<size_t>(6 * (size_t)nP, 1))) || (rc = h->d_lambda0.reserve(4)) ||
-      (rc = h->d_S.reserve(std::max<size_t>((size_t)n * n, 1))) || (rc = h->d_bs.reserve(std::max(n, 1))) ||
-      (rc = h->d_x.reserve(std::max<size_t>((size_t)n + 3 * (size_t)nL, 1))))
-    return rc;
-  PoseQ* const posesB[3] = {reinterpret_cast<PoseQ*>(h->up_d.p + o_poses), h->d_poses[1].p, h->d_poses[0].p};
-  double* const pointsB[3] = {reinterpret_cast<double*>(h->up_d.p + o_points), h->d_points[1].p, h->d_points[0].p};
-
-  const double t_c = now_s();
-  Huber hb;
-  hb.delta_mono = (float)std::sqrt(5.991); hb.dsqr_mono = hb.delta_mono * hb.delta_mono;          // S/Optimizer.cc:1991-1992
-  hb.delta_stereo = (float)std::sqrt(7.815); hb.dsqr_stereo = hb.delta_stereo * hb.delta_stereo;
-  // FP64 matrix-core LDL^T (ldlt_mfma.hpp): up to 50 free poses
-  const bool force_wide = sw.ldlt_wide;          // test switch: k_wide_* at any size
-  const bool use_mfma = nP >= 1 && ldltm::supports(n) && !force_wide;
-  // windows beyond the matrix-core kernels (more than 50 free poses): blocked LDL^T over many workgroups
-  const bool use_wide = nP >= 1 && !use_mfma;
-  if (use_wide && n > kWideMaxUnknowns) return ORBG_CAP_EXCEEDED;      // (k_wide_back's x lives in LDS)
-  if (use_wide && (rc = h->d_wide.reserve(2 * (size_t)n + 32))) return rc;
-  if (use_mfma) {
-    if ((rc = h->d_St.reserve(ldltm::tile_image_doubles(n))) || (rc = h->d_wfac.reserve(ldltm::wglob_doubles(ldltm::make_geo(n))))) return rc;
-  }
-  // 21 .. 50 free poses: the same tile image, factored by eight workgroups of one XCD (ldlt_xcd.hpp)
-  const bool use_xcd = use_mfma && sw.ldlt_xcd != 0 && ldltx::pays(n);
-  if (use_xcd && !h->ldlt_x.scr) {
-    if ((rc = h->d_xscr.reserve(ldltx::scratch_doubles())) || (rc = h->d_xflags.reserve(ldltx::kFlagWords))) return rc;
-    ORBG_HIP(hipMemsetAsync(h->d_xflags.p, 0, ldltx::kFlagWords * sizeof(unsigned), st));
-    // (the G / D^-1 pair region: a fresh nonce per bind already makes stale pairs of a recycled allocation fail their test; zero all the same)
-    ORBG_HIP(hipMemsetAsync(h->d_xscr.p + ldltx::kGbOff, 0, (ldltx::kWOff - ldltx::kGbOff) * sizeof(double), st));
-    h->ldlt_x.bind(h->d_xscr.p, h->d_xflags.p);
-    static std::atomic<int> n_users{0};              // users of one process on different XCDs; processes sharing a GPU differ by pid
-    h->ldlt_x.pick = ((int)getpid() + n_users.fetch_add(1)) & 7;
-  }
-  int cur = 0;   // index of the buffer holding the current estimate
-  // k_update's workgroup size: the kernel is a chain of dependent memory round trips per landmark; small workgroups spread the same
-  // wavefronts over more compute units (measured at C2: 256 threads 0.499 ms per solve, 128: 0.488, 64: 0.484)
-  constexpr int upd_threads = 64;
-  const int n_blocks_u = (NP + NX + upd_threads - 1) / upd_threads;
-  if ((rc = h->d_scale_partial.reserve(std::max(n_blocks_u, 1)))) return rc;
-  if (!h->d_ticket.p) {
-    if ((rc = h->d_ticket.reserve(4))) return rc;
-    ORBG_HIP(hipMemsetAsync(h->d_ticket.p, 0, 4 * sizeof(unsigned), st));
-  }
-  // final_mode: the last block also publishes {robust chi2, computeScale(), solver flag} to the host record
-  auto launch_errors = [&](int buf, int final_mode) {
-    if (NE > 0)
-      hipLaunchKernelGGL(k_errors<CamT>, dim3(n_blocks_e), dim3(256), 0, st, NE, D.edges, posesB[buf], pointsB[buf], cam, hb,
-                         h->d_err.p, h->d_chi2.p, h->d_partial.p, final_mode, h->d_ticket.p, h->d_scale_partial.p, n_blocks_u,
-                         h->d_ok.p, h->rec.d, final_mode ? ++h->rec_seq : 0u);
-  };
-  // two sets of linearisation outputs: while the host waits for the verdict on a trial, the linearisation of the TRIAL
-  // state (= the next iteration's, if the trial is accepted -- the usual case) is already running into the other set
-  double* const EBs[2] = {h->d_EB.p, h->d_EB2.p};
-  double* const Hlls[2] = {h->d_Hll.p, h->d_Hll2.p};
-  double* const bls[2] = {h->d_bl.p, h->d_bl2.p};
-  double* const Hpps[2] = {h->d_Hpp.p, h->d_Hpp2.p};
-  double* const bps[2] = {h->d_bp.p, h->d_bp2.p};
-  int ls = 0;                      // linearisation set of the current iteration
-  bool spec_ready = false;         // set ls^1 holds the linearisation of the current estimate
-  auto launch_linearise = [&](int buf, int set) {
-    if (NE > 0 || nP > 0)
-      hipLaunchKernelGGL(k_lin_all<CamT>, dim3(nP + (NE > 0 ? n_blocks_e : 0)), dim3(256), 0, st, nP, NE, D.edges, posesB[buf],
-                         pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, EBs[set], D.ps_start,
-                         D.ps_edges, Hpps[set], bps[set]);
-    if (nL > 0)
-      hipLaunchKernelGGL(k_reduce_points, dim3((nL + 255) / 256), dim3(256), 0, st, nL, D.pt_start, D.pt_edges, EBs[set],
-                         Hlls[set], bls[set]);
-  };
-  auto finish = [&](double lambda, int want_scale, int want_maxdiag, bool with_ok) -> int {
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, bps[ls], bls[ls], Hpps[ls],
-                       Hlls[ls], lambda, with_ok ? h->d_ok.p : (int*)nullptr, want_scale, want_maxdiag, h->rec.d, 0.0, (double*)nullptr);
-    ORBG_HIP(hipGetLastError());
-    ORBG_HIP(hipStreamSynchronize(st));
-    return with_ok && h->rec.h->ok == ldltx::kOkTimedOut ? kRcLdltTimedOut : ORBG_OK;
-  };
-  auto poll_record = [&]() -> int {
-    // the last workgroup of k_errors publishes the record and then its sequence number: spin on that word (the
-    // runtime's completion path costs ~10 us per LM trial); fall back to a stream sync if it does not arrive
-    volatile unsigned* w = &h->rec.h->seq;
-    const unsigned want = h->rec_seq;
-    bool got = false;
-    if (orbg::poll_allowed()) {              // (the policy of the thread that runs the solve: caller or local-BA worker)
-      timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-      const unsigned long long tg = rec_tag(want);
-      const volatile HostRec* hr = h->rec.h;
-      for (unsigned spins = 0; !got; spins++) {
-        if (*w == want) {
-          // ... and the three pairs of THIS record have arrived (they and seq are independent stores)
-          const double c = hr->chi2, sc = hr->scale; const int okv = hr->ok;
-          unsigned long long bc, bs; memcpy(&bc, &c, 8); memcpy(&bs, &sc, 8);
-          if ((bc ^ hr->c_chi2) == tg && (bs ^ hr->c_scale) == tg && (((unsigned long long)(unsigned)okv) ^ hr->c_ok) == tg) { got = true; break; }
-        }
-        if ((spins & 0xFFFF) == 0xFFFF) {
-          timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-          if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 50.0) break;
-        }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  void initial_state() {
+    for (int i = 0; i < NP; i++) {
+      const float* T = p->poses + 16 * (size_t)i;
+      const double R[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+      quat_from_R(R, H.poses[i].q);
+      quat_normalize(H.poses[i].q);
+      H.poses[i].t[0] = T[3]; H.poses[i].t[1] = T[7]; H.poses[i].t[2] = T[11];
     }
-    if (!got) ORBG_HIP(hipStreamSynchronize(st));
-    if (h->rec.h->ok == kOkPublishTimedOut) return ORBG_INTERNAL;      // (a fused linearisation's publisher never saw all edge workgroups arrive)
-    // the eight-workgroup LDL^T gave up waiting for a participant: not an LM verdict -- the caller re-solves the window (lba_solve_impl)
-    return h->rec.h->ok == ldltx::kOkTimedOut ? kRcLdltTimedOut : ORBG_OK;
-  };
+    for (size_t i = 0; i < 3 * (size_t)NX; i++) H.points[i] = p->points[i];
+  }
 
-  // results block (one pinned allocation the export kernel writes straight into) and its launcher: also used speculatively
-  size_t doff = 0;
-  auto dtake = [&](size_t bytes) { const size_t o = doff; doff = (doff + bytes + 63) & ~(size_t)63; return o; };
-  const size_t d_poses_o = dtake(sizeof(PoseQ) * (size_t)NP), d_points_o = dtake(24 * (size_t)NX), d_flags_o = dtake((size_t)NE);
-  const size_t d_chi_o = dtake(r->edge_chi2 ? 8 * (size_t)NE : 0);
-  if ((rc = h->dl_h.reserve(doff + 64))) return rc;
-  auto launch_export = [&](int buf) {
-    const int n_thr = std::max(std::max(NE, NP), 3 * NX);
-    if (n_thr > 0)
-      hipLaunchKernelGGL(k_export<CamT>, dim3((n_thr + 255) / 256), dim3(256), 0, st, NE, NP, NX, D.edges, posesB[buf], pointsB[buf], cam,
-                         h->d_chi2.p, h->dl_h.d + d_flags_o, r->edge_chi2 ? reinterpret_cast<double*>(h->dl_h.d + d_chi_o) : (double*)nullptr,
-                         reinterpret_cast<PoseQ*>(h->dl_h.d + d_poses_o), reinterpret_cast<double*>(h->dl_h.d + d_points_o));
-  };
-  // Speculation beyond the next linearisation: `version` counts LM trials; work launched for "this trial gets accepted and
-  // ends the round / the solve" is valid only if no later trial ran and the trial's buffer became the current one.
-  int version = 0;
-  int fin_version = -1;            // k_finish (lambda init of the NEXT round) already ran on the speculative set
-  int exp_version = -1, exp_buf = -1;   // k_export of the trial state already in flight (completion word posted)
+  // ---- buffers: part A of the arena goes up now (the pair items the Schur kernel needs are built while the device already
+  // computes the first residuals and Jacobians), and the device buffers of this size are reserved
+  int buffers() {
+    int rc;
+    if ((rc = upload_arena(h, 0, off_a, st))) return rc;
+    d_edges = h->d_edges.p;
+    D = at(h->up_d.p);
+    if (dev_lists) { D.pair_i1 = nullptr; D.pair_i2 = nullptr; }      // (k_schur derives the pair from its index)
+    if (dev_items) {
+      D.pair_start = nullptr;
+      if ((rc = h->d_items_dev.reserve((size_t)n_pairs_all * item_cap)) || (rc = h->d_pair_count.reserve(std::max(n_pairs_all, 1)))) return rc;
+      D.items = h->d_items_dev.p;
+    }
+    // the three state buffers (current / trial estimate / the trial after it, written on speculation by the fused solve + update
+    // launch): buffer 0 IS the uploaded state inside the arena (part A is not written again during the solve; two device-to-device
+    // copies of a few KB cost the stream ~10 us each before the first residuals), buffers 1 and 2 allocations of their own.
+    if ((rc = h->d_poses[1].reserve(std::max(NP, 1))) || (rc = h->d_points[1].reserve(std::max<size_t>(3 * (size_t)NX, 1))) ||
+        (rc = h->d_poses[0].reserve(std::max(NP, 1))) || (rc = h->d_points[0].reserve(std::max<size_t>(3 * (size_t)NX, 1))) ||
+        (rc = h->d_err.reserve(std::max<size_t>(3 * (size_t)NE, 1))) || (rc = h->d_chi2.reserve(std::max(NE, 1))) ||
+        (rc = h->d_partial.reserve(std::max(n_blocks_e, 1))) || (rc = h->lin[0].reserve(NE, nL, nP)) ||
+        (rc = h->lin[1].reserve(NE, nL, nP)) || (rc = h->d_lambda0.reserve(4)) ||
+        (rc = h->d_S.reserve(std::max<size_t>((size_t)n * n, 1))) || (rc = h->d_bs.reserve(std::max(n, 1))) ||
+        (rc = h->d_x.reserve(std::max<size_t>((size_t)n + 3 * (size_t)nL, 1))))
+      return rc;
+    posesB[0] = D.poses; posesB[1] = h->d_poses[1].p; posesB[2] = h->d_poses[0].p;
+    pointsB[0] = D.points; pointsB[1] = h->d_points[1].p; pointsB[2] = h->d_points[0].p;
+    return ORBG_OK;
+  }
+  // ---- the solver of the reduced camera system, the record's scratch, the results block
+  int pick_solver() {
+    int rc;
+    // FP64 matrix-core LDL^T (ldlt_mfma.hpp): up to 50 free poses (ORBG_LDLT_WIDE=1: k_wide_* at any size)
+    use_mfma = nP >= 1 && ldltm::supports(n) && !h->sw.ldlt_wide;
+    // windows beyond the matrix-core kernels (more than 50 free poses): blocked LDL^T over many workgroups
+    use_wide = nP >= 1 && !use_mfma;
+    if (use_wide && n > kWideMaxUnknowns) return ORBG_CAP_EXCEEDED;      // (k_wide_back's x lives in LDS)
+    if (use_wide && (rc = h->d_wide.reserve(2 * (size_t)n + 32))) return rc;
+    if (use_mfma) {
+      if ((rc = h->d_St.reserve(ldltm::tile_image_doubles(n))) || (rc = h->d_wfac.reserve(ldltm::wglob_doubles(ldltm::make_geo(n))))) return rc;
+    }
+    // 21 .. 50 free poses: the same tile image, factored by eight workgroups of one XCD (ldlt_xcd.hpp)
+    use_xcd = use_mfma && h->sw.ldlt_xcd != 0 && ldltx::pays(n);
+    if (use_xcd && !h->ldlt_x.scr) {
+      if ((rc = h->d_xscr.reserve(ldltx::scratch_doubles())) || (rc = h->d_xflags.reserve(ldltx::kFlagWords))) return rc;
+      ORBG_HIP(hipMemsetAsync(h->d_xflags.p, 0, ldltx::kFlagWords * sizeof(unsigned), st));
+      // (the G / D^-1 pair region: a fresh nonce per bind already makes stale pairs of a recycled allocation fail their test; zero all the same)
+      ORBG_HIP(hipMemsetAsync(h->d_xscr.p + ldltx::kGbOff, 0, (ldltx::kWOff - ldltx::kGbOff) * sizeof(double), st));
+      h->ldlt_x.bind(h->d_xscr.p, h->d_xflags.p);
+      static std::atomic<int> n_users{0};              // users of one process on different XCDs; processes sharing a GPU differ by pid
+      h->ldlt_x.pick = ((int)getpid() + n_users.fetch_add(1)) & 7;
+    }
+    n_blocks_u = (NP + NX + kUpdThreads - 1) / kUpdThreads;
+    if ((rc = h->d_scale_partial.reserve(std::max(n_blocks_u, 1)))) return rc;
+    if (!h->d_ticket.p) {
+      if ((rc = h->d_ticket.reserve(4))) return rc;
+      ORBG_HIP(hipMemsetAsync(h->d_ticket.p, 0, 4 * sizeof(unsigned), st));
+    }
+    // the results block: one pinned allocation the export kernels write straight into
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 63) & ~(size_t)63; return o; };
+    o_rposes = take(sizeof(PoseQ) * (size_t)NP); o_rpoints = take(24 * (size_t)NX); o_rflags = take((size_t)NE);
+    o_rchi = take(r->edge_chi2 ? 8 * (size_t)NE : 0);
+    if ((rc = h->dl_h.reserve(off + 64))) return rc;
+    out.flags = h->dl_h.d + o_rflags;
+    out.chi2 = r->edge_chi2 ? reinterpret_cast<double*>(h->dl_h.d + o_rchi) : (double*)nullptr;
+    out.poses = reinterpret_cast<PoseQ*>(h->dl_h.d + o_rposes);
+    out.points = reinterpret_cast<double*>(h->dl_h.d + o_rpoints);
+    prof_this_solve = h->prof_on && (h->prof_solves++ & 3) == 0;
+    return ORBG_OK;
+  }
 
-  int solve_version = -1;          // Schur complement + LDL^T of the NEXT trial already launched (speculatively) at this trial number
-  bool prof_pending = false;       // an event pair brackets one LDL^T launch of this call
-  const bool prof_this_solve = h->prof_on && (h->prof_solves++ & 3) == 0;
-  // in_buf / out_buf: with the fused launch the trial state posesB[out_buf] = posesB[in_buf] (+) x is written by the same launch
-  auto launch_solve = [&](int set_, double lam_, const double* lamp_, int in_buf, int out_buf) -> int {
-    if (nP > 0) {
-      // (more pose pairs than compute units: the two-pass form, three workgroups per compute unit)
-      const auto schur_fn = n_pairs_all > 256 ? k_schur<2> : k_schur<1>;
-      hipLaunchKernelGGL(schur_fn, dim3(n_pairs_all), dim3(kSchurThreads), 0, st, nP, D.pair_i1, D.pair_i2, D.pair_start, D.items,
-                         EBs[set_], Hlls[set_], bls[set_], Hpps[set_], bps[set_], lam_, h->d_S.p, h->d_bs.p, lamp_, item_cap,
-                         dev_items ? h->d_pair_count.p : (const int*)nullptr, use_mfma ? h->d_St.p : (double*)nullptr);
-      // (two event records and an elapsed-time query cost the solve ~8 us: one solve in four is enough for an average)
-      const bool bracket = h->prof_on && !prof_pending && prof_this_solve;
-      if (bracket) ORBG_HIP(hipEventRecord(h->prof_ev[0], st));
-      if (use_xcd) {
-        const bool one_short = h->sw.ldlt_xcd_short_once;
-        h->sw.ldlt_xcd_short_once = false;
-        ORBG_HIP(ldltx::launch(h->ldlt_x, n, h->d_St.p, h->d_x.p, h->d_ok.p, st, ldltx::kMaxP, sw.ldlt_xcd == 2, one_short));
-      } else if (use_mfma) {
-        ORBG_HIP(ldltm::launch(n, h->d_St.p, h->d_x.p, h->d_ok.p, h->d_wfac.p, st, &h->ldlt_attr));
-      } else {
-        ORBG_HIP(launch_ldlt_wide(n, h->d_S.p, h->d_bs.p, h->d_x.p, h->d_ok.p, h->d_wide.p, st));
+  // ---- the first residuals + linearisation, launched before the host has finished the structure, into set ls ^ 1: the first
+  // iteration takes it (spec_ready); then what the first Schur complement needs besides
+  int first_linearisation() {
+    // first iteration in two launches (k_errlin_prep, k_finish_items) where the observation lists are sorted on the device
+    first2 = dev_lists && NE > 0 && nL > 0 && !stop();
+    if (first2 || !stop()) {
+      const int set = lm.ls ^ 1;
+      if (first2) {
+        if (dev_csr) {
+          hipLaunchKernelGGL(k_csr_fill, dim3(n_blocks_e), dim3(256), 0, st, NE, d_edges, D.pose_col, D.point_col, D.cur_pt, D.cur_ps,
+                             D.cur_pf, D.pt_edges, D.ps_edges, D.pf_edges);
+          const int n_blocks_l = (nL + 255) / 256;              // (k_csr_sort: one thread per landmark)
+          hipLaunchKernelGGL(k_csr_sort, dim3(nP + n_blocks_l + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, nP, nL, D.ps_start,
+                             D.ps_edges, D.pt_start, D.pt_edges, D.pf_start, D.pf_edges, D.pf_col, D.lm_mask, d_edges, D.pose_col, n,
+                             use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
+          errlin(lm.cur, set, false, LmIn{});
+        } else {
+          errlin_prep(lm.cur, set);
+        }
+        finish_items(set);
+        lm.fin_version = lm.version;
+      } else if (NE > 0) {
+        errlin(lm.cur, set, false, LmIn{});
+        finish_lambda_init(set);           // the first round's lambda init needs nothing the host is still building
+        lm.fin_version = lm.version;
       }
-      if (bracket) { ORBG_HIP(hipEventRecord(h->prof_ev[1], st)); prof_pending = true; }
+      ORBG_HIP(hipGetLastError());
+      lm.err_valid = true;
+      lm.spec_ready = true;
+    }
+    // not needed before the first Schur complement: the zeroed step vector and the padding / zeros of the bordered tile image
+    // (they depend on n only, k_schur never touches them -- once per call) go behind the first linearisation
+    if (first2) return ORBG_OK;            // (k_errlin_prep / k_csr_sort did that)
+    if (dev_lists) {
+      // ... in one launch with the per-landmark lists (k_prep)
+      const int nsb = (nL + kSortPfThreads - 1) / kSortPfThreads;
+      hipLaunchKernelGGL(k_prep, dim3(nsb + 32 + 8), dim3(kSortPfThreads), 0, st, nsb, nL, D.pf_start, D.pf_edges, D.pf_col, D.lm_mask,
+                         d_edges, D.pose_col, n, use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
+      ORBG_HIP(hipGetLastError());
     } else {
-      ORBG_HIP(hipMemsetAsync(h->d_ok.p, 0xFF, sizeof(int), st));   // nothing to solve: ok
+      ORBG_HIP(hipMemsetAsync(h->d_x.p, 0, (size_t)n_zero * sizeof(double), st));
+      if (use_mfma) ORBG_HIP(ldltm::launch_image_pad(n, h->d_St.p, st));
     }
     return ORBG_OK;
-  };
-  double lambda = -1, ni = 2;
-  int nBad = 0;
-  bool first_chi = true;
-  bool err_valid = false;          // d_err / d_chi2 hold the residuals of the CURRENT estimate
-  double currentChi = 0;
-  bool last_round = false;
-  auto optimize = [&](int iterations, int* done_out) -> int {
-    int done = 0;
+  }
+
+  // ---- while those run: the rest of the structure -- the pose pairs (i1 <= i2) and their landmark items, built here (grouped by
+  // pair: a counting sort keeps landmark order) or on the device, and the rest of the arena's uploads
+  int pair_items() {
+    const Arena A = H;
+    const lba_edge* const edges = h->edges_pin.h;
+    if (!dev_lists) {
+      // per landmark: stable insertion sort of its free observations by pose column (a handful each), then its pose mask (device
+      // items) or the count of its (pose pair) items; pair id = row_off[i1] + i2
+      std::vector<int>& row_off = h->s_row_off;
+      row_off.resize(std::max(nP, 1));
+      for (int i1 = 0; i1 < nP; i1++) row_off[i1] = i1 * nP - i1 * (i1 - 1) / 2 - i1;
+      for (int i = 0; i <= n_pairs_all; i++) A.pair_start[i] = 0;
+      for (int l = 0; l < nL; l++) {
+        const int b0 = A.pf_start[l], e0 = A.pf_start[l + 1];
+        for (int a2 = b0 + 1; a2 < e0; a2++) {
+          const int e = A.pf_edges[a2], key = A.pose_col[edges[e].pose];
+          int b2 = a2 - 1;
+          while (b2 >= b0 && A.pose_col[edges[A.pf_edges[b2]].pose] > key) { A.pf_edges[b2 + 1] = A.pf_edges[b2]; b2--; }
+          A.pf_edges[b2 + 1] = e;
+        }
+        for (int j = b0; j < e0; j++) A.pf_col[j] = A.pose_col[edges[A.pf_edges[j]].pose];
+        if (dev_items) {
+          unsigned long long m = 0;
+          for (int j = b0; j < e0; j++) m |= 1ull << A.pf_col[j];
+          A.lm_mask[l] = m;
+        } else {
+          for (int a2 = b0; a2 < e0; a2++) {
+            const int ro = row_off[A.pf_col[a2]] + 1;
+            for (int b2 = a2; b2 < e0; b2++) A.pair_start[ro + A.pf_col[b2]]++;
+          }
+        }
+      }
+    }
+    // the pair table, a function of nP alone: every pair (diagonals always; off-diagonals even if empty so that S is fully written)
+    for (int i1 = 0, id = 0; i1 < nP; i1++)
+      for (int i2 = i1; i2 < nP; i2++, id++) { A.pair_i1[id] = i1; A.pair_i2[id] = i2; }
+    int rc;
+    if (dev_items) {
+      if (stop()) return ORBG_OK;
+      // the pf lists and pose masks go up next (with the pair table: nothing is left for a third upload) and the device builds the
+      // pair items behind the first linearisation
+      if (!dev_lists && (rc = upload_arena(h, off_a, o_pair_start, st))) return rc;      // (dev_lists: k_schur derives the pair from its index)
+      if (nL > 0 && !first2)
+        hipLaunchKernelGGL(k_build_items, dim3(n_pairs_all), dim3(256), 0, st, nP, nL, D.lm_mask, D.pf_start, D.pf_edges, D.pf_col,
+                           h->d_items_dev.p, item_cap, h->d_pair_count.p);
+      ORBG_HIP(hipGetLastError());
+      return ORBG_OK;
+    }
+    for (int i = 0; i < n_pairs_all; i++) A.pair_start[i + 1] += A.pair_start[i];
+    std::vector<int>& fill = h->s_fill;
+    fill.assign(A.pair_start, A.pair_start + n_pairs_all);
+    const std::vector<int>& row_off = h->s_row_off;
+    for (int l = 0; l < nL; l++) {
+      const int b0 = A.pf_start[l], e0 = A.pf_start[l + 1];
+      for (int a2 = b0; a2 < e0; a2++) {
+        const int ro = row_off[A.pf_col[a2]], ea = A.pf_edges[a2];
+        for (int b2 = a2; b2 < e0; b2++) A.items[fill[ro + A.pf_col[b2]]++] = PairItem{ea, A.pf_edges[b2], l};
+      }
+    }
+    return upload_arena(h, off_a, o_end, st);
+  }
+
+  // ---- one LM trial on the device: the solve (unless it already runs), the update into buffer `trial`, the evaluation of the
+  // trial state, and what goes out ahead of the verdict (LmState); returns once the verdict's record is on the host
+  // first_of_spec: the first trial of an iteration that took the speculative set
+  int launch_trial(int trial, bool first_of_spec, bool lambda_on_device, bool round_may_end, bool* speculated) {
+    LmState& m = lm;
+    int rc;
+    const double* lam_p = lambda_on_device ? h->d_lambda0.p : (const double*)nullptr;
+    // the solve of this trial may already be running: it was launched, with the lambda the device computed for the accepted
+    // case, behind the previous trial's residual / linearisation kernel
+    if (!(m.solve_version == m.version - 1 && first_of_spec) && (rc = solve(m.ls, m.lambda, lam_p))) return rc;
+    update(m.cur, trial, m.ls, m.lambda, lam_p);
+    *speculated = false;
+    if (NE == 0) return finish_record(m.ls, m.lambda, 1, 0, true);
+    if (!(m.last_round && round_may_end)) {
+      // speculate on acceptance: residuals + record + linearisation of the trial state into the other set while the host waits
+      const int set = m.ls ^ 1;
+      errlin(trial, set, true, LmIn{m.currentChi, m.lambda, lambda_on_device ? h->d_lambda0.p + 2 : (const double*)nullptr, lam_p,
+                                    h->d_lambda0.p + 1});
+      *speculated = true;
+      // ... and, when the next trial belongs to the same round, its Schur complement + LDL^T with the lambda the device has just
+      // computed for the accepted case: the host's verdict then arrives while they run
+      if (!round_may_end && nP > 0) {
+        if ((rc = solve(set, 0.0, h->d_lambda0.p + 1))) return rc;
+        m.solve_version = m.version;
+      }
+      // ... or, if this trial ends the round, the next round's lambda init
+      if (round_may_end && !lambda_on_device) {
+        finish_lambda_init(set);
+        m.fin_version = m.version;
+      }
+    } else if (!lambda_on_device) {
+      // the last trial of the solve if it is accepted: its evaluation with the export of its state (dropped if it is rejected)
+      errors_export(trial);
+      if ((rc = h->sig.post(st))) return rc;
+      m.exp_version = m.version; m.exp_buf = trial;
+    } else {
+      errors(trial, 1);
+    }
+    ORBG_HIP(hipGetLastError());
+    return poll_record();
+  }
+  // ---- the LM driver: SparseOptimizer::optimize with OptimizationAlgorithmLevenberg::solve as its iteration
+  int optimize(int iterations, int* done_out) {
+    LmState& m = lm;
+    int done = 0, rc;
     bool ok = true;
-    for (int it = 0; it < iterations && !terminate() && ok; it++) {
+    for (int it = 0; it < iterations && !stop() && ok; it++) {
       // computeActiveErrors (skipped when the residuals of the current estimate are already on the device:
       // recomputing them would reproduce the same bits) + buildSystem (skipped when the speculative set holds it)
-      const bool used_spec = spec_ready;
-      if (spec_ready) {
-        ls ^= 1;
-        spec_ready = false;
+      const bool used_spec = m.spec_ready;
+      if (m.spec_ready) {
+        m.ls ^= 1;
+        m.spec_ready = false;
       } else {
-        if (!err_valid) { launch_errors(cur, 0); err_valid = true; }
-        launch_linearise(cur, ls);
+        if (!m.err_valid) { errors(m.cur, 0); m.err_valid = true; }
+        linearise(m.cur, m.ls);
       }
-      int rc2;
       bool lambda_on_device = false;
       if (it == 0) {
         if (NE > 0) {
-          // computeLambdaInit without a host round trip: k_finish leaves lambda in device memory for the first trial
-          // (it may already have run, speculatively, behind the last trial of the previous round)
-          if (!(used_spec && fin_version == version))
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, bps[ls], bls[ls], Hpps[ls],
-                               Hlls[ls], 0.0, (int*)nullptr, 0, 1, h->rec.d, p->lambda_init, h->d_lambda0.p);
+          // computeLambdaInit on the device (it may already have run, speculatively, behind the last trial of the previous round)
+          if (!(used_spec && m.fin_version == m.version)) finish_lambda_init(m.ls);
           lambda_on_device = true;
         } else {
-          if ((rc2 = finish(0.0, 0, 1, false))) return rc2;
-          currentChi = h->rec.h->chi2;
-          lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
+          if ((rc = finish_record(m.ls, 0.0, 0, 1, false))) return rc;
+          m.currentChi = h->rec.h->chi2;
+          m.lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
         }
-        ni = 2; nBad = 0;
+        m.ni = 2; m.nBad = 0;
       }
-      if (!lambda_on_device && first_chi) { r->chi2_initial = currentChi; first_chi = false; }
-      double tempChi = currentChi;
-      double iniChi = currentChi;
+      if (!lambda_on_device && m.first_chi) { r->chi2_initial = m.currentChi; m.first_chi = false; }
+      // the round may end with this iteration: its last one, or the third in a row that barely improves chi2 (nBad >= 3)
+      const bool round_may_end = it + 1 >= iterations || m.nBad >= 2;
+      double iniChi = m.currentChi;
       double rho = 0;
       int qmax = 0;
       do {
-        const int trial = (cur + 1) % 3;
-        version++;
-        const double* lam_p = lambda_on_device ? h->d_lambda0.p : (const double*)nullptr;
-        // the solve of this trial may already be running: it was launched, with the lambda the device computed for the accepted
-        // case, behind the previous trial's residual / linearisation kernel (with the fused launch: its update into `trial` too)
-        if (!(solve_version == version - 1 && qmax == 0 && used_spec) && (rc2 = launch_solve(ls, lambda, lam_p, cur, trial))) return rc2;
-        hipLaunchKernelGGL(k_update<upd_threads>, dim3(n_blocks_u), dim3(upd_threads), 0, st, NP, NX, nP, D.pose_col, D.point_col,
-                           posesB[cur], pointsB[cur], h->d_x.p, D.pf_start, D.pf_edges, D.pf_col, EBs[ls],
-                           Hlls[ls], bls[ls], lambda, posesB[trial], pointsB[trial], bps[ls], h->d_scale_partial.p, lam_p);
-        bool speculated = false, fused_export = false;
-        if (NE > 0) {
-          // speculate on acceptance: linearise the trial state into the other set while the host waits for the verdict
-          // (not after the very last iteration that can run)
-          // ... nor when two iterations in a row barely improved chi2: a third one ends the round (nBad >= 3)
-          const bool may_continue = !(last_round && (it + 1 >= iterations || nBad >= 2));
-          if (may_continue) {
-            // residuals + record + linearisation of the trial state in ONE launch
-            const int set = ls ^ 1;
-            const int n_blocks_l = errlin_tail_blocks(nL);   // the landmark reduction (quads) and the record's publisher ride in the same launch
-            hipLaunchKernelGGL(k_errlin<CamT>, dim3(nP + n_blocks_e + n_blocks_l), dim3(256), 0, st, nP, NE, D.edges, posesB[trial],
-                               pointsB[trial], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, EBs[set], D.ps_start,
-                               D.ps_edges, Hpps[set], bps[set], h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, n_blocks_u, h->d_ok.p,
-                               h->rec.d, ++h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, Hlls[set], bls[set],
-                               LmIn{currentChi, lambda, lambda_on_device ? h->d_lambda0.p + 2 : (const double*)nullptr,
-                                    lambda_on_device ? h->d_lambda0.p : (const double*)nullptr, h->d_lambda0.p + 1});
-            speculated = true;
-            // ... and, when the next trial belongs to the same round, its Schur complement + LDL^T with the lambda the device
-            // has just computed for the accepted case: the host's verdict then arrives while they run
-            if (it + 1 < iterations && nBad < 2 && nP > 0) {
-              // (fused launch: the update of the trial AFTER this one, into the third buffer -- this trial's state stays intact
-              // in case it is rejected, the current estimate in case it is not)
-              if ((rc2 = launch_solve(set, 0.0, h->d_lambda0.p + 1, trial, (trial + 1) % 3))) return rc2;
-              solve_version = version;
-            }
-          } else {
-            // the last evaluation that can run in the last round goes together with the (speculative) export of its state
-            fused_export = last_round && (it + 1 >= iterations || nBad >= 2) && !lambda_on_device;
-            if (fused_export) {
-              const int n_thr = std::max(std::max(NE, NP), 3 * NX);
-              hipLaunchKernelGGL(k_errors_export<CamT>, dim3((n_thr + 255) / 256), dim3(256), 0, st, n_blocks_e, NE, D.edges, posesB[trial],
-                                 pointsB[trial], cam, hb, h->d_err.p, h->d_chi2.p, h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p,
-                                 n_blocks_u, h->d_ok.p, h->rec.d, ++h->rec_seq, NP, NX, h->dl_h.d + d_flags_o,
-                                 r->edge_chi2 ? reinterpret_cast<double*>(h->dl_h.d + d_chi_o) : (double*)nullptr,
-                                 reinterpret_cast<PoseQ*>(h->dl_h.d + d_poses_o), reinterpret_cast<double*>(h->dl_h.d + d_points_o));
-            } else {
-              launch_errors(trial, 1);
-            }
-          }
-          const bool round_may_end = it + 1 >= iterations || nBad >= 2;
-          if (speculated && !last_round && round_may_end && !lambda_on_device) {
-            // ... and if this trial ends the round, the next round's lambda init as well
-            hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, bps[ls ^ 1], bls[ls ^ 1],
-                               Hpps[ls ^ 1], Hlls[ls ^ 1], 0.0, (int*)nullptr, 0, 1, h->rec.d, p->lambda_init, h->d_lambda0.p);
-            fin_version = version;
-          }
-          if (last_round && round_may_end && !lambda_on_device) {
-            // ... or, in the last round, the export of the trial state (dropped if the trial is rejected or the round goes on)
-            if (!fused_export) launch_export(trial);
-            if ((rc2 = h->sig.post(st))) return rc2;
-            exp_version = version; exp_buf = trial;
-          }
-          ORBG_HIP(hipGetLastError());
-          if ((rc2 = poll_record())) return rc2;
-        } else if ((rc2 = finish(lambda, 1, 0, true))) {
-          return rc2;
-        }
+        const int trial = (m.cur + 1) % 3;
+        m.version++;
+        bool speculated;
+        if ((rc = launch_trial(trial, qmax == 0 && used_spec, lambda_on_device, round_may_end, &speculated))) return rc;
         if (lambda_on_device) {
           // the round's initial chi2 / lambda, as the device computed them before this first trial
-          currentChi = h->rec.h->chi2_init;
-          lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
+          m.currentChi = h->rec.h->chi2_init;
+          m.lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
           lambda_on_device = false;
-          if (first_chi) { r->chi2_initial = currentChi; first_chi = false; }
-          tempChi = currentChi; iniChi = currentChi;
+          if (m.first_chi) { r->chi2_initial = m.currentChi; m.first_chi = false; }
+          iniChi = m.currentChi;
         }
         const bool ok2 = h->rec.h->ok != 0;
-        tempChi = h->rec.h->chi2;
+        double tempChi = h->rec.h->chi2;
         if (!ok2) tempChi = std::numeric_limits<double>::max();
-        rho = currentChi - tempChi;
+        rho = m.currentChi - tempChi;
         double scale = h->rec.h->scale;
         scale += 1e-3;
         rho /= scale;
@@ -2327,249 +2494,154 @@ static int lba_solve_attempt_t(lba_handle* h, const lba_problem* p, StopRef stop
           double alpha = 1. - c3 * c3 * c3;            // arithmetic on the device for the speculative next solve
           alpha = std::min(alpha, 2. / 3.);
           const double scaleFactor = std::max(1. / 3., alpha);
-          lambda *= scaleFactor;
-          ni = 2;
-          currentChi = tempChi;
-          cur = trial;                                // discardTop(): keep the trial state
-          err_valid = true;
-          spec_ready = speculated;
+          m.lambda *= scaleFactor;
+          m.ni = 2;
+          m.currentChi = tempChi;
+          m.cur = trial;                              // discardTop(): keep the trial state
+          m.err_valid = true;
+          m.spec_ready = speculated;
         } else {
-          lambda *= ni;
-          ni *= 2;                                    // pop(): current buffer untouched
-          err_valid = false;                          // d_err now belongs to the rejected trial
-          spec_ready = false;
+          m.lambda *= m.ni;
+          m.ni *= 2;                                  // pop(): current buffer untouched
+          m.err_valid = false;                        // d_err now belongs to the rejected trial
+          m.spec_ready = false;
         }
         qmax++;
-        trials_done++;
-      } while (rho < 0 && qmax < 10 && !terminate());
+        stop.trials_done++;
+      } while (rho < 0 && qmax < 10 && !stop());
       done++;
-      r->chi2_final = currentChi;
+      r->chi2_final = m.currentChi;
       if (r->trace && r->trace_len < r->trace_cap) {
-        r->trace[3 * r->trace_len] = lambda; r->trace[3 * r->trace_len + 1] = currentChi; r->trace[3 * r->trace_len + 2] = qmax;
+        r->trace[3 * r->trace_len] = m.lambda; r->trace[3 * r->trace_len + 1] = m.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
         r->trace_len++;
       }
       if (qmax == 10 || rho == 0) { ok = false; continue; }
-      if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-      if (nBad >= 3) ok = false;
+      if ((iniChi - m.currentChi) * 1e3 < iniChi) m.nBad++; else m.nBad = 0;
+      if (m.nBad >= 3) ok = false;
     }
     *done_out = done;
     return ORBG_OK;
-  };
+  }
 
-  // first residuals + linearisation are launched before the host has finished the structure
-  const int n_zero = n + 3 * nL;
-  // first iteration in two launches (k_errlin_prep, k_finish_items) where the observation lists are sorted on the device
-  const bool first2 = dev_lists && NE > 0 && nL > 0 && !terminate();
-  if (first2 && dev_csr) {
-    const int set = ls ^ 1;
-    const int n_blocks_l = (nL + 255) / 256;              // (k_csr_sort: one thread per landmark)
-    const int n_tail = errlin_tail_blocks(nL);
-    uint8_t* const B = h->up_d.p;
-    hipLaunchKernelGGL(k_csr_fill, dim3(n_blocks_e), dim3(256), 0, st, NE, D.edges, D.pose_col, D.point_col, reinterpret_cast<int*>(B + o_cur_pt),
-                       reinterpret_cast<int*>(B + o_cur_ps), reinterpret_cast<int*>(B + o_cur_pf), const_cast<int*>(D.pt_edges),
-                       const_cast<int*>(D.ps_edges), const_cast<int*>(D.pf_edges));
-    hipLaunchKernelGGL(k_csr_sort, dim3(nP + n_blocks_l + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, nP, nL, D.ps_start,
-                       const_cast<int*>(D.ps_edges), D.pt_start, const_cast<int*>(D.pt_edges), D.pf_start, const_cast<int*>(D.pf_edges),
-                       const_cast<int*>(D.pf_col), reinterpret_cast<unsigned long long*>(B + o_lm_mask), D.edges, D.pose_col, n,
-                       use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
-    hipLaunchKernelGGL(k_errlin<CamT>, dim3(nP + n_blocks_e + n_tail), dim3(256), 0, st, nP, NE, D.edges, posesB[cur],
-                       pointsB[cur], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, EBs[set], D.ps_start,
-                       D.ps_edges, Hpps[set], bps[set], h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, 0, (const int*)nullptr,
-                       h->rec.d, h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, Hlls[set], bls[set],
-                       LmIn{0.0, 0.0, (const double*)nullptr, (const double*)nullptr, (double*)nullptr});
-    hipLaunchKernelGGL(k_finish_items, dim3(1 + n_pairs_all), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, bps[set], bls[set],
-                       Hpps[set], Hlls[set], h->rec.d, p->lambda_init, h->d_lambda0.p,
-                       reinterpret_cast<const unsigned long long*>(B + o_lm_mask), D.pf_start, D.pf_edges, D.pf_col,
-                       h->d_items_dev.p, item_cap, h->d_pair_count.p);
+  // ---- results: chi2 of the LAST error evaluation (d_chi2), depth test with the current estimate (S/Optimizer.cc:2131-2166):
+  // flags computed on the device, everything comes back through one pinned block
+  int final_export() {
+    if (lm.exp_version == lm.version && lm.exp_buf == lm.cur) return h->sig.wait(st);   // the speculative export is the final one
+    export_state(lm.cur);
     ORBG_HIP(hipGetLastError());
-    err_valid = true; spec_ready = true; fin_version = version;
-  } else if (first2) {
-    const int set = ls ^ 1;
-    const int n_blocks_l = errlin_tail_blocks(nL), n_err = nP + n_blocks_e + n_blocks_l, nsb = (nL + 255) / 256;
-    hipLaunchKernelGGL(k_errlin_prep<CamT>, dim3(n_err + nsb + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, n_err, nsb,
-                       const_cast<int*>(D.pf_edges), const_cast<int*>(D.pf_col), D.pf_start,
-                       reinterpret_cast<unsigned long long*>(h->up_d.p + o_lm_mask), n, use_mfma ? h->d_St.p : (double*)nullptr,
-                       h->d_x.p, n_zero,
-                       nP, NE, D.edges, posesB[cur], pointsB[cur], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, EBs[set],
-                       D.ps_start, D.ps_edges, Hpps[set], bps[set], h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, 0,
-                       (const int*)nullptr, h->rec.d, h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, Hlls[set], bls[set],
-                       LmIn{0.0, 0.0, (const double*)nullptr, (const double*)nullptr, (double*)nullptr});
-    hipLaunchKernelGGL(k_finish_items, dim3(1 + n_pairs_all), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, bps[set], bls[set],
-                       Hpps[set], Hlls[set], h->rec.d, p->lambda_init, h->d_lambda0.p,
-                       reinterpret_cast<const unsigned long long*>(h->up_d.p + o_lm_mask), D.pf_start, D.pf_edges, D.pf_col,
-                       h->d_items_dev.p, item_cap, h->d_pair_count.p);
-    ORBG_HIP(hipGetLastError());
-    err_valid = true; spec_ready = true; fin_version = version;
-  } else if (!terminate()) {
-    if (NE > 0) {
-      // residuals + linearisation of the initial estimate in the fused kernel of the later trials (its record is not waited
-      // for: it carries the sequence number the host has already seen)
-      const int set = ls ^ 1;
-      const int n_blocks_l = errlin_tail_blocks(nL);
-      hipLaunchKernelGGL(k_errlin<CamT>, dim3(nP + n_blocks_e + n_blocks_l), dim3(256), 0, st, nP, NE, D.edges, posesB[cur],
-                         pointsB[cur], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, EBs[set], D.ps_start,
-                         D.ps_edges, Hpps[set], bps[set], h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, 0, (const int*)nullptr,
-                         h->rec.d, h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, Hlls[set], bls[set],
-                         LmIn{0.0, 0.0, (const double*)nullptr, (const double*)nullptr, (double*)nullptr});
-    }
-    err_valid = true;
-    spec_ready = true;
-    if (NE > 0) {
-      // the first round's lambda init needs nothing the host is still building: it goes right behind the linearisation
-      hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, nP, nL, h->d_x.p, bps[ls ^ 1], bls[ls ^ 1],
-                         Hpps[ls ^ 1], Hlls[ls ^ 1], 0.0, (int*)nullptr, 0, 1, h->rec.d, p->lambda_init, h->d_lambda0.p);
-      fin_version = version;
-    }
-    ORBG_HIP(hipGetLastError());
+    return h->sig.sync(st);
   }
-  // not needed before the first Schur complement: the zeroed step vector and the padding / zeros of the bordered tile image
-  // (they depend on n only, k_schur never touches them -- once per call) go behind the first linearisation
-  if (first2) {
-    // (done by k_errlin_prep)
-  } else if (dev_lists) {
-    // ... in one launch with the per-landmark lists (k_prep)
-    const int nsb = (nL + kSortPfThreads - 1) / kSortPfThreads;
-    hipLaunchKernelGGL(k_prep, dim3(nsb + 32 + 8), dim3(kSortPfThreads), 0, st, nsb, nL, D.pf_start, const_cast<int*>(D.pf_edges),
-                       const_cast<int*>(D.pf_col), reinterpret_cast<unsigned long long*>(h->up_d.p + o_lm_mask), D.edges, D.pose_col,
-                       n, use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
-    ORBG_HIP(hipGetLastError());
-  } else {
-    ORBG_HIP(hipMemsetAsync(h->d_x.p, 0, (size_t)n_zero * sizeof(double), st));
-    if (use_mfma) ORBG_HIP(ldltm::launch_image_pad(n, h->d_St.p, st));
-  }
-  const double t_s2b = now_s();
-  if (!dev_lists)
-  // while those run: the landmarks' free observations sorted by pose column, their pose masks / the pair counts
-  {
-    // per landmark: stable insertion sort of its free observations by pose column (a handful each), then count its
-    // (pose pair) items; pair id = row_off[i1] + i2
-    std::vector<int>& row_off = h->s_row_off;
-    row_off.resize(std::max(nP, 1));
-    for (int i1 = 0; i1 < nP; i1++) row_off[i1] = i1 * nP - i1 * (i1 - 1) / 2 - i1;
-    for (int i = 0; i <= n_pairs_all; i++) pair_start[i] = 0;
-    for (int l = 0; l < nL; l++) {
-      const int b0 = pf_start[l], e0 = pf_start[l + 1];
-      for (int a2 = b0 + 1; a2 < e0; a2++) {
-        const int e = pf_edges[a2], key = pose_col[edges[e].pose];
-        int b2 = a2 - 1;
-        while (b2 >= b0 && pose_col[edges[pf_edges[b2]].pose] > key) { pf_edges[b2 + 1] = pf_edges[b2]; b2--; }
-        pf_edges[b2 + 1] = e;
-      }
-      for (int j = b0; j < e0; j++) pf_col[j] = pose_col[edges[pf_edges[j]].pose];
-      if (dev_items) {
-        unsigned long long m = 0;
-        for (int j = b0; j < e0; j++) m |= 1ull << pf_col[j];
-        lm_mask[l] = m;
+  void write_back() {
+    if (prof_pending) {                                   // the stream is idle here: both events have completed
+      float ems = 0;
+      if (hipEventElapsedTime(&ems, h->prof_ev[0], h->prof_ev[1]) == hipSuccess) { h->prof_sum_ms += ems; h->prof_n++; h->prof_n_unknowns = n; }
+    }
+    const PoseQ* rposes = reinterpret_cast<const PoseQ*>(h->dl_h.h + o_rposes);
+    const double* rpoints = reinterpret_cast<const double*>(h->dl_h.h + o_rpoints);
+    int n_out = 0;
+    {
+      // (restrict-qualified locals and no branch in the bodies: the loops vectorise; as one loop with the two tests inside they
+      // cost ~1 ns per edge)
+      const uint8_t* __restrict__ rf = h->dl_h.h + o_rflags;
+      uint8_t* __restrict__ odp = reinterpret_cast<uint8_t*>(r->edge_depth_pos);
+      uint8_t* __restrict__ oout = reinterpret_cast<uint8_t*>(r->edge_outlier);
+      if (lm.version == 0) {
+        // the flag was raised between the check that precedes optimize() and the first iteration: g2o never evaluated a
+        // residual (e->chi2() reads an edge's never-written _error: pinned as zero, as in the oracle), so only the depth test
+        // of the unchanged estimate can make an outlier (S/Optimizer.cc:2219-2253)
+        if (odp) for (int k = 0; k < NE; k++) odp[k] = rf[k] & 1;
+        if (oout) for (int k = 0; k < NE; k++) oout[k] = (rf[k] & 1) ^ 1;
+        for (int k = 0; k < NE; k++) n_out += (rf[k] & 1) ^ 1;
       } else {
-        for (int a2 = b0; a2 < e0; a2++) {
-          const int ro = row_off[pf_col[a2]] + 1;
-          for (int b2 = a2; b2 < e0; b2++) pair_start[ro + pf_col[b2]]++;
-        }
+        if (odp) for (int k = 0; k < NE; k++) odp[k] = rf[k] & 1;
+        if (oout) for (int k = 0; k < NE; k++) oout[k] = (rf[k] >> 1) & 1;
+        for (int k = 0; k < NE; k++) n_out += (rf[k] >> 1) & 1;
       }
     }
-  }
-  size_t off_b = off_a;
-  auto pair_id = [&](int i1, int i2) { return i1 * nP - i1 * (i1 - 1) / 2 + (i2 - i1); };
-  if (dev_items && !terminate()) {
-    // the pf lists and pose masks go up next and the device builds the pair items behind the first linearisation; the pair
-    // table (a function of nP alone) rides along, so nothing is left for a third upload
-    for (int i1 = 0; i1 < nP; i1++)
-      for (int i2 = i1; i2 < nP; i2++) { pair_i1[pair_id(i1, i2)] = i1; pair_i2[pair_id(i1, i2)] = i2; }
-    off_b = o_pair_start;
-    if (!dev_lists && (rc = upload_arena(h, off_a, off_b, st))) return rc;      // (dev_lists: k_schur derives the pair from its index)
-    if (nL > 0 && !first2)
-      hipLaunchKernelGGL(k_build_items, dim3(n_pairs_all), dim3(256), 0, st, nP, nL,
-                         reinterpret_cast<const unsigned long long*>(h->up_d.p + o_lm_mask), D.pf_start, D.pf_edges, D.pf_col,
-                         h->d_items_dev.p, item_cap, h->d_pair_count.p);
-    ORBG_HIP(hipGetLastError());
-  }
-  // pose pairs (i1 <= i2) and their landmark items, grouped by pair (counting sort keeps landmark order)
-  if (!dev_items) {
-    for (int i = 0; i < n_pairs_all; i++) pair_start[i + 1] += pair_start[i];
-    std::vector<int>& fill = h->s_fill;
-    fill.assign(pair_start, pair_start + n_pairs_all);
-    const std::vector<int>& row_off = h->s_row_off;
-    for (int l = 0; l < nL; l++) {
-      const int b0 = pf_start[l], e0 = pf_start[l + 1];
-      for (int a2 = b0; a2 < e0; a2++) {
-        const int ro = row_off[pf_col[a2]], ea = pf_edges[a2];
-        for (int b2 = a2; b2 < e0; b2++) items[fill[ro + pf_col[b2]]++] = PairItem{ea, pf_edges[b2], l};
-      }
+    if (r->edge_chi2 && NE > 0) {
+      if (lm.version == 0) memset(r->edge_chi2, 0, 8 * (size_t)NE);
+      else memcpy(r->edge_chi2, h->dl_h.h + o_rchi, 8 * (size_t)NE);
     }
+    r->n_outliers = n_out;
+    // vToErase.size() >= (vpMapPointEdgeMono.size() + vpMapPointEdgeStereo.size()) * 0.5  (S/Optimizer.cc:2256: the right camera's edges
+    // are in vToErase but not in the sum)
+    if (NE > 0 && n_out >= (NE - n_right_edges) * 0.5) r->status = LBA_REJECTED_OUTLIERS;
+    for (int i = 0; i < NP; i++) {                       // Converter::toCvMat(SE3Quat)
+      double R[9];
+      quat_to_R(rposes[i].q, R);
+      float* T = r->poses + 16 * (size_t)i;
+      for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) T[4 * a + c] = (float)R[3 * a + c]; T[4 * a + 3] = (float)rposes[i].t[a]; }
+      T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
+    }
+    for (size_t i = 0; i < 3 * (size_t)NX; i++) r->points[i] = (float)rpoints[i];
   }
-  // keep every pair (diagonals always; off-diagonals even if empty so that S is fully written)
-  for (int i1 = 0; i1 < nP; i1++)
-    for (int i2 = i1; i2 < nP; i2++) { pair_i1[pair_id(i1, i2)] = i1; pair_i2[pair_id(i1, i2)] = i2; }
+};
+// Instantiated here, pinhole first: the kernel templates the members launch are then instantiated in the order of the launch forms
+// above, which is the order of the kernels in the device code object.
+template struct LbaRun<Cam>;
+template struct LbaRun<CamRig>;
 
-  if (!dev_items && (rc = upload_arena(h, off_b, off, st))) return rc;
+// The kernels that evaluate edges exist twice: for the five pinhole scalars (every BASELINE configuration; unchanged code) and for
+// a problem that carries a camera rig (fisheye models, the right camera's *ToBody edges).
+template <class CamT>
+static int lba_solve_attempt_t(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r, const CamT& cam) {
+  if (!r || p->n_poses < 0 || p->n_points < 0 || p->n_edges < 0) return ORBG_BAD_ARG;
+  if (!r->poses || !r->points) return ORBG_BAD_ARG;
+  int rc = select_device(h->device);
+  if (rc) return rc;
+  LbaRun<CamT> run(h, p, r, cam, stop_ref);
+  r->status = LBA_APPLIED; r->iters_round1 = r->iters_round2 = 0; r->n_outliers = 0; r->trace_len = 0;
+  r->chi2_initial = r->chi2_final = 0;
+  if (run.stop()) {                                    // S/Optimizer.cc:2127-2129
+    r->status = LBA_ABORTED_BEFORE_OPT;
+    memcpy(r->poses, p->poses, sizeof(float) * 16 * (size_t)p->n_poses);
+    memcpy(r->points, p->points, sizeof(float) * 3 * (size_t)p->n_points);
+    for (int k = 0; k < p->n_edges; k++) {
+      if (r->edge_chi2) r->edge_chi2[k] = 0;
+      if (r->edge_depth_pos) r->edge_depth_pos[k] = 1;
+      if (r->edge_outlier) r->edge_outlier[k] = 0;
+    }
+    return ORBG_OK;
+  }
+  run.stop.past_precheck = true;
+  static TraceAcc tr("lba_solve_h structure (before the first launch) / upload submit / LM loop incl. pair items / export+wait / write-back / "
+                     "of the structure: edge pass + layout / CSR lists / of the LM loop: pair items + symbolic + upload");
+  const double t_a = now_s();
+  if ((rc = run.edge_pass()) || (rc = run.layout())) return rc;
+  const double t_s1 = now_s();
+  run.fill_lists();
+  const double t_s2 = now_s();
+  run.initial_state();
+  const double t_b = now_s();
+  if ((rc = run.buffers())) return rc;
+  const double t_c = now_s();
+  if ((rc = run.pick_solver()) || (rc = run.first_linearisation())) return rc;
+  const double t_s2b = now_s();
+  if ((rc = run.pair_items())) return rc;
   const double t_s3b = now_s();
   int done = 0;
-  if ((rc = optimize(p->its_round1 > 0 ? p->its_round1 : 5, &done))) return rc;
+  if ((rc = run.optimize(p->its_round1 > 0 ? p->its_round1 : 5, &done))) return rc;
   r->iters_round1 = done;
-  if (!terminate()) {
-    last_round = true;
-    if ((rc = optimize(p->its_round2 > 0 ? p->its_round2 : 10, &done))) return rc;
+  if (!run.stop()) {
+    run.lm.last_round = true;
+    if ((rc = run.optimize(p->its_round2 > 0 ? p->its_round2 : 10, &done))) return rc;
     r->iters_round2 = done;
   }
   const double t_d = now_s();
-  // ---- results: chi2 of the LAST error evaluation (d_chi2), depth test with the current estimate (S/Optimizer.cc:2131-2166):
-  // flags computed on the device, everything comes back through one pinned block
-  if (exp_version == version && exp_buf == cur) {
-    if ((rc = h->sig.wait(st))) return rc;              // the speculative export is the final one
-  } else {
-    launch_export(cur);
-    ORBG_HIP(hipGetLastError());
-    if ((rc = h->sig.sync(st))) return rc;
-  }
+  if ((rc = run.final_export())) return rc;
   const double t_e = now_s();
-  if (prof_pending) {                                   // the stream is idle here: both events have completed
-    float ems = 0;
-    if (hipEventElapsedTime(&ems, h->prof_ev[0], h->prof_ev[1]) == hipSuccess) { h->prof_sum_ms += ems; h->prof_n++; h->prof_n_unknowns = n; }
-  }
-  const PoseQ* rposes = reinterpret_cast<const PoseQ*>(h->dl_h.h + d_poses_o);
-  const double* rpoints = reinterpret_cast<const double*>(h->dl_h.h + d_points_o);
-  const uint8_t* rflags = h->dl_h.h + d_flags_o;
-  int n_out = 0;
-  {
-    // (restrict-qualified locals and no branch in the bodies: the loops vectorise; as one loop with the two tests inside they
-    // cost ~1 ns per edge)
-    const uint8_t* __restrict__ rf = rflags;
-    uint8_t* __restrict__ odp = reinterpret_cast<uint8_t*>(r->edge_depth_pos);
-    uint8_t* __restrict__ oout = reinterpret_cast<uint8_t*>(r->edge_outlier);
-    if (version == 0) {
-      // the flag was raised between the check that precedes optimize() and the first iteration: g2o never evaluated a
-      // residual (e->chi2() reads an edge's never-written _error: pinned as zero, as in the oracle), so only the depth test
-      // of the unchanged estimate can make an outlier (S/Optimizer.cc:2219-2253)
-      if (odp) for (int k = 0; k < NE; k++) odp[k] = rf[k] & 1;
-      if (oout) for (int k = 0; k < NE; k++) oout[k] = (rf[k] & 1) ^ 1;
-      for (int k = 0; k < NE; k++) n_out += (rf[k] & 1) ^ 1;
-    } else {
-      if (odp) for (int k = 0; k < NE; k++) odp[k] = rf[k] & 1;
-      if (oout) for (int k = 0; k < NE; k++) oout[k] = (rf[k] >> 1) & 1;
-      for (int k = 0; k < NE; k++) n_out += (rf[k] >> 1) & 1;
-    }
-  }
-  if (r->edge_chi2 && NE > 0) {
-    if (version == 0) memset(r->edge_chi2, 0, 8 * (size_t)NE);
-    else memcpy(r->edge_chi2, h->dl_h.h + d_chi_o, 8 * (size_t)NE);
-  }
-  r->n_outliers = n_out;
-  // vToErase.size() >= (vpMapPointEdgeMono.size() + vpMapPointEdgeStereo.size()) * 0.5  (S/Optimizer.cc:2256: the right camera's edges
-  // are in vToErase but not in the sum)
-  if (NE > 0 && n_out >= (NE - n_right_edges) * 0.5) r->status = LBA_REJECTED_OUTLIERS;
-  for (int i = 0; i < NP; i++) {                       // Converter::toCvMat(SE3Quat)
-    double R[9];
-    quat_to_R(rposes[i].q, R);
-    float* T = r->poses + 16 * (size_t)i;
-    for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) T[4 * a + c] = (float)R[3 * a + c]; T[4 * a + 3] = (float)rposes[i].t[a]; }
-    T[12] = 0; T[13] = 0; T[14] = 0; T[15] = 1;
-  }
-  for (size_t i = 0; i < 3 * (size_t)NX; i++) r->points[i] = (float)rpoints[i];
-  {
-    const double t_f = now_s();
-    tr.t[0] += t_b - t_a; tr.t[1] += t_c - t_b; tr.t[2] += t_d - t_c; tr.t[3] += t_e - t_d; tr.t[4] += t_f - t_e; tr.t[5] += t_s1 - t_a; tr.t[6] += t_s2 - t_s1; tr.t[7] += t_s3b - t_s2b; tr.n++;
-  }
+  run.write_back();
+  const double t_f = now_s();
+  tr.t[0] += t_b - t_a; tr.t[1] += t_c - t_b; tr.t[2] += t_d - t_c; tr.t[3] += t_e - t_d; tr.t[4] += t_f - t_e; tr.t[5] += t_s1 - t_a; tr.t[6] += t_s2 - t_s1; tr.t[7] += t_s3b - t_s2b; tr.n++;
   return ORBG_OK;
+}
+static int lba_solve_attempt(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r) {
+  if (!h || !p) return ORBG_BAD_ARG;
+  const Cam cam{p->fx, p->fy, p->cx, p->cy, p->bf, p->bf};
+  if (!p->rig) return lba_solve_attempt_t(h, p, stop_ref, r, cam);
+  CamRig g;
+  if (!cam_rig_from(*p->rig, cam, &g)) return ORBG_BAD_ARG;
+  return lba_solve_attempt_t(h, p, stop_ref, r, g);
 }
 
 // Live measurement for bench.py's roofline: with profiling on, ONE launch of the reduced-camera-system LDL^T per solve is
