@@ -397,6 +397,97 @@ int orbm_search_by_bow_kf(orbm_frame* kf2, const orbm_featvec_view* fv2, const u
                           const orbm_featvec_view* fv1, float nnratio, int check_orientation,
                           int32_t* matches12, int* nmatches);
 
+/* ---------------------------------------------------------------- Sim3Solver (server place recognition)
+ * The link between orbm_search_by_bow_kf and orbm_search_by_projection_sim3 in LoopClosing::DetectCommonRegionsFromBoW
+ * (S/LoopClosing.cc:707-718): RANSAC over minimal sets of three matched map points, Horn's closed form per hypothesis, inliers by
+ * reprojection in both keyframes.  Every hypothesis of a call is evaluated in ONE kernel launch; the reference's serial rule
+ * ("first iteration that converges, else the last one with the largest count") is then replayed over the counts in draw order, so
+ * the outcome is the one the serial loop gives for the same draws, including the iteration at which it stops.
+ *
+ * The flat problem is what the constructor keeps per surviving pair (S/Sim3Solver.cc:38-128): X3Dc1 / X3Dc2 = mvX3Dc1 / mvX3Dc2
+ * (n x 3 float, camera frames), max_err1 / max_err2 = mvnMaxError1 / mvnMaxError2 -- vector<size_t> in I/Sim3Solver.h:76-77, i.e.
+ * 9.210 * sigma2 TRUNCATED to an integer -- and the intrinsics of pKF1->mpCamera / pKF2->mpCamera (Pinhole::project,
+ * S/CameraModels/Pinhole.cpp:41-52; mK1 / mK2 are stored by the reference and never read).  camera_model1/2 must be 0 (pinhole):
+ * any other model is refused with ORBG_BAD_ARG.  A point with z <= 0 is not special-cased: the reference does not.
+ * struct_size = sizeof(the struct) as the caller was compiled: a struct that can grow says how large the caller believes it is. */
+typedef struct orbm_sim3_problem {
+  uint32_t struct_size;
+  int32_t  n;                    /* N = mvpMapPoints1.size() */
+  const float* X3Dc1;            /* n x 3 */
+  const float* X3Dc2;            /* n x 3 */
+  const uint32_t* max_err1;      /* n */
+  const uint32_t* max_err2;      /* n */
+  float fx1, fy1, cx1, cy1;      /* pCamera1 */
+  float fx2, fy2, cx2, cy2;      /* pCamera2 */
+  int32_t camera_model1, camera_model2;
+  int32_t fix_scale;             /* mbFixScale */
+} orbm_sim3_problem;
+
+/* SetRansacParameters' arguments (S/Sim3Solver.cc:132; defaults 0.99, 6, 300 in I/Sim3Solver.h:46) */
+typedef struct orbm_sim3_params {
+  double  probability;
+  int32_t min_inliers;
+  int32_t max_iterations;
+} orbm_sim3_params;
+
+/* Outcome of iterate() / find().  T12 / R / t / s / inliers / n_inliers describe mBestT12, mBestRotation, mBestTranslation, mBestScale,
+ * mvbBestInliers and mnBestInliers AFTER the call (valid when have_best; they persist between calls as in the reference, and on
+ * convergence they are the converged hypothesis).  The reference's outputs follow from the flags: nInliers / vbInliers are
+ * n_inliers / inliers when converged and 0 / all false otherwise; the four-argument iterate returns T12 when converged and an empty
+ * matrix otherwise, the five-argument one T12 when converged or improved_in_this_call (its local bestSim3, :243,282) and empty otherwise.
+ * inliers: caller's buffer of n bytes over the kept pairs (NULL: not wanted); vbInliers[mvnIndices1[i]] = inliers[i].
+ * hyp_*: optional per-hypothesis outputs of THIS call in draw order, for checkers (NULL: not read back): inlier counts
+ * (iterations), T12 (iterations x 16) and bit-packed masks (iterations x ceil(n / 64) words, bit i & 63 of word i >> 6).  They cover
+ * every iteration handed to the launch, also those behind the one that converged. */
+typedef struct orbm_sim3_result {
+  uint32_t struct_size;
+  int32_t  no_more;                /* bNoMore */
+  int32_t  converged;              /* bConverge */
+  int32_t  n_inliers;              /* mnBestInliers */
+  int32_t  iterations_done;        /* mnIterations after the call */
+  int32_t  iterations_run;         /* iterations the serial loop would have run in this call */
+  int32_t  improved_in_this_call;
+  int32_t  best_iteration;         /* 0-based mnIterations index of the hypothesis that became the best in this call, or -1 */
+  int32_t  have_best;
+  float    T12[16];
+  float    R[9];
+  float    t[3];
+  float    s;
+  uint8_t* inliers;
+  int32_t* hyp_n_inliers;
+  float*   hyp_T12;
+  uint64_t* hyp_masks;
+} orbm_sim3_result;
+
+typedef struct orbm_sim3 orbm_sim3;
+
+/* Sim3Solver::Sim3Solver after its loop over the matches (S/Sim3Solver.cc:119-127): create + set_problem.  set_problem copies the
+ * arrays, resets mnIterations / mnBestInliers and applies SetRansacParameters() at its defaults, as the constructor does. */
+int orbm_sim3_create(int device, orbm_sim3** out);
+int orbm_sim3_destroy(orbm_sim3* h);
+int orbm_sim3_set_stream(orbm_sim3* h, void* hip_stream);
+int orbm_sim3_set_problem(orbm_sim3* h, const orbm_sim3_problem* p);
+/* void Sim3Solver::SetRansacParameters(double probability, int minInliers, int maxIterations), S/Sim3Solver.cc:132-157 (host). */
+int orbm_sim3_set_ransac_parameters(orbm_sim3* h, double probability, int min_inliers, int max_iterations);
+/* ... the same formula without a handle: *out = mRansacMaxIts for N = n.  Runs without a device. */
+int orbm_sim3_ransac_iterations(int n, double probability, int min_inliers, int max_iterations, int* out);
+/* The minimal sets of :189-206: draws = the raw DUtils::Random::RandomInt(0, size - 1) results, three per iteration (iteration k
+ * draws from lists of n, n - 1 and n - 2 entries; anything else is ORBG_BAD_ARG); idx = the three correspondence indices the
+ * swap-with-back removal on mvAllIndices gives.  Host only, runs without a device; the kernel uses the same closed form. */
+int orbm_sim3_resolve_draws(int n, const int32_t* draws, int n_iterations, int32_t* idx);
+/* cv::Mat Sim3Solver::iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers[, bool& bConverge]),
+ * S/Sim3Solver.cc:159-292: up to n_iterations iterations (fewer when mRansacMaxIts is reached) in one launch; draws as above, 3 *
+ * n_iterations values, of which the first 3 * iterations_run are the ones the serial loop would have consumed.  N < min_inliers:
+ * no_more without a launch (:165-169).  find() (:294-298) is iterate(mRansacMaxIts). */
+int orbm_sim3_iterate(orbm_sim3* h, int n_iterations, const int32_t* draws, orbm_sim3_result* result);
+/* find() of B fresh solvers -- the candidates DetectCommonRegionsFromBoW tries one after another, of up to four agents -- in ONE
+ * launch: problems[b] with SetRansacParameters(params[b]) and draws[b] (3 * mRansacMaxIts(b) values, see
+ * orbm_sim3_ransac_iterations).  results[b] as for iterate on a new solver.  All arguments and the device are checked before any
+ * result is written.  A problem with min_inliers <= n < 3 cannot draw a minimal set (the reference would index an empty list):
+ * ORBG_BAD_ARG, here and in orbm_sim3_iterate. */
+int orbm_sim3_solve_batch(int device, const orbm_sim3_problem* problems, int B, const orbm_sim3_params* params,
+                          const int32_t* const* draws, orbm_sim3_result* results);
+
 /* ---------------------------------------------------------------- bag of words */
 
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> flattened (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:60-130,

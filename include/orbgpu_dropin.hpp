@@ -14,6 +14,7 @@
 //   void Tracking::SearchLocalPoints() body: the loop above + the matcher call as ONE device pass  S/Tracking.cc:3083-3155
 //   void LocalBundleAdjustment(KeyFrame*, bool* pbStopFlag, Map*, int& num_fixedKF, int)      I/Optimizer.h:42,   S/Optimizer.cc:1810-2410
 //   int  PoseOptimization(Frame*)                                                             I/Optimizer.h:47,   S/Optimizer.cc:964-1278
+//   class Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bFixScale, vpKeyFrameMatchedMP)  I/Sim3Solver.h:36-131, S/Sim3Solver.cc (orbgpu::Sim3Solver, at the end)
 //
 // Matrix access goes through mat_f32 / mat_u8 / make_mat (overloads for cv::Mat below, for the mock in the test header).
 #ifndef ORBGPU_DROPIN_HPP_
@@ -21,6 +22,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <list>
 #include <map>
@@ -1237,6 +1239,180 @@ int PoseOptimization(FrameT* pFrame) {
 }
 
 }  // namespace dropin
+
+// ------------------------------------------------------------------------------------------------ Sim3Solver
+// ORB_SLAM3::Sim3Solver (I/Sim3Solver.h:36-131, S/Sim3Solver.cc) with the reference's constructor and method signatures, in two
+// separable halves: collect() -- the constructor's loop over the matches (:71-117), host only -- and the orbm_sim3_* calls.
+
+// What the constructor keeps: the flat problem plus mvnIndices1 / mN1.
+struct Sim3Flat {
+  std::vector<float> X3Dc1, X3Dc2;             // mvX3Dc1, mvX3Dc2
+  std::vector<uint32_t> max_err1, max_err2;    // mvnMaxError1, mvnMaxError2 (vector<size_t> there: the product 9.210 * sigma2 is truncated)
+  std::vector<size_t> indices1;                // mvnIndices1
+  int mN1 = 0;
+  float k1[4] = {0, 0, 0, 0}, k2[4] = {0, 0, 0, 0};
+  int model1 = 0, model2 = 0;
+  bool fix_scale = true;
+  orbm_sim3_problem problem() const {
+    orbm_sim3_problem p;
+    std::memset(&p, 0, sizeof(p));
+    p.struct_size = sizeof(p); p.n = (int32_t)indices1.size();
+    p.X3Dc1 = X3Dc1.data(); p.X3Dc2 = X3Dc2.data(); p.max_err1 = max_err1.data(); p.max_err2 = max_err2.data();
+    p.fx1 = k1[0]; p.fy1 = k1[1]; p.cx1 = k1[2]; p.cy1 = k1[3]; p.fx2 = k2[0]; p.fy2 = k2[1]; p.cx2 = k2[2]; p.cy2 = k2[3];
+    p.camera_model1 = model1; p.camera_model2 = model2; p.fix_scale = fix_scale ? 1 : 0;
+    return p;
+  }
+};
+
+// DUtils::Random::RandomInt(min, max) over rand() (Thirdparty/DBoW2/DUtils/Random.cpp:28-31)
+struct Sim3RandomInt {
+  int operator()(int min, int max) const {
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+  }
+};
+
+// The constructor's loop, S/Sim3Solver.cc:38-117.  vpKeyFrameMatchedMP: the name bDifferentKFs suggests that a caller who passes
+// the keyframes of the matched points gets keypoint 2 and its sigma from them.  The code does the opposite: bDifferentKFs is set when
+// the vector is EMPTY (:45-49, and the vector is then filled with pKF2), and only then is pKFm taken from it (:82-83) -- so pKFm is
+// pKF2 in both cases and a vector the caller passed is never read.  Reproduced as written: the argument is accepted and ignored.
+template <class KeyFrameT, class MapPointT>
+inline Sim3Flat sim3_collect(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatched12, bool bFixScale,
+                             const std::vector<KeyFrameT*>& /*vpKeyFrameMatchedMP*/ = std::vector<KeyFrameT*>()) {
+  using dropin::mat_f32;
+  Sim3Flat f;
+  f.fix_scale = bFixScale;
+  const std::vector<MapPointT*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();       // :56
+  f.mN1 = (int)vpMatched12.size();                                                 // :58
+  const auto Rcw1 = pKF1->GetRotation(); const auto tcw1 = pKF1->GetTranslation(); // :67-70
+  const auto Rcw2 = pKF2->GetRotation(); const auto tcw2 = pKF2->GetTranslation();
+  // Rcw * X + tcw on CV_32F is one gemm: double accumulation in k order, beta * tcw added in double, rounded once
+  auto to_camera = [](const float* R, const float* t, const float* X, std::vector<float>& out) {
+    for (int i = 0; i < 3; i++)
+      out.push_back((float)((((double)R[3 * i] * (double)X[0] + (double)R[3 * i + 1] * (double)X[1]) + (double)R[3 * i + 2] * (double)X[2]) + (double)t[i]));
+  };
+  KeyFrameT* pKFm = pKF2;                                                          // :76, and see above
+  for (int i1 = 0; i1 < f.mN1; i1++) {
+    if (!vpMatched12[i1]) continue;                                                // :79
+    MapPointT* pMP1 = vpKeyFrameMP1[i1];
+    MapPointT* pMP2 = vpMatched12[i1];
+    if (!pMP1) continue;                                                           // :84-85
+    if (pMP1->isBad() || pMP2->isBad()) continue;                                  // :87-88
+    const int indexKF1 = std::get<0>(pMP1->GetIndexInKeyFrame(pKF1));              // :93-94
+    const int indexKF2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKFm));
+    if (indexKF1 < 0 || indexKF2 < 0) continue;                                    // :96-97
+    const auto& kp1 = pKF1->mvKeysUn[indexKF1];
+    const auto& kp2 = pKFm->mvKeysUn[indexKF2];
+    const float sigmaSquare1 = pKF1->mvLevelSigma2[kp1.octave];
+    const float sigmaSquare2 = pKFm->mvLevelSigma2[kp2.octave];
+    f.max_err1.push_back((uint32_t)(size_t)(9.210 * sigmaSquare1));                // :105-106: a double pushed into vector<size_t>
+    f.max_err2.push_back((uint32_t)(size_t)(9.210 * sigmaSquare2));
+    f.indices1.push_back((size_t)i1);
+    const auto X1w = pMP1->GetWorldPos(); const auto X2w = pMP2->GetWorldPos();
+    to_camera(mat_f32(Rcw1), mat_f32(tcw1), mat_f32(X1w), f.X3Dc1);                // :112-116
+    to_camera(mat_f32(Rcw2), mat_f32(tcw2), mat_f32(X2w), f.X3Dc2);
+  }
+  // pCamera1 / pCamera2 = pKF->mpCamera (:41): the projections go through them (:122-123); mK1 / mK2 are stored and never read
+  f.model1 = (int)pKF1->mpCamera->GetType(); f.model2 = (int)pKF2->mpCamera->GetType();
+  for (int k = 0; k < 4; k++) { f.k1[k] = pKF1->mpCamera->getParameter(k); f.k2[k] = pKF2->mpCamera->getParameter(k); }
+  return f;
+}
+
+template <class KeyFrameT, class MapPointT, class RandomIntT = Sim3RandomInt>
+class Sim3Solver {
+ public:
+  using MatT = decltype(std::declval<KeyFrameT&>().GetRotation());
+
+  Sim3Solver(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatched12, const bool bFixScale = true,
+             const std::vector<KeyFrameT*> vpKeyFrameMatchedMP = std::vector<KeyFrameT*>(), int device = 0, RandomIntT random_int = RandomIntT())
+      : mFlat(sim3_collect(pKF1, pKF2, vpMatched12, bFixScale, vpKeyFrameMatchedMP)), mRandomInt(random_int) {
+    check(orbm_sim3_create(device, &mHandle), "orbm_sim3_create");
+    const orbm_sim3_problem p = mFlat.problem();
+    const int rc = orbm_sim3_set_problem(mHandle, &p);                             // (ends with SetRansacParameters(), :127)
+    if (rc != ORBG_OK) { orbm_sim3_destroy(mHandle); mHandle = nullptr; check(rc, "orbm_sim3_set_problem"); }
+  }
+  ~Sim3Solver() { if (mHandle) orbm_sim3_destroy(mHandle); }
+  Sim3Solver(const Sim3Solver&) = delete;
+  Sim3Solver& operator=(const Sim3Solver&) = delete;
+
+  const Sim3Flat& flat() const { return mFlat; }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+    check(orbm_sim3_set_ransac_parameters(mHandle, probability, minInliers, maxIterations), "orbm_sim3_set_ransac_parameters");
+    mMinInliers = minInliers;
+    mIterationsDone = 0;                                                           // :156
+    const int n = (int)mFlat.indices1.size();
+    if (n > 0) check(orbm_sim3_ransac_iterations(n, probability, minInliers, maxIterations, &mMaxIts), "orbm_sim3_ransac_iterations");
+    else mMaxIts = std::max(1, maxIterations);
+    mHaveParams = true;
+  }
+
+  MatT find(std::vector<bool>& vbInliers12, int& nInliers) {                       // :294-298
+    bool bFlag;
+    ensure_params();
+    return iterate(mMaxIts, bFlag, vbInliers12, nInliers);
+  }
+  MatT iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {                  // :159-240
+    const orbm_sim3_result r = run(nIterations, bNoMore, vbInliers, nInliers);
+    return r.converged ? to_mat(r.T12, 4, 4) : MatT();
+  }
+  MatT iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, bool& bConverge) { // :242-292
+    const orbm_sim3_result r = run(nIterations, bNoMore, vbInliers, nInliers);
+    bConverge = r.converged != 0;
+    return (r.converged || r.improved_in_this_call) ? to_mat(r.T12, 4, 4) : MatT();
+  }
+  MatT GetEstimatedRotation() { return mHaveBest ? to_mat(mBest.R, 3, 3) : MatT(); }
+  MatT GetEstimatedTranslation() { return mHaveBest ? to_mat(mBest.t, 3, 1) : MatT(); }
+  float GetEstimatedScale() { return mBest.s; }
+
+ private:
+  void ensure_params() {
+    if (!mHaveParams) {
+      const int n = (int)mFlat.indices1.size();
+      mMinInliers = 6; mMaxIts = 1;
+      if (n > 0) check(orbm_sim3_ransac_iterations(n, 0.99, 6, 300, &mMaxIts), "orbm_sim3_ransac_iterations");
+      mHaveParams = true;
+    }
+  }
+  static MatT to_mat(const float* d, int rows, int cols) { MatT m; dropin::make_mat(m, rows, cols, d); return m; }
+  // All draws of the call are taken BEFORE the launch (three per iteration, from lists of n, n - 1, n - 2 entries): after a call that
+  // converges early the generator has advanced further than in the reference, which stops drawing at the converged iteration.  Only the
+  // iterations that can still run before mRansacMaxIts are drawn for, so a loop that never converges draws exactly what the reference does.
+  orbm_sim3_result run(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {
+    ensure_params();
+    const int n = (int)mFlat.indices1.size();
+    const int H = std::max(0, std::min(nIterations, mMaxIts - mIterationsDone));     // S/Sim3Solver.cc:179
+    std::vector<int32_t> draws;
+    if (n >= 3 && n >= mMinInliers && H > 0) {
+      draws.reserve(3 * (size_t)H);
+      for (int k = 0; k < H; k++)
+        for (int j = 0; j < 3; j++) draws.push_back(mRandomInt(0, n - j - 1));
+    }
+    std::vector<uint8_t> mask(std::max(n, 1));
+    orbm_sim3_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.struct_size = sizeof(r); r.inliers = mask.data();
+    check(orbm_sim3_iterate(mHandle, std::max(nIterations, 0), draws.empty() ? nullptr : draws.data(), &r), "orbm_sim3_iterate");
+    mIterationsDone = r.iterations_done;
+    bNoMore = r.no_more != 0;
+    vbInliers = std::vector<bool>(mFlat.mN1, false);
+    nInliers = 0;
+    if (r.converged) {
+      nInliers = r.n_inliers;
+      for (int i = 0; i < n; i++) if (mask[i]) vbInliers[mFlat.indices1[i]] = true;   // :224-226
+    }
+    if (r.have_best) { mBest = r; mBest.inliers = nullptr; mHaveBest = true; }
+    return r;
+  }
+
+  Sim3Flat mFlat;
+  RandomIntT mRandomInt;
+  orbm_sim3* mHandle = nullptr;
+  orbm_sim3_result mBest{};
+  bool mHaveBest = false, mHaveParams = false;
+  int mMinInliers = 6, mMaxIts = 1, mIterationsDone = 0;    // mnIterations, as the handle reports it
+};
+
 }  // namespace orbgpu
 
 #endif  // ORBGPU_DROPIN_HPP_

@@ -147,6 +147,27 @@ class DatabaseView(C.Structure):
                 ("covis_kf", C.c_void_p), ("map_id", C.c_void_p), ("bad", C.c_void_p), ("map_bad", C.c_void_p)]
 
 
+class Sim3Problem(C.Structure):
+    """orbm_sim3_problem: what Sim3Solver's constructor keeps per surviving pair, flat."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("X3Dc1", C.c_void_p), ("X3Dc2", C.c_void_p),
+                ("max_err1", C.c_void_p), ("max_err2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("camera_model1", C.c_int32), ("camera_model2", C.c_int32), ("fix_scale", C.c_int32)]
+
+
+class Sim3Params(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32)]
+
+
+class Sim3Result(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("no_more", C.c_int32), ("converged", C.c_int32), ("n_inliers", C.c_int32),
+                ("iterations_done", C.c_int32), ("iterations_run", C.c_int32), ("improved_in_this_call", C.c_int32),
+                ("best_iteration", C.c_int32), ("have_best", C.c_int32), ("T12", C.c_float * 16), ("R", C.c_float * 9),
+                ("t", C.c_float * 3), ("s", C.c_float), ("inliers", C.c_void_p), ("hyp_n_inliers", C.c_void_p),
+                ("hyp_T12", C.c_void_p), ("hyp_masks", C.c_void_p)]
+
+
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
                 ("iters", C.c_int32 * 4), ("chi2", C.c_double * 4)]
@@ -181,6 +202,8 @@ EXPORTED_SYMBOLS = [
     "orbm_search_by_projection_frame_resident", "orbg_quiesce", "orbg_set_wait_policy", "orbg_get_wait_policy",
     "orbx_frame_mono", "orbx_frame_mono_dev", "orbx_frame_mono_submit", "orbx_frame_mono_dev_submit", "orbx_frame_mono_wait",
     "orbx_set_frame_outputs_un", "orbx_undistort_points",
+    "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
+    "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
@@ -219,6 +242,8 @@ def load():
     lib.orbg_version.restype = C.c_char_p
     lib.orbg_strerror.restype = C.c_char_p
     lib.orbg_strerror.argtypes = [C.c_int]
+    lib.orbm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
+    lib.orbm_sim3_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

@@ -865,3 +865,192 @@ class KeyFrameDatabase:
                                                           _vp(place_score), _vp(loop), C.byref(nl), _vp(merge), C.byref(nm)),
                    "orbd_detect_n_best_candidates")
         return loop[: nl.value].copy(), merge[: nm.value].copy()
+
+
+# ---------------------------------------------------------------- Sim3Solver (S/Sim3Solver.cc)
+
+def sim3_ransac_iterations(n, probability=0.99, minInliers=6, maxIterations=300):
+    """mRansacMaxIts of Sim3Solver::SetRansacParameters (S/Sim3Solver.cc:132-157) for N = n.  Host code, needs no device."""
+    out = C.c_int(0)
+    capi.check(capi.load().orbm_sim3_ransac_iterations(int(n), float(probability), int(minInliers), int(maxIterations), C.byref(out)),
+               "orbm_sim3_ransac_iterations")
+    return out.value
+
+
+def sim3_draws(n, n_iterations, rng):
+    """The raw DUtils::Random::RandomInt(0, size - 1) results of n_iterations iterations (S/Sim3Solver.cc:193): int32 (n_iterations, 3),
+    column j uniform in [0, n - j).  rng: a numpy Generator or a seed.  Tests, the checker and the solver below all draw through this."""
+    if not isinstance(rng, np.random.Generator):
+        rng = np.random.default_rng(rng)
+    d = np.empty((int(n_iterations), 3), np.int32)
+    for j in range(3):
+        d[:, j] = rng.integers(0, max(int(n) - j, 1), size=int(n_iterations))
+    return d
+
+
+def sim3_resolve_draws(n, draws):
+    """Raw draws -> the three correspondence indices of each minimal set (swap-with-back removal on mvAllIndices, :191-206)."""
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1, 3)
+    idx = np.zeros_like(d)
+    capi.check(capi.load().orbm_sim3_resolve_draws(int(n), _vp(d), len(d), _vp(idx)), "orbm_sim3_resolve_draws")
+    return idx
+
+
+class Sim3Problem:
+    """The flat problem Sim3Solver's constructor builds (S/Sim3Solver.cc:38-128): camera-frame points of the kept pairs, the truncated
+    thresholds 9.210 * sigma2 (uint32: the reference stores them in vector<size_t>), pinhole intrinsics (fx, fy, cx, cy) of the two
+    keyframes' cameras, mbFixScale, and mvnIndices1 / mN1 to map the kept pairs back to vpMatched12."""
+
+    def __init__(self, X3Dc1, X3Dc2, max_err1, max_err2, K1, K2, bFixScale, indices1=None, mN1=None):
+        self.X1 = np.ascontiguousarray(X3Dc1, np.float32).reshape(-1, 3)
+        self.X2 = np.ascontiguousarray(X3Dc2, np.float32).reshape(-1, 3)
+        self.e1 = np.ascontiguousarray(max_err1, np.uint32).reshape(-1)
+        self.e2 = np.ascontiguousarray(max_err2, np.uint32).reshape(-1)
+        self.n = len(self.X1)
+        assert len(self.X2) == self.n and len(self.e1) == self.n and len(self.e2) == self.n
+        self.K1 = tuple(float(v) for v in K1)
+        self.K2 = tuple(float(v) for v in K2)
+        self.fix_scale = bool(bFixScale)
+        self.indices1 = np.arange(self.n, dtype=np.int64) if indices1 is None else np.asarray(indices1, np.int64)
+        self.mN1 = int(mN1) if mN1 is not None else (int(self.indices1.max()) + 1 if self.n else 0)
+
+    def struct(self, camera_models=(0, 0)):
+        return capi.Sim3Problem(C.sizeof(capi.Sim3Problem), self.n, capi.ptr(self.X1), capi.ptr(self.X2), capi.ptr(self.e1), capi.ptr(self.e2),
+                                *self.K1, *self.K2, int(camera_models[0]), int(camera_models[1]), int(self.fix_scale))
+
+
+class Sim3Iteration:
+    """What one iterate() / find() call returned.  T12 is the five-argument overload's return value (the converged hypothesis, else the
+    best found during THIS call, else None); T12_four the four-argument one's (None unless converged).  vbInliers has length mN1 and
+    nInliers / vbInliers are zero unless converged, as in the reference.  best_* is the solver's state after the call."""
+
+    def __init__(self, prob, r, mask, hyp):
+        self.bNoMore, self.bConverge = bool(r.no_more), bool(r.converged)
+        self.iterations_done, self.iterations_run, self.best_iteration = r.iterations_done, r.iterations_run, r.best_iteration
+        self.improved = bool(r.improved_in_this_call)
+        self.have_best = bool(r.have_best)
+        self.best_T12 = np.array(r.T12, np.float32).reshape(4, 4) if self.have_best else None
+        self.best_R = np.array(r.R, np.float32).reshape(3, 3) if self.have_best else None
+        self.best_t = np.array(r.t, np.float32) if self.have_best else None
+        self.best_s = np.float32(r.s) if self.have_best else None
+        self.best_inliers = r.n_inliers
+        self.best_mask = mask.astype(bool)
+        self.nInliers = r.n_inliers if self.bConverge else 0
+        self.vbInliers = np.zeros(prob.mN1, bool)
+        if self.bConverge:
+            self.vbInliers[prob.indices1[self.best_mask]] = True
+        self.T12_four = self.best_T12 if self.bConverge else None
+        self.T12 = self.best_T12 if (self.bConverge or self.improved) else None
+        self.hyp_n_inliers, self.hyp_T12, self.hyp_masks = hyp
+
+
+def _sim3_result(prob, n_hyp, per_hypothesis):
+    mask = np.zeros(max(prob.n, 1), np.uint8)
+    hyp = (None, None, None)
+    if per_hypothesis:
+        hyp = (np.zeros(max(n_hyp, 1), np.int32), np.zeros((max(n_hyp, 1), 16), np.float32),
+               np.zeros((max(n_hyp, 1), max((prob.n + 63) // 64, 1)), np.uint64))
+    r = capi.Sim3Result()
+    r.struct_size = C.sizeof(capi.Sim3Result)
+    r.inliers = capi.ptr(mask)
+    r.hyp_n_inliers, r.hyp_T12, r.hyp_masks = (capi.ptr(a) for a in hyp)
+    return r, mask, hyp
+
+
+def _sim3_unpack(prob, r, mask, hyp, n_hyp):
+    if hyp[0] is not None:
+        bits = np.unpackbits(hyp[2][:n_hyp].view(np.uint8), axis=1, bitorder="little")[:, : prob.n].astype(bool)
+        hyp = (hyp[0][:n_hyp], hyp[1][:n_hyp].reshape(-1, 4, 4), bits)
+    return Sim3Iteration(prob, r, mask[: prob.n], hyp)
+
+
+class Sim3Solver:
+    """ORB_SLAM3::Sim3Solver (I/Sim3Solver.h:36-131) over a flat Sim3Problem: every hypothesis of a call in one kernel launch, the
+    serial choice among them replayed on the device.  Draws come from the caller (`draws`, raw RandomInt results as sim3_draws makes
+    them) or from the solver's own seeded generator."""
+
+    def __init__(self, problem, device=0, seed=0):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        self.prob = problem
+        self.rng = np.random.default_rng(seed)
+        self.device = device
+        capi.check(self.lib.orbm_sim3_create(device, C.byref(self.h)), "orbm_sim3_create")
+        st = problem.struct()
+        capi.check(self.lib.orbm_sim3_set_problem(self.h, C.byref(st)), "orbm_sim3_set_problem")
+        self.mRansacMinInliers = 6
+        self.mRansacMaxIts = sim3_ransac_iterations(problem.n, 0.99, 6, 300) if problem.n > 0 else 1
+        self._last = None
+        self._done = 0                       # mnIterations
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbm_sim3_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        capi.check(self.lib.orbm_sim3_set_stream(self.h, C.c_void_p(hip_stream) if hip_stream else None), "orbm_sim3_set_stream")
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        capi.check(self.lib.orbm_sim3_set_ransac_parameters(self.h, float(probability), int(minInliers), int(maxIterations)),
+                   "orbm_sim3_set_ransac_parameters")
+        self.mRansacMinInliers = int(minInliers)
+        self._done = 0
+        self.mRansacMaxIts = sim3_ransac_iterations(self.prob.n, probability, minInliers, maxIterations) if self.prob.n > 0 else max(1, int(maxIterations))
+
+    def iterate(self, nIterations, draws=None, per_hypothesis=False):
+        """-> Sim3Iteration.  draws: int32 (nIterations, 3) raw draws; None: taken from the solver's generator (all nIterations of them
+        before the launch, so after an early convergence the generator is further on than a serial loop's would be)."""
+        nIterations = int(nIterations)
+        if draws is None:
+            draws = sim3_draws(self.prob.n, nIterations, self.rng) if self.prob.n >= 3 else np.zeros((nIterations, 3), np.int32)
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1, 3)
+        assert len(d) >= min(nIterations, max(0, self.mRansacMaxIts - self._done)), "three raw draws per iteration that can still run"
+        r, mask, hyp = _sim3_result(self.prob, nIterations, per_hypothesis)
+        capi.check(self.lib.orbm_sim3_iterate(self.h, nIterations, _vp(d), C.byref(r)), "orbm_sim3_iterate")
+        n_hyp = min(nIterations, max(0, self.mRansacMaxIts - (r.iterations_done - r.iterations_run))) if self.prob.n >= self.mRansacMinInliers else 0
+        self._done = r.iterations_done
+        self._last = _sim3_unpack(self.prob, r, mask, hyp, n_hyp)
+        return self._last
+
+    def find(self, draws=None, per_hypothesis=False):
+        """cv::Mat Sim3Solver::find(vbInliers12, nInliers), S/Sim3Solver.cc:294-298 -> Sim3Iteration (T12_four is find's return value)."""
+        return self.iterate(self.mRansacMaxIts, draws, per_hypothesis)
+
+    def GetEstimatedRotation(self):
+        return None if self._last is None or not self._last.have_best else self._last.best_R.copy()
+
+    def GetEstimatedTranslation(self):
+        return None if self._last is None or not self._last.have_best else self._last.best_t.copy()
+
+    def GetEstimatedScale(self):
+        return None if self._last is None or not self._last.have_best else float(self._last.best_s)
+
+    @staticmethod
+    def solve_batch(problems, params=None, draws=None, device=0, seed=0, per_hypothesis=False):
+        """find() of len(problems) fresh solvers in ONE launch.  params: (probability, minInliers, maxIterations) per problem (None: the
+        defaults); draws: per problem the raw draws of mRansacMaxIts iterations (None: from a generator seeded with `seed`).
+        -> list of Sim3Iteration."""
+        lib = capi.load()
+        B = len(problems)
+        params = [(0.99, 6, 300)] * B if params is None else [tuple(p) for p in params]
+        rng = np.random.default_rng(seed)
+        its = [sim3_ransac_iterations(p.n, *q) if p.n > 0 else 1 for p, q in zip(problems, params)]
+        if draws is None:
+            draws = [sim3_draws(p.n, h, rng) if p.n >= 3 else np.zeros((h, 3), np.int32) for p, h in zip(problems, its)]
+        ds = [np.ascontiguousarray(d, np.int32).reshape(-1, 3) for d in draws]
+        for d, h, p, q in zip(ds, its, problems, params):
+            assert p.n < q[1] or len(d) >= h, "three raw draws per iteration of mRansacMaxIts"
+        P = (capi.Sim3Problem * max(B, 1))(*[p.struct() for p in problems])
+        Q = (capi.Sim3Params * max(B, 1))(*[capi.Sim3Params(float(q[0]), int(q[1]), int(q[2])) for q in params])
+        D = (C.c_void_p * max(B, 1))(*[d.ctypes.data for d in ds])
+        outs = [_sim3_result(p, h, per_hypothesis) for p, h in zip(problems, its)]
+        R = (capi.Sim3Result * max(B, 1))(*[o[0] for o in outs])
+        capi.check(lib.orbm_sim3_solve_batch(int(device), P, B, Q, D, R), "orbm_sim3_solve_batch")
+        return [_sim3_unpack(p, R[b], outs[b][1], outs[b][2], its[b] if p.n >= params[b][1] else 0) for b, p in enumerate(problems)]
