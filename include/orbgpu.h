@@ -488,6 +488,78 @@ int orbm_sim3_iterate(orbm_sim3* h, int n_iterations, const int32_t* draws, orbm
 int orbm_sim3_solve_batch(int device, const orbm_sim3_problem* problems, int B, const orbm_sim3_params* params,
                           const int32_t* const* draws, orbm_sim3_result* results);
 
+/* ---------------------------------------------------------------- OptimizeSim3 (server place recognition, step 4 of 5)
+ * int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+ *                             const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints),
+ * S/Optimizer.cc:4031-4310 -- the overload LoopClosing calls between the two SearchByProjection of DetectCommonRegionsFromBoW
+ * (S/LoopClosing.cc:782) and for every keyframe in DetectAndReffineSim3FromLastKF (:555).  The overloads at :3833 and :4312 have no
+ * caller and are not provided.  The per-candidate chain is now five exports: orbm_search_by_bow_kf -> orbm_sim3_iterate /
+ * orbm_sim3_solve_batch -> orbm_search_by_projection_sim3 (camera_project = 0) -> orbm_sim3_optimize ->
+ * orbm_search_by_projection_sim3 (camera_project = 1).
+ *
+ * The whole refinement -- optimize(5) with Huber, the removal of the pairs with chi2 > th2, optimize(10 or 5) without Huber, the
+ * final classification; every Levenberg-Marquardt iteration and trial, with g2o's numeric Jacobians (delta = 1e-9) -- runs in ONE
+ * kernel launch, and a batch of problems (the three loop + three merge candidates of up to four agents) in one launch too, one
+ * workgroup per problem.  Results do not depend on what else is in the batch, and two runs give the same bits.
+ *
+ * The flat problem is what the loop :4083-4223 hands to g2o per kept match i (orbgpu::sim3opt_collect in orbgpu_dropin.hpp builds
+ * it): X3Dc1 / X3Dc2 = P3D1c / P3D2c, the map points in the two camera frames AS THE FLOATS the reference computes (:4108, :4116);
+ * obs1 = pKF1->mvKeysUn[i].pt (:4164-4165), inv_sigma2_1 = pKF1->mvInvLevelSigma2[kpUn1.octave] (:4172); obs2 / inv_sigma2_2 the
+ * same for pKF2->mvKeysUn[i2] (:4186-4187, :4210) when pMP2 is observed in pKF2, and otherwise (i2 < 0, kept because bAllPoints)
+ * what :4192-4210 produce: obs2 = (x / z, y / z) of P3D2c -- NORMALISED coordinates, compared with a pixel projection -- and
+ * inv_sigma2_2 = mvInvLevelSigma2[0], because cv::KeyPoint(Point2f, mnTrackScaleLevel) sets `size` and leaves `octave` 0.  That is
+ * the reference's behaviour and is reproduced; such pairs are almost always removed in round 1.
+ * fx1 .. cy2: vSim3->pCamera1 / pCamera2 (:4056-4057, Pinhole::project, S/CameraModels/Pinhole.cpp:41-47); camera_model1/2 must be 0
+ * (pinhole), anything else is ORBG_BAD_ARG as in orbm_sim3_problem.  A mapped point with z <= 0 is not special-cased, and NaN / inf
+ * take the branches the reference's comparisons give them (chi2 > th2 is false for NaN: such a pair stays an inlier). */
+typedef struct orbm_sim3opt_problem {
+  uint32_t struct_size;
+  int32_t  n;                       /* edge pairs = vpEdges12.size() */
+  const float* X3Dc1;               /* n x 3, P3D1c (:4108) */
+  const float* X3Dc2;               /* n x 3, P3D2c (:4116) */
+  const float* obs1;                /* n x 2 (:4165) */
+  const float* obs2;                /* n x 2 (:4187 / :4198) */
+  const float* inv_sigma2_1;        /* n (:4172) */
+  const float* inv_sigma2_2;        /* n (:4210) */
+  float fx1, fy1, cx1, cy1;         /* vSim3->pCamera1 */
+  float fx2, fy2, cx2, cy2;         /* vSim3->pCamera2 */
+  int32_t camera_model1, camera_model2;
+  int32_t fix_scale;                /* bFixScale -> vSim3->_fix_scale (:4052) */
+  float   th2;                      /* th2; the Huber delta is sqrt(th2) computed in float (:4073) */
+  double  q[4], t[3], s;            /* g2oS12 on entry: rotation().coeffs() (x, y, z, w), translation(), scale() */
+  int32_t n_correspondences;        /* nCorrespondences (:4160; == n: every counted match gets its pair; the early return is worded on it) */
+} orbm_sim3opt_problem;
+
+/* removed[i] over the pairs: 0 kept, 1 NULL-ed at :4244 (round 1), 2 NULL-ed at :4294 (final pass); the caller sets
+ * vpMatches1[vnIndexEdge[i]] = NULL where it is not 0.  returned_early: the `return 0` at :4271 (nCorrespondences - nBad < 10) --
+ * q / t / s are then the INPUT (the reference does not write g2oS12 there) while `removed` carries the round-1 removals (vpMatches1 is
+ * already edited).  mAcumHessian is set to zero by the reference (:4280; the line that would fill it is commented out, :4299): the
+ * caller zeroes it unless returned_early.  trace (optional, trace_cap entries of 4 doubles): per LM iteration {round, lambda after
+ * the iteration, activeRobustChi2 after it, trials}.  edge_chi2 (optional, 4 x n doubles): chi2 of e12 / e21 as read at :4241 (the
+ * LAST trial's errors, no computeError before it) and as read at :4291 (recomputed; 0 for pairs that did not get there). */
+typedef struct orbm_sim3opt_result {
+  uint32_t struct_size;
+  int32_t  n_in;                    /* the return value */
+  int32_t  returned_early;
+  int32_t  n_bad_round1;            /* nBad (:4249) */
+  double   q[4], t[3], s;           /* g2oS12 after the call */
+  uint8_t* removed;                 /* n bytes, caller's (NULL: not wanted) */
+  int32_t  iters[2];                /* LM iterations run in each round */
+  double   chi2[2];                 /* activeRobustChi2 after the last accepted step of each round */
+  double*  trace;
+  int32_t  trace_cap, trace_len;
+  double*  edge_chi2;
+} orbm_sim3opt_result;
+
+/* One problem / B problems in one launch.  n == 0: no launch, the outcome g2o gives for an empty graph (optimize() does nothing,
+ * 0 - 0 < 10: n_in = 0, returned_early = 1, the input estimate).  All arguments and the device are checked before any result is
+ * written: struct_size, NULL arrays with n > 0, a non-finite q / t / s, th2 <= 0 (or NaN), a camera model other than pinhole ->
+ * ORBG_BAD_ARG; no device -> ORBG_NO_DEVICE (there is no CPU fallback).  The arguments are checked before the device is looked for.
+ * The work runs on the library's M stream of `device` (see "Streams"), with buffers that belong to the calling thread: concurrent
+ * calls from several threads are independent. */
+int orbm_sim3_optimize(int device, const orbm_sim3opt_problem* p, orbm_sim3opt_result* r);
+int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* problems, int B, orbm_sim3opt_result* results);
+
 /* ---------------------------------------------------------------- bag of words */
 
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> flattened (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:60-130,

@@ -15,6 +15,7 @@
 //   void LocalBundleAdjustment(KeyFrame*, bool* pbStopFlag, Map*, int& num_fixedKF, int)      I/Optimizer.h:42,   S/Optimizer.cc:1810-2410
 //   int  PoseOptimization(Frame*)                                                             I/Optimizer.h:47,   S/Optimizer.cc:964-1278
 //   class Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bFixScale, vpKeyFrameMatchedMP)  I/Sim3Solver.h:36-131, S/Sim3Solver.cc (orbgpu::Sim3Solver, at the end)
+//   int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)   S/Optimizer.cc:4031-4310 (orbgpu::OptimizeSim3, at the end)
 //
 // Matrix access goes through mat_f32 / mat_u8 / make_mat (overloads for cv::Mat below, for the mock in the test header).
 #ifndef ORBGPU_DROPIN_HPP_
@@ -30,6 +31,7 @@
 #include <mutex>
 #include <set>
 #include <stdexcept>
+#include <string>
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
@@ -1412,6 +1414,129 @@ class Sim3Solver {
   bool mHaveBest = false, mHaveParams = false;
   int mMinInliers = 6, mMaxIts = 1, mIterationsDone = 0;    // mnIterations, as the handle reports it
 };
+
+// ------------------------------------------------------------------------------------------------ OptimizeSim3
+// int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
+//                             const bool bFixScale, Eigen::Matrix<double,7,7>& mAcumHessian, const bool bAllPoints)
+// (S/Optimizer.cc:4031-4310) in two separable halves, like the solver above: sim3opt_collect() -- the loop over the matches
+// (:4083-4223), host only -- and the orbm_sim3_optimize call with the write-back.
+
+// What the loop hands to g2o, flat, plus vnIndexEdge and the loop's counters.
+struct Sim3OptFlat {
+  std::vector<float> X3Dc1, X3Dc2;             // P3D1c, P3D2c of the kept matches (the fixed VertexSBAPointXYZ estimates)
+  std::vector<float> obs1, obs2;               // the two measurements
+  std::vector<float> inv_sigma2_1, inv_sigma2_2;
+  std::vector<size_t> vnIndexEdge;
+  std::vector<bool> vbIsInKF2;
+  int nCorrespondences = 0, nBadMPs = 0, nInKF2 = 0, nOutKF2 = 0, nMatchWithoutMP = 0;
+  float k1[4] = {0, 0, 0, 0}, k2[4] = {0, 0, 0, 0};
+  int model1 = 0, model2 = 0;
+  orbm_sim3opt_problem problem(const double* q_xyzw, const double* t, double s, float th2, bool bFixScale) const {
+    orbm_sim3opt_problem p;
+    std::memset(&p, 0, sizeof(p));
+    p.struct_size = sizeof(p); p.n = (int32_t)vnIndexEdge.size();
+    p.X3Dc1 = X3Dc1.data(); p.X3Dc2 = X3Dc2.data(); p.obs1 = obs1.data(); p.obs2 = obs2.data();
+    p.inv_sigma2_1 = inv_sigma2_1.data(); p.inv_sigma2_2 = inv_sigma2_2.data();
+    p.fx1 = k1[0]; p.fy1 = k1[1]; p.cx1 = k1[2]; p.cy1 = k1[3]; p.fx2 = k2[0]; p.fy2 = k2[1]; p.cx2 = k2[2]; p.cy2 = k2[3];
+    p.camera_model1 = model1; p.camera_model2 = model2; p.fix_scale = bFixScale ? 1 : 0; p.th2 = th2;
+    for (int k = 0; k < 4; k++) p.q[k] = q_xyzw[k];
+    for (int k = 0; k < 3; k++) p.t[k] = t[k];
+    p.s = s; p.n_correspondences = nCorrespondences;
+    return p;
+  }
+};
+
+// The loop :4083-4223.  Two things it does that a reader would not guess, both reproduced: a match whose pMP2 is not observed in pKF2
+// (i2 < 0, kept only with bAllPoints) gets the NORMALISED coordinates of P3D2c as its observation, and its weight is
+// mvInvLevelSigma2[0] whatever pMP2->mnTrackScaleLevel says -- cv::KeyPoint(Point2f, mnTrackScaleLevel) sets `size`, not `octave`
+// (:4192-4210).  With pMP1 == NULL, pMP2->isBad() is read and the pair is skipped either way (:4128-4146); pMP2 is never NULL there (:4085).
+template <class KeyFrameT, class MapPointT>
+inline Sim3OptFlat sim3opt_collect(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatches1, bool bAllPoints) {
+  using dropin::mat_f32;
+  Sim3OptFlat f;
+  const auto R1w = pKF1->GetRotation(); const auto t1w = pKF1->GetTranslation();   // :4045-4048
+  const auto R2w = pKF2->GetRotation(); const auto t2w = pKF2->GetTranslation();
+  const int N = (int)vpMatches1.size();                                            // :4061
+  const auto vpMapPoints1 = pKF1->GetMapPointMatches();                            // :4062
+  // R * P3Dw + t on CV_32F is one gemm: double accumulation in k order, the translation added in double, rounded once
+  auto to_camera = [](const float* R, const float* t, const float* X, float* out) {
+    for (int i = 0; i < 3; i++)
+      out[i] = (float)((((double)R[3 * i] * (double)X[0] + (double)R[3 * i + 1] * (double)X[1]) + (double)R[3 * i + 2] * (double)X[2]) + (double)t[i]);
+  };
+  for (int i = 0; i < N; i++) {
+    if (!vpMatches1[i]) continue;                                                  // :4085
+    auto* pMP1 = vpMapPoints1[i];
+    MapPointT* pMP2 = vpMatches1[i];
+    const int i2 = std::get<0>(pMP2->GetIndexInKeyFrame(pKF2));                    // :4094
+    float P3D1c[3], P3D2c[3];
+    if (pMP1 && pMP2) {
+      if (!pMP1->isBad() && !pMP2->isBad()) {                                      // :4104
+        const auto P3D1w = pMP1->GetWorldPos(); const auto P3D2w = pMP2->GetWorldPos();
+        to_camera(mat_f32(R1w), mat_f32(t1w), mat_f32(P3D1w), P3D1c);              // :4108
+        to_camera(mat_f32(R2w), mat_f32(t2w), mat_f32(P3D2w), P3D2c);              // :4116
+      } else {
+        f.nBadMPs++;
+        continue;
+      }
+    } else {
+      f.nMatchWithoutMP++;                                                         // :4130
+      (void)pMP2->isBad();                                                         // :4133: a vertex nobody uses, then `continue`
+      continue;
+    }
+    if (i2 < 0 && !bAllPoints) continue;                                           // :4148
+    if (P3D2c[2] < 0) continue;                                                    // :4154, on the float
+    f.nCorrespondences++;
+    const auto& kpUn1 = pKF1->mvKeysUn[i];                                         // :4164
+    f.obs1.push_back(kpUn1.pt.x); f.obs1.push_back(kpUn1.pt.y);
+    f.inv_sigma2_1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);                // :4172
+    if (i2 >= 0) {
+      const auto& kpUn2 = pKF2->mvKeysUn[i2];                                      // :4186
+      f.obs2.push_back(kpUn2.pt.x); f.obs2.push_back(kpUn2.pt.y);
+      f.inv_sigma2_2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);              // :4210
+      f.nInKF2++;
+    } else {
+      const float invz = 1 / P3D2c[2];                                             // :4194-4196
+      f.obs2.push_back(P3D2c[0] * invz); f.obs2.push_back(P3D2c[1] * invz);
+      f.inv_sigma2_2.push_back(pKF2->mvInvLevelSigma2[0]);                         // :4199, :4210: kpUn2.octave is 0
+      f.nOutKF2++;
+    }
+    for (int k = 0; k < 3; k++) { f.X3Dc1.push_back(P3D1c[k]); f.X3Dc2.push_back(P3D2c[k]); }
+    f.vnIndexEdge.push_back((size_t)i);                                            // :4220
+    f.vbIsInKF2.push_back(i2 >= 0);
+  }
+  f.model1 = (int)pKF1->mpCamera->GetType(); f.model2 = (int)pKF2->mpCamera->GetType();   // vSim3->pCamera1 / pCamera2, :4056-4057
+  for (int k = 0; k < 4; k++) { f.k1[k] = pKF1->mpCamera->getParameter(k); f.k2[k] = pKF2->mpCamera->getParameter(k); }
+  return f;
+}
+
+// Sim3T: g2o::Sim3 -- rotation().coeffs() (x, y, z, w), translation(), scale() and Sim3T(Quaterniond(w, x, y, z), Vector3d(x, y, z), s).
+// Matrix7T: anything with operator()(i, j) (Eigen::Matrix<double, 7, 7>).  Throws std::runtime_error when the library refuses the
+// call (no device, a camera model other than pinhole): there is no CPU fallback.
+template <class KeyFrameT, class MapPointT, class Sim3T, class Matrix7T>
+inline int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2,
+                        const bool bFixScale, Matrix7T& mAcumHessian, const bool bAllPoints = false, int device = 0) {
+  const Sim3OptFlat f = sim3opt_collect<KeyFrameT, MapPointT>(pKF1, pKF2, vpMatches1, bAllPoints);
+  const auto& r0 = g2oS12.rotation().coeffs();
+  const auto& t0 = g2oS12.translation();
+  const double q[4] = {r0[0], r0[1], r0[2], r0[3]}, t[3] = {t0[0], t0[1], t0[2]};
+  const orbm_sim3opt_problem p = f.problem(q, t, g2oS12.scale(), th2, bFixScale);
+  std::vector<uint8_t> removed(f.vnIndexEdge.size() + 1, 0);
+  orbm_sim3opt_result r;
+  std::memset(&r, 0, sizeof(r));
+  r.struct_size = sizeof(r);
+  r.removed = removed.data();
+  const int rc = orbm_sim3_optimize(device, &p, &r);
+  if (rc != ORBG_OK) throw std::runtime_error(std::string("orbm_sim3_optimize: ") + orbg_strerror(rc));
+  for (size_t i = 0; i < f.vnIndexEdge.size(); i++)
+    if (removed[i]) vpMatches1[f.vnIndexEdge[i]] = static_cast<MapPointT*>(nullptr);       // :4244, :4294
+  if (r.returned_early) return 0;                                                          // :4271: g2oS12 and mAcumHessian untouched
+  for (int i = 0; i < 7; i++)
+    for (int j = 0; j < 7; j++) mAcumHessian(i, j) = 0.0;                                  // :4280 (the line that would fill it is commented out)
+  using QuatT = typename std::decay<decltype(g2oS12.rotation())>::type;
+  using VecT = typename std::decay<decltype(g2oS12.translation())>::type;
+  g2oS12 = Sim3T(QuatT(r.q[3], r.q[0], r.q[1], r.q[2]), VecT(r.t[0], r.t[1], r.t[2]), r.s);   // :4306
+  return r.n_in;
+}
 
 }  // namespace orbgpu
 

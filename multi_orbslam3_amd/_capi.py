@@ -168,6 +168,23 @@ class Sim3Result(C.Structure):
                 ("hyp_T12", C.c_void_p), ("hyp_masks", C.c_void_p)]
 
 
+class Sim3OptProblem(C.Structure):
+    """orbm_sim3opt_problem: what OptimizeSim3's loop over the matches hands to g2o, flat."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("X3Dc1", C.c_void_p), ("X3Dc2", C.c_void_p),
+                ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p), ("inv_sigma2_2", C.c_void_p),
+                ("fx1", C.c_float), ("fy1", C.c_float), ("cx1", C.c_float), ("cy1", C.c_float),
+                ("fx2", C.c_float), ("fy2", C.c_float), ("cx2", C.c_float), ("cy2", C.c_float),
+                ("camera_model1", C.c_int32), ("camera_model2", C.c_int32), ("fix_scale", C.c_int32), ("th2", C.c_float),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("n_correspondences", C.c_int32)]
+
+
+class Sim3OptResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_in", C.c_int32), ("returned_early", C.c_int32), ("n_bad_round1", C.c_int32),
+                ("q", C.c_double * 4), ("t", C.c_double * 3), ("s", C.c_double), ("removed", C.c_void_p),
+                ("iters", C.c_int32 * 2), ("chi2", C.c_double * 2), ("trace", C.c_void_p), ("trace_cap", C.c_int32),
+                ("trace_len", C.c_int32), ("edge_chi2", C.c_void_p)]
+
+
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
                 ("iters", C.c_int32 * 4), ("chi2", C.c_double * 4)]
@@ -204,6 +221,7 @@ EXPORTED_SYMBOLS = [
     "orbx_set_frame_outputs_un", "orbx_undistort_points",
     "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
     "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
+    "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
@@ -244,6 +262,8 @@ def load():
     lib.orbg_strerror.argtypes = [C.c_int]
     lib.orbm_sim3_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]
     lib.orbm_sim3_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
+    lib.orbm_sim3_optimize.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.orbm_sim3_optimize_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

@@ -1054,3 +1054,160 @@ class Sim3Solver:
         R = (capi.Sim3Result * max(B, 1))(*[o[0] for o in outs])
         capi.check(lib.orbm_sim3_solve_batch(int(device), P, B, Q, D, R), "orbm_sim3_solve_batch")
         return [_sim3_unpack(p, R[b], outs[b][1], outs[b][2], its[b] if p.n >= params[b][1] else 0) for b, p in enumerate(problems)]
+
+
+# ---------------------------------------------------------------- OptimizeSim3 (S/Optimizer.cc:4031-4310)
+
+class Sim3OptProblem:
+    """The flat problem OptimizeSim3's loop over the matches hands to g2o (S/Optimizer.cc:4083-4223): per kept match the map points
+    in the two camera frames as float32 (P3D1c, P3D2c), the two observations and their invSigma2, the pinhole intrinsics
+    (fx, fy, cx, cy) of pCamera1 / pCamera2, bFixScale, th2, and g2oS12 as q (x, y, z, w), t, s in float64.  index_edge = vnIndexEdge."""
+
+    def __init__(self, X3Dc1, X3Dc2, obs1, obs2, inv_sigma2_1, inv_sigma2_2, K1, K2, bFixScale, th2, q, t, s, index_edge=None,
+                 n_correspondences=None):
+        f = np.float32
+        self.X1 = np.ascontiguousarray(X3Dc1, f).reshape(-1, 3)
+        self.X2 = np.ascontiguousarray(X3Dc2, f).reshape(-1, 3)
+        self.obs1 = np.ascontiguousarray(obs1, f).reshape(-1, 2)
+        self.obs2 = np.ascontiguousarray(obs2, f).reshape(-1, 2)
+        self.w1 = np.ascontiguousarray(inv_sigma2_1, f).reshape(-1)
+        self.w2 = np.ascontiguousarray(inv_sigma2_2, f).reshape(-1)
+        self.n = len(self.X1)
+        assert all(len(a) == self.n for a in (self.X2, self.obs1, self.obs2, self.w1, self.w2))
+        self.K1 = tuple(float(v) for v in K1)
+        self.K2 = tuple(float(v) for v in K2)
+        self.fix_scale = bool(bFixScale)
+        self.th2 = float(th2)
+        self.q = np.array(q, np.float64).reshape(4)
+        self.t = np.array(t, np.float64).reshape(3)
+        self.s = float(s)
+        self.index_edge = np.arange(self.n, dtype=np.int64) if index_edge is None else np.asarray(index_edge, np.int64)
+        self.n_correspondences = self.n if n_correspondences is None else int(n_correspondences)
+
+    def struct(self, camera_models=(0, 0)):
+        st = capi.Sim3OptProblem()
+        st.struct_size = C.sizeof(capi.Sim3OptProblem)
+        st.n = self.n
+        st.X3Dc1, st.X3Dc2, st.obs1, st.obs2 = capi.ptr(self.X1), capi.ptr(self.X2), capi.ptr(self.obs1), capi.ptr(self.obs2)
+        st.inv_sigma2_1, st.inv_sigma2_2 = capi.ptr(self.w1), capi.ptr(self.w2)
+        st.fx1, st.fy1, st.cx1, st.cy1 = self.K1
+        st.fx2, st.fy2, st.cx2, st.cy2 = self.K2
+        st.camera_model1, st.camera_model2 = int(camera_models[0]), int(camera_models[1])
+        st.fix_scale = int(self.fix_scale)
+        st.th2 = self.th2
+        st.q[:] = self.q.tolist()
+        st.t[:] = self.t.tolist()
+        st.s = self.s
+        st.n_correspondences = self.n_correspondences
+        return st
+
+
+class Sim3OptResult:
+    """What OptimizeSim3 returned: nIn (its return value), returned_early (the `return 0` at :4271: q / t / s are then the input),
+    q / t / s and S12 = [sR t; 0 1] (4 x 4 float64), removed (per pair: 0 kept, 1 / 2 NULL-ed in round 1 / in the final pass), trace
+    (per LM iteration: round, lambda, chi2, trials), edge_chi2 (4 x n) when asked for."""
+
+    def __init__(self, prob, r, removed, trace, edge_chi2):
+        self.nIn, self.returned_early, self.n_bad_round1 = int(r.n_in), bool(r.returned_early), int(r.n_bad_round1)
+        self.q, self.t, self.s = np.array(r.q[:], np.float64), np.array(r.t[:], np.float64), float(r.s)
+        x, y, z, w = self.q
+        R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                      [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+        self.S12 = np.eye(4)
+        self.S12[:3, :3] = self.s * R
+        self.S12[:3, 3] = self.t
+        self.removed = removed[: prob.n].copy()
+        self.iters = (int(r.iters[0]), int(r.iters[1]))
+        self.chi2 = (float(r.chi2[0]), float(r.chi2[1]))
+        self.trace = trace[: r.trace_len].copy()
+        self.edge_chi2 = None if edge_chi2 is None else edge_chi2[:, : prob.n].copy()
+        self.index_edge = prob.index_edge
+
+    def apply(self, vpMatches1, null=-1):
+        """vpMatches1[vnIndexEdge[i]] = NULL for every removed pair (:4244, :4294), in place."""
+        vpMatches1[self.index_edge[self.removed != 0]] = null
+        return vpMatches1
+
+
+def _sim3opt_result(prob, edge_chi2):
+    removed = np.zeros(max(prob.n, 1), np.uint8)
+    trace = np.zeros((15, 4), np.float64)
+    chi = np.zeros((4, max(prob.n, 1)), np.float64) if edge_chi2 else None
+    r = capi.Sim3OptResult()
+    r.struct_size = C.sizeof(capi.Sim3OptResult)
+    r.removed, r.trace, r.trace_cap, r.edge_chi2 = capi.ptr(removed), capi.ptr(trace), 15, capi.ptr(chi)
+    return r, removed, trace, chi
+
+
+class _OptimizeSim3:
+    """int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints) on a flat Sim3OptProblem:
+    OptimizeSim3(problem) -> Sim3OptResult in one kernel launch; OptimizeSim3.batch([...]) refines every problem of the list in ONE
+    launch and returns what the single calls return, bit for bit."""
+
+    def __call__(self, problem, device=0, edge_chi2=False, camera_models=(0, 0)):
+        st = problem.struct(camera_models)
+        r, removed, trace, chi = _sim3opt_result(problem, edge_chi2)
+        capi.check(capi.load().orbm_sim3_optimize(int(device), C.byref(st), C.byref(r)), "orbm_sim3_optimize")
+        if chi is not None and problem.n > 0:
+            chi = chi.reshape(-1)[: 4 * problem.n].reshape(4, problem.n)
+        return Sim3OptResult(problem, r, removed, trace, chi)
+
+    def batch(self, problems, device=0, edge_chi2=False):
+        B = len(problems)
+        P = (capi.Sim3OptProblem * max(B, 1))(*[p.struct() for p in problems])
+        outs = [_sim3opt_result(p, edge_chi2) for p in problems]
+        R = (capi.Sim3OptResult * max(B, 1))(*[o[0] for o in outs])
+        capi.check(capi.load().orbm_sim3_optimize_batch(int(device), P, B, R), "orbm_sim3_optimize_batch")
+        res = []
+        for b, p in enumerate(problems):
+            chi = outs[b][3]
+            if chi is not None and p.n > 0:
+                chi = chi.reshape(-1)[: 4 * p.n].reshape(4, p.n)
+            res.append(Sim3OptResult(p, R[b], outs[b][1], outs[b][2], chi))
+        return res
+
+
+OptimizeSim3 = _OptimizeSim3()
+
+
+def sim3opt_collect(Tcw1, Tcw2, mp_of_kp1, keys1, octave1, inv_level_sigma2_1, keys2, octave2, inv_level_sigma2_2, vpMatches1, mp_pos,
+                    mp_bad, mp_index_in_kf2, K1, K2, g2oS12, th2, bFixScale, bAllPoints=True):
+    """The loop of OptimizeSim3 over the matches (S/Optimizer.cc:4083-4223) on plain arrays -> Sim3OptProblem (index_edge = vnIndexEdge).
+    Tcw1 / Tcw2: 4 x 4 float32 poses of pKF1 / pKF2; mp_of_kp1: map point id per keypoint of pKF1 or -1 (GetMapPointMatches); keys /
+    octave: mvKeysUn pt (N x 2) and octave; vpMatches1: map point id matched to keypoint i of pKF1 or -1; mp_pos / mp_bad /
+    mp_index_in_kf2: per map point GetWorldPos, isBad and GetIndexInKeyFrame(pKF2) (-1: not observed there); g2oS12 = (q xyzw, t, s).
+    Points go to the camera frames the way the reference's CV_32F product does (every entry accumulated in double, rounded once)."""
+    f, d = np.float32, np.float64
+    vp = np.asarray(vpMatches1, np.int64)
+    m1 = np.asarray(mp_of_kp1, np.int64)
+    mp_pos = np.asarray(mp_pos, f).reshape(-1, 3)
+    mp_bad = np.asarray(mp_bad, bool)
+    idx2 = np.asarray(mp_index_in_kf2, np.int64)
+    i = np.nonzero(vp >= 0)[0]                                      # :4085
+    i = i[m1[i] >= 0]                                               # pMP1 == NULL: counted, skipped (:4128-4146)
+    i = i[~(mp_bad[m1[i]] | mp_bad[vp[i]])]                         # :4104
+    i2 = idx2[vp[i]]
+    if not bAllPoints:                                              # :4148
+        i, i2 = i[i2 >= 0], i2[i2 >= 0]
+
+    def to_cam(T, P):
+        T = np.asarray(T, f).astype(d)
+        P = P.astype(d)
+        return np.stack([((T[r, 0] * P[:, 0] + T[r, 1] * P[:, 1]) + T[r, 2] * P[:, 2]) + T[r, 3] for r in range(3)], 1).astype(f)
+    P1, P2 = to_cam(Tcw1, mp_pos[m1[i]]), to_cam(Tcw2, mp_pos[vp[i]])
+    keep = ~(P2[:, 2] < 0)                                          # :4154, on the float
+    i, i2, P1, P2 = i[keep], i2[keep], P1[keep], P2[keep]
+    keys1, keys2 = np.asarray(keys1, f).reshape(-1, 2), np.asarray(keys2, f).reshape(-1, 2)
+    s1, s2 = np.asarray(inv_level_sigma2_1, f), np.asarray(inv_level_sigma2_2, f)
+    obs1, w1 = keys1[i], s1[np.asarray(octave1, np.int64)[i]]
+    inside = i2 >= 0
+    j2 = np.where(inside, i2, 0)
+    with np.errstate(all="ignore"):
+        invz = f(1) / P2[:, 2]                                      # :4194-4198: normalised coordinates as the observation
+        norm = np.stack([P2[:, 0] * invz, P2[:, 1] * invz], 1).astype(f)
+    obs2 = np.where(inside[:, None], keys2[j2] if len(keys2) else norm, norm).astype(f)
+    # cv::KeyPoint(Point2f, mnTrackScaleLevel) sets `size`: the octave stays 0 (:4199, :4210)
+    w2 = np.where(inside, s2[np.asarray(octave2, np.int64)[j2]] if len(keys2) else s2[0], s2[0]).astype(f)
+    q, t, s = g2oS12
+    return Sim3OptProblem(P1, P2, obs1, obs2, w1, w2, K1, K2, bFixScale, th2, q, t, s, index_edge=i)
