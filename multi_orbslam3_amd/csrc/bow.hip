@@ -368,20 +368,24 @@ extern "C" int orbm_distinctive_descriptors(int device, const uint8_t* desc, con
   const int total = start[m];
   if (start[0] != 0 || total < 0 || (total > 0 && !desc)) return ORBG_BAD_ARG;
   for (int i = 0; i < m; i++) if (start[i + 1] < start[i] || start[i + 1] - start[i] > 65535) return ORBG_BAD_ARG;
-  int rc = select_device(device);
+  struct Bufs {
+    DevBuf<uint8_t> d_desc; DevBuf<int> d_start, d_best;
+    void release_buffers() { d_desc.release(); d_start.release(); d_best.release(); }
+  };
+  // the calling thread's work area and its kept stream: the library's M stream (never the legacy null stream); with ORBG_STREAM_POOL=0
+  // one stream of its own per calling thread, kept until the thread exits
+  static thread_local orbg::WorkArea<Bufs> sc;
+  int rc = sc.open(device, "misc");
   if (rc) return rc;
-  struct Scratch { DevBuf<uint8_t> d_desc; DevBuf<int> d_start, d_best; int device = -1; };
-  static thread_local Scratch sc;
-  if (sc.device != device) { sc.d_desc.release(); sc.d_start.release(); sc.d_best.release(); sc.device = device; }
   if ((rc = sc.d_desc.reserve((size_t)std::max(total, 1) * 32)) || (rc = sc.d_start.reserve(m + 1)) || (rc = sc.d_best.reserve(m))) return rc;
-  orbg::MiscStream ms;                                 // the library's M stream (never the legacy null stream)
-  if ((rc = ms.open())) return rc;
-  if (total > 0) ORBG_HIP(hipMemcpyAsync(sc.d_desc.p, desc, (size_t)total * 32, hipMemcpyHostToDevice, ms.s));
-  ORBG_HIP(hipMemcpyAsync(sc.d_start.p, start, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ms.s));
-  hipLaunchKernelGGL(distinctive_kernel, dim3(m), dim3(64), 0, ms.s, sc.d_desc.p, sc.d_start.p, m, sc.d_best.p);
+  const hipStream_t st = sc.stream;
+  const orbg::StreamDrain drain{st};
+  if (total > 0) ORBG_HIP(hipMemcpyAsync(sc.d_desc.p, desc, (size_t)total * 32, hipMemcpyHostToDevice, st));
+  ORBG_HIP(hipMemcpyAsync(sc.d_start.p, start, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(distinctive_kernel, dim3(m), dim3(64), 0, st, sc.d_desc.p, sc.d_start.p, m, sc.d_best.p);
   ORBG_HIP(hipGetLastError());
-  ORBG_HIP(hipMemcpyAsync(best, sc.d_best.p, (size_t)m * 4, hipMemcpyDeviceToHost, ms.s));
-  ORBG_HIP(hipStreamSynchronize(ms.s));
+  ORBG_HIP(hipMemcpyAsync(best, sc.d_best.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+  ORBG_HIP(hipStreamSynchronize(st));
   return ORBG_OK;
 }
 
@@ -391,29 +395,31 @@ extern "C" int orbv_score_l1(int device, const int32_t* q_word, const double* q_
   if (m == 0) return ORBG_OK;
   const int total = cand_start[m];
   if (cand_start[0] != 0 || total < 0 || (total > 0 && (!cand_word || !cand_value))) return ORBG_BAD_ARG;
-  int rc = select_device(device);
+  struct Bufs {
+    DevBuf<int> qw, cs, cw; DevBuf<double> qv, cv, sc;
+    void release_buffers() { qw.release(); cs.release(); cw.release(); qv.release(); cv.release(); sc.release(); }
+  };
+  static thread_local orbg::WorkArea<Bufs> t;            // (as above: the kept M stream, or the thread's own without the pool)
+  int rc = t.open(device, "misc");
   if (rc) return rc;
-  struct Scratch { DevBuf<int> qw, cs, cw; DevBuf<double> qv, cv, sc; int device = -1; };
-  static thread_local Scratch t;
-  if (t.device != device) { t.qw.release(); t.cs.release(); t.cw.release(); t.qv.release(); t.cv.release(); t.sc.release(); t.device = device; }
   if ((rc = t.qw.reserve(std::max(nq, 1))) || (rc = t.qv.reserve(std::max(nq, 1))) || (rc = t.cs.reserve(m + 1)) ||
       (rc = t.cw.reserve(std::max(total, 1))) || (rc = t.cv.reserve(std::max(total, 1))) || (rc = t.sc.reserve(m)))
     return rc;
-  orbg::MiscStream ms;
-  if ((rc = ms.open())) return rc;
+  const hipStream_t st = t.stream;
+  const orbg::StreamDrain drain{st};
   if (nq > 0) {
-    ORBG_HIP(hipMemcpyAsync(t.qw.p, q_word, (size_t)nq * 4, hipMemcpyHostToDevice, ms.s));
-    ORBG_HIP(hipMemcpyAsync(t.qv.p, q_value, (size_t)nq * 8, hipMemcpyHostToDevice, ms.s));
+    ORBG_HIP(hipMemcpyAsync(t.qw.p, q_word, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    ORBG_HIP(hipMemcpyAsync(t.qv.p, q_value, (size_t)nq * 8, hipMemcpyHostToDevice, st));
   }
-  ORBG_HIP(hipMemcpyAsync(t.cs.p, cand_start, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, ms.s));
+  ORBG_HIP(hipMemcpyAsync(t.cs.p, cand_start, (size_t)(m + 1) * 4, hipMemcpyHostToDevice, st));
   if (total > 0) {
-    ORBG_HIP(hipMemcpyAsync(t.cw.p, cand_word, (size_t)total * 4, hipMemcpyHostToDevice, ms.s));
-    ORBG_HIP(hipMemcpyAsync(t.cv.p, cand_value, (size_t)total * 8, hipMemcpyHostToDevice, ms.s));
+    ORBG_HIP(hipMemcpyAsync(t.cw.p, cand_word, (size_t)total * 4, hipMemcpyHostToDevice, st));
+    ORBG_HIP(hipMemcpyAsync(t.cv.p, cand_value, (size_t)total * 8, hipMemcpyHostToDevice, st));
   }
-  hipLaunchKernelGGL(bow_score_l1_kernel, dim3((m + 63) / 64), dim3(64), 0, ms.s, t.qw.p, t.qv.p, nq, t.cs.p, t.cw.p, t.cv.p, m, t.sc.p);
+  hipLaunchKernelGGL(bow_score_l1_kernel, dim3((m + 63) / 64), dim3(64), 0, st, t.qw.p, t.qv.p, nq, t.cs.p, t.cw.p, t.cv.p, m, t.sc.p);
   ORBG_HIP(hipGetLastError());
-  ORBG_HIP(hipMemcpyAsync(score, t.sc.p, (size_t)m * 8, hipMemcpyDeviceToHost, ms.s));
-  ORBG_HIP(hipStreamSynchronize(ms.s));
+  ORBG_HIP(hipMemcpyAsync(score, t.sc.p, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  ORBG_HIP(hipStreamSynchronize(st));
   return ORBG_OK;
 }
 

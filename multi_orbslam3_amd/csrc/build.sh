@@ -7,8 +7,14 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function"
 mkdir -p "$HERE/obj"
 pids=()
+# an object is rebuilt when its source, any header / include file here, the public header or this script is newer than it
+DEPS=("$HERE"/*.hpp "$HERE"/*.inc "$HERE/../../include/orbgpu.h" "$HERE/build.sh")
 for f in extractor matcher lba pose_opt bow sim3 sim3_opt; do
-  if [ ! -f "$HERE/obj/$f.o" ] || [ "$HERE/$f.hip" -nt "$HERE/obj/$f.o" ] || [ "$HERE/common.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/wave.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/stereo_finalize.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/ldlt_mfma.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/ldlt_xcd.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/se3.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/grid_build.hpp" -nt "$HERE/obj/$f.o" ] || [ "$HERE/ldlt_jump_tables.inc" -nt "$HERE/obj/$f.o" ] || [ "$HERE/orb_pattern_data.inc" -nt "$HERE/obj/$f.o" ] || [ "$HERE/build.sh" -nt "$HERE/obj/$f.o" ] || [ "$HERE/../../include/orbgpu.h" -nt "$HERE/obj/$f.o" ]; then
+  stale=0
+  for d in "$HERE/$f.hip" "${DEPS[@]}"; do
+    if [ "$d" -nt "$HERE/obj/$f.o" ]; then stale=1; break; fi
+  done
+  if [ ! -f "$HERE/obj/$f.o" ] || [ $stale = 1 ]; then
     $HIPCC $FLAGS -c "$HERE/$f.hip" -o "$HERE/obj/$f.o" &
     pids+=($!)
   fi

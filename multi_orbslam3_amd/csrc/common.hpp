@@ -45,6 +45,9 @@ template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;                  // an owner: overwriting one would lose its allocation
+  DevBuf& operator=(const DevBuf&) = delete;
   int reserve(size_t n) {
     if (n <= cap) return ORBG_OK;
     if (p) { ORBG_HIP(hipFree(p)); p = nullptr; cap = 0; }
@@ -65,6 +68,9 @@ struct PinnedBuf {
   T* h = nullptr;
   T* d = nullptr;
   size_t cap = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
   int reserve(size_t n) {
     if (n <= cap) return ORBG_OK;
     if (h) { ORBG_HIP(hipHostFree(h)); h = nullptr; d = nullptr; cap = 0; }
@@ -84,8 +90,11 @@ struct PinnedBuf {
 struct StreamSignal {
   PinnedBuf<unsigned> word;
   unsigned seq = 0;
+  StreamSignal() = default;
+  StreamSignal(const StreamSignal&) = delete;
+  StreamSignal& operator=(const StreamSignal&) = delete;
   int init() { int rc = word.reserve(16); if (rc) return rc; word.h[0] = 0; return ORBG_OK; }
-  void release() { word.release(); }
+  void release() { word.release(); seq = 0; }   // (init() zeroes the next word: the count starts over with it)
   int post(hipStream_t st);      // enqueue the signal kernel (misc.cpp)
   // for kernels that post the signal themselves (DoneSig below): next sequence number + the word's device address
   int arm(unsigned* seq_out, volatile unsigned** flag_out) {
@@ -120,6 +129,15 @@ hipError_t create_stream(hipStream_t* st, const char* role);
 void release_stream(hipStream_t st);       // destroys a stream of its own; pool streams live as long as the process
 bool is_library_stream(hipStream_t st);    // one of the pool's streams (shared between handles: never capture on it, never destroy it)
 
+inline int select_device(int device) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) return ORBG_NO_DEVICE;
+  if (device < 0 || device >= n) return ORBG_BAD_ARG;
+  ORBG_HIP(hipSetDevice(device));
+  return ORBG_OK;
+}
+
 // *_set_stream (include/orbgpu.h, "Streams"): the handle's work goes to the caller's stream from now on; NULL = back to the library's
 // stream of the role.  The handle must be idle; its old stream is drained first.  A caller's stream is never destroyed by the library.
 inline int swap_stream(hipStream_t* slot, bool* external, void* user, const char* role) {
@@ -138,13 +156,43 @@ struct MiscStream {
   ~MiscStream() { if (s) { (void)hipStreamSynchronize(s); release_stream(s); } }
 };
 
-inline int select_device(int device) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) return ORBG_NO_DEVICE;
-  if (device < 0 || device >= n) return ORBG_BAD_ARG;
-  ORBG_HIP(hipSetDevice(device));
-  return ORBG_OK;
-}
+// for a call on a KEPT stream that copies into the caller's memory: however the scope is left, an error return included, nothing it
+// enqueued is still in flight afterwards (MiscStream does the same for its per-call stream)
+struct StreamDrain {
+  hipStream_t s;
+  ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
+// The work area of an entry point WITHOUT a handle (pose_optimize, orbm_sim3_solve_batch, ...: the reference calls a static member, so
+// the buffers belong to the calling thread: `static thread_local WorkArea<...>`), also the device half of a small handle.  Bufs holds
+// the site's buffers and `void release_buffers()`; the area adds the device they live on and the stream the calls run on.  It derives
+// FROM the buffers so that they are still alive when its destructor -- thread exit for a thread_local -- releases them.
+template <class Bufs>
+struct WorkArea : Bufs {
+  int device = -1;
+  hipStream_t stream = nullptr;
+  bool ext_stream = false;                 // `stream` is the caller's (swap_stream): never destroyed here
+  WorkArea() = default;
+  WorkArea(const WorkArea&) = delete;
+  WorkArea& operator=(const WorkArea&) = delete;
+  // selects `dev`; what the area holds on another device is released first; the stream of `role` is created on first use
+  int open(int dev, const char* role) {
+    int rc = select_device(dev);
+    if (rc) return rc;
+    if (device != dev) { release(); device = dev; }
+    if (!stream) { ORBG_HIP(create_stream(&stream, role)); ext_stream = false; }
+    return ORBG_OK;
+  }
+  // on the device the buffers live on, after the stream has drained.  Errors are swallowed: this also runs at thread and process exit.
+  void release() {
+    if (device < 0) return;
+    (void)hipSetDevice(device);
+    if (stream) { (void)hipStreamSynchronize(stream); if (!ext_stream) release_stream(stream); stream = nullptr; }
+    ext_stream = false;
+    Bufs::release_buffers();
+    device = -1;
+  }
+  ~WorkArea() { release(); }
+};
 
 }  // namespace orbg

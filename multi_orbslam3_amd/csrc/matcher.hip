@@ -1546,7 +1546,12 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   if ((nq > 0 && (!v->kps_left || !v->desc_left)) || (nt > 0 && (!v->kps_right || !v->desc_right))) return ORBG_BAD_ARG;
   for (int i = 0; i < nq; i++) { const int o = v->kps_left[v->mono_left + i].octave; if (o < 0 || o >= v->n_levels) return ORBG_BAD_ARG; }
   for (int i = 0; i < nt; i++) { const int o = v->kps_right[v->mono_right + i].octave; if (o < 0 || o >= v->n_levels) return ORBG_BAD_ARG; }
-  int rc = select_device(device);
+  struct Bufs {
+    PinnedBuf<uint8_t> in, out; DevBuf<uint8_t> din; StreamSignal sig;
+    void release_buffers() { in.release(); out.release(); din.release(); sig.release(); }
+  };
+  static thread_local orbg::WorkArea<Bufs> S;
+  int rc = S.open(device, "misc");                      // the library's M stream (kept: a stream object per call costs a synchronisation)
   if (rc) return rc;
   for (int i = 0; i < v->n_left; i++) { left_to_right[i] = -1; depth[i] = -1.0f; }
   for (int i = 0; i < v->n_right; i++) right_to_left[i] = -1;
@@ -1554,13 +1559,6 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   if (nq == 0 || nt < 2) return ORBG_OK;
   // one pinned block in (one copy to the device), results straight into mapped pinned memory (buffers of the calling thread, kept from
   // frame to frame); mvRightToLeftMatch and nMatches follow from mvLeftToRightMatch on the host (:1144-1145: the last left feature stays)
-  struct Scratch { int device = -1; PinnedBuf<uint8_t> in, out; DevBuf<uint8_t> din; StreamSignal sig; hipStream_t st = nullptr; };
-  static thread_local Scratch S;
-  if (S.device != device) {
-    S.in.release(); S.out.release(); S.din = DevBuf<uint8_t>(); S.sig.release(); S.sig = StreamSignal(); S.device = device;
-    if (S.st) { release_stream(S.st); S.st = nullptr; }
-    ORBG_HIP(create_stream(&S.st, "misc"));             // the library's M stream (kept: a stream object per call costs a synchronisation)
-  }
   auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
   const size_t o_kl = 0, o_kr = up(o_kl + (size_t)nq * sizeof(orbx_keypoint)), o_dl = up(o_kr + (size_t)nt * sizeof(orbx_keypoint)), o_dr = up(o_dl + (size_t)nq * 32),
                o_sg = up(o_dr + (size_t)nt * 32), in_bytes = up(o_sg + (size_t)v->n_levels * 4);
@@ -1571,7 +1569,7 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   memcpy(S.in.h + o_dl, v->desc_left + (size_t)v->mono_left * 32, (size_t)nq * 32);
   memcpy(S.in.h + o_dr, v->desc_right + (size_t)v->mono_right * 32, (size_t)nt * 32);
   memcpy(S.in.h + o_sg, v->level_sigma2, (size_t)v->n_levels * 4);
-  ORBG_HIP(hipMemcpyAsync(S.din.p, S.in.h, in_bytes, hipMemcpyHostToDevice, S.st));
+  ORBG_HIP(hipMemcpyAsync(S.din.p, S.in.h, in_bytes, hipMemcpyHostToDevice, S.stream));
   FisheyeDev D;
   D.nq = nq; D.nt = nt; D.mono_left = v->mono_left; D.mono_right = v->mono_right;
   D.kl = reinterpret_cast<const orbx_keypoint*>(S.din.p + o_kl); D.kr = reinterpret_cast<const orbx_keypoint*>(S.din.p + o_kr);
@@ -1579,9 +1577,9 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   D.cam1 = rig_cam_of(v->left); D.cam2 = rig_cam_of(v->right);
   memcpy(D.Tlr, v->Tlr, sizeof(D.Tlr));
   D.l2r = reinterpret_cast<int*>(S.out.d + p_l2r); D.depth = reinterpret_cast<float*>(S.out.d + p_dep); D.p3d = reinterpret_cast<float*>(S.out.d + p_p3d);
-  hipLaunchKernelGGL(fisheye_stereo_kernel, dim3((nq + 3) / 4), dim3(256), 0, S.st, D);
+  hipLaunchKernelGGL(fisheye_stereo_kernel, dim3((nq + 3) / 4), dim3(256), 0, S.stream, D);
   ORBG_HIP(hipGetLastError());
-  if ((rc = S.sig.sync(S.st))) return rc;
+  if ((rc = S.sig.sync(S.stream))) return rc;
   const int* h_l2r = reinterpret_cast<const int*>(S.out.h + p_l2r); const float* h_dep = reinterpret_cast<const float*>(S.out.h + p_dep);
   const float* h_p3d = reinterpret_cast<const float*>(S.out.h + p_p3d);
   int nm = 0;

@@ -7,6 +7,7 @@
 
 #include "common.hpp"
 #include "wave.hpp"
+#include "lm_block.hpp"
 #include "se3.hpp"
 
 using namespace orbg;
@@ -24,7 +25,7 @@ namespace {
 
 constexpr int kPoThreads = 256;
 constexpr int kPoMaxPer = 16;      // correspondences per thread (n <= 4096)
-constexpr int kPoLdsN = 1024;      // correspondences whose inputs are staged in LDS
+constexpr int kPoPinnedN = 1024;   // up to here the kernel reads its inputs from the pinned staging block, beyond from a device copy
 constexpr int kPoRow = 8 * 33;     // one reduction row: 8 segments of 32 values, padded against LDS bank conflicts
 
 // Block-wide sums of NV per-thread values in a fixed order: transpose through LDS, 8 threads per value add 32
@@ -49,60 +50,6 @@ __device__ inline void po_block_reduce(const double* vals, double* s_acc, double
     out[tid] = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
   }
   __syncthreads();
-}
-
-// Block-wide sum of ONE double per thread: DPP tree inside each wavefront, the four wave totals through LDS, added in wave
-// order by every thread (one barrier; `slot` alternates between consecutive calls so that no second barrier is needed).
-__device__ __forceinline__ double po_block_sum(double v, double (*wsum)[4], int slot) {
-  const double w = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) wsum[slot][threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((wsum[slot][0] + wsum[slot][1]) + wsum[slot][2]) + wsum[slot][3];
-}
-
-__device__ __forceinline__ double po_readlane(double v, int lane) {   // lane must be wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-
-// (H + lambda I) x = b by LDL^T without pivoting, spread over lanes 0..5 of a wave: lane `li` holds row li.  Every
-// subtraction happens in the order of a scalar left-looking factorisation (ascending k), so the factors are the
-// same bits a serial solve would produce.  Returns false unless every pivot is positive (Eigen::LDLT::isPositive),
-// in which case x is left untouched.  x[] comes out wave-uniform.
-__device__ inline bool po_solve6(const double* Hrow, double b_li, int li, double lambda, double* x) {
-  // (round 4, measured and dropped: the seven divisions as products with 1/d from the hardware seed + two Newton steps -- no
-  // measurable gain, 162 vs 158-164 us at 450 correspondences, and one of the twelve parity cases changed an iteration count)
-  double A[6], D[6];
-#pragma unroll
-  for (int j = 0; j < 6; j++) A[j] = Hrow[j] + (j == li ? lambda : 0.0);
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const double d = po_readlane(A[k], k);
-    if (!(d > 0.0) || fabs(d) == INFINITY) ok = false;
-    D[k] = d;
-    const double Lik = A[k] / d;
-#pragma unroll
-    for (int j = k + 1; j < 6; j++) { const double Ljk = po_readlane(Lik, j); A[j] -= (Lik * Ljk) * d; }
-    A[k] = Lik;
-  }
-  if (!ok) return false;
-  double y = b_li;
-#pragma unroll
-  for (int k = 0; k < 5; k++) { const double yk = po_readlane(y, k); if (li > k) y -= A[k] * yk; }
-  double Di = D[0];
-#pragma unroll
-  for (int k = 1; k < 6; k++) Di = (li == k) ? D[k] : Di;
-  y /= Di;
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double sv = po_readlane(y, i);
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) sv -= po_readlane(A[i], k) * x[k];
-    x[i] = sv;
-  }
-  return true;
 }
 
 // ---- two correspondences side by side.  A lone wavefront issues a DEPENDENT FP64 instruction every ~9 cycles and an independent
@@ -340,14 +287,12 @@ __device__ long long g_po_prof[16];
 #define PO_T0() do { } while (0)
 #define PO_ACC(slot) do { } while (0)
 #endif
-template <bool LDS_IN>      // LDS_IN: n <= kPoLdsN, the correspondences are staged in LDS (typed LDS accesses: a pointer that may be LDS or
-                            // global at run time turns every load into a flat_load with a full wait behind it)
-__global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float* g_Xw, const float* g_ou, const float* g_ov, const float* g_our,
-                                                             const float* g_oinv, Cam cam, PoseQ T0,
+// more than 2 * kPoWide correspondences (no rig): four wavefronts, a thread's correspondences re-read from global memory on every pass
+__global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float* Xw, const float* ou, const float* ov, const float* our,
+                                                             const float* oinv, Cam cam, PoseQ T0,
                                                              PoseQ* __restrict__ T_out, uint8_t* __restrict__ outlier_out,
                                                              int* __restrict__ stats /*n_bad, iters[4], .., [7] = seq*/,
                                                              double* __restrict__ chi_out, unsigned seq) {
-  __shared__ float s_in[7 * kPoLdsN];                    // correspondences staged once (they are re-read ~36 times)
   __shared__ double s_acc[28 * kPoRow];
   __shared__ double s_part[28 * 8];
   __shared__ double red[28];
@@ -361,16 +306,6 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
   const double dM = (float)sqrt(5.991), dS = (float)sqrt(7.815);
   const double dsqM = dM * dM, dsqS = dS * dS;
   for (int i = tid; i < n; i += kPoThreads) { s_chi2[i] = 0; s_out[i] = 0; }
-  if (LDS_IN) {
-    // the inputs may sit in mapped host memory (zero-copy): read them exactly once
-    for (int i = tid; i < 3 * n; i += kPoThreads) s_in[i] = g_Xw[i];
-    for (int i = tid; i < n; i += kPoThreads) { s_in[3 * n + i] = g_ou[i]; s_in[4 * n + i] = g_ov[i]; s_in[5 * n + i] = g_our[i]; s_in[6 * n + i] = g_oinv[i]; }
-  }
-  const float* const Xw = LDS_IN ? s_in : g_Xw;
-  const float* const ou = LDS_IN ? s_in + 3 * n : g_ou;
-  const float* const ov = LDS_IN ? s_in + 4 * n : g_ov;
-  const float* const our = LDS_IN ? s_in + 5 * n : g_our;
-  const float* const oinv = LDS_IN ? s_in + 6 * n : g_oinv;
   double x[6] = {0, 0, 0, 0, 0, 0};
   double lambda = 0, ni = 2, currentChi = 0;
   int nBadLM = 0;
@@ -384,7 +319,7 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
     T = T0;                                                   // setEstimate(toSE3Quat(mTcw)) every round (:1191)
     double cnt = 0;
     for (int i = tid; i < n; i += kPoThreads) cnt += !s_out[i];
-    const int n_active = (int)po_block_sum(cnt, s_wsum, sum_slot); sum_slot ^= 1;
+    const int n_active = (int)block_sum(cnt, s_wsum, sum_slot); sum_slot ^= 1;
     int done = 0;
     bool ok = n_active > 0;
     for (int it = 0; it < 10 && ok; it++) {
@@ -480,7 +415,7 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
           const int wv = tid >> 6;
           for (int cc = 0; cc < wv; cc++) { lam_c *= ni_c; ni_c *= 2; }
           double xc[6] = {x[0], x[1], x[2], x[3], x[4], x[5]};
-          const bool okc = po_solve6(Hrow, b_li, li, lam_c, xc);
+          const bool okc = lane_ldlt_solve<6>(Hrow, b_li, li, lam_c, xc);
           PoseQ Tc;
           pose_oplus_series(T, xc, &Tc);
           if ((tid & 63) == 0) {
@@ -535,7 +470,7 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
           if (act1) { s_chi2[i1] = e2.c2.b; tchi += e2.rho0.b; }
         }
         PO_ACC(3);
-        double tempChi = po_block_sum(tchi, s_wsum, sum_slot); sum_slot ^= 1;
+        double tempChi = block_sum(tchi, s_wsum, sum_slot); sum_slot ^= 1;
         PO_ACC(4);
         if (!ok2) tempChi = 1.7976931348623157e308;
         rho = currentChi - tempChi;
@@ -581,7 +516,7 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
       s_out[i] = bad;
       bl += bad;
     }
-    nBad = (int)po_block_sum(bl, s_wsum, sum_slot); sum_slot ^= 1;
+    nBad = (int)block_sum(bl, s_wsum, sum_slot); sum_slot ^= 1;
     if (round == 2) robust = false;                          // setRobustKernel(0)
     if (n < 10) break;                                        // optimizer.edges().size() < 10
   }
@@ -802,7 +737,7 @@ __global__ __launch_bounds__(kPoWide) void pose_opt_wide_kernel(int n, const flo
             for (int cc = 0; cc < wv; cc++) { lam_c *= ni_c; ni_c *= 2; }
             double xc[6] = {x[0], x[1], x[2], x[3], x[4], x[5]};
             PO_IN0();
-            const bool okc = po_solve6(Hrow, b_li, li, lam_c, xc);
+            const bool okc = lane_ldlt_solve<6>(Hrow, b_li, li, lam_c, xc);
             PO_IN(6);
             PoseQ Tc;
             pose_oplus_series(T, xc, &Tc);
@@ -915,34 +850,31 @@ extern "C" int pose_opt_debug_prof(long long* out, int reset) {
 }
 #endif
 
-// per-thread scratch of pose_optimize (PoseOptimization has no handle: the reference calls a static member); released when the thread exits
+// the calling thread's work area (common.hpp; PoseOptimization has no handle: the reference calls a static member)
 namespace {
-struct PoScratch {
-  PinnedBuf<uint8_t> stage; DevBuf<uint8_t> dev; int device = -1; hipStream_t stream = nullptr; bool ext_stream = false;
-  void drop_stream() { if (stream && !ext_stream) orbg::release_stream(stream); stream = nullptr; ext_stream = false; }
-  void drop() { stage.release(); dev.release(); drop_stream(); }
-  ~PoScratch() { drop(); }
+struct PoBufs {
+  PinnedBuf<uint8_t> stage; DevBuf<uint8_t> dev;
+  void release_buffers() { stage.release(); dev.release(); }
 };
-PoScratch& po_scratch() { static thread_local PoScratch sc; return sc; }
+WorkArea<PoBufs>& po_work() { static thread_local WorkArea<PoBufs> w; return w; }
 }  // namespace
 
 // the calling thread's pose_optimize calls on `device` use the caller's stream from now on (NULL: the library's M stream again)
 extern "C" int pose_opt_set_stream(int device, void* hip_stream) {
-  int rc = select_device(device);
+  WorkArea<PoBufs>& sc = po_work();
+  int rc = sc.open(device, "po");
   if (rc) return rc;
-  PoScratch& sc = po_scratch();
-  if (sc.device != device) { sc.drop(); sc.device = device; }
-  if (sc.stream) ORBG_HIP(hipStreamSynchronize(sc.stream));
-  sc.drop_stream();
-  if (hip_stream) { sc.stream = (hipStream_t)hip_stream; sc.ext_stream = true; }
-  return ORBG_OK;
+  return orbg::swap_stream(&sc.stream, &sc.ext_stream, hip_stream, "po");
 }
 
 extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   if (!p || !r || p->n < 0 || (p->n > 0 && (!p->Xw || !p->u || !p->v || !p->ur || !p->inv_sigma2 || !r->outlier))) return ORBG_BAD_ARG;
   if (p->n > kPoThreads * kPoMaxPer) return ORBG_CAP_EXCEEDED;
   if (p->rig && p->n > 8 * kPoWide) return ORBG_CAP_EXCEEDED;           // (the rig form runs on the wide kernel only: 4096 correspondences)
-  int rc = select_device(p->device);
+  // the thread's work area: one pinned staging block, inputs in, results out, kept across calls; the stream comes from the library's
+  // pool (common.hpp: role "po" = M, non-blocking like all of the library's streams) or from pose_opt_set_stream
+  WorkArea<PoBufs>& sc = po_work();
+  int rc = sc.open(p->device, "po");
   if (rc) return rc;
   const int n = p->n;
   memcpy(r->Tcw, p->Tcw, sizeof(float) * 16);
@@ -950,11 +882,6 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   for (int i = 0; i < 4; i++) { r->iters[i] = 0; r->chi2[i] = 0; }
   for (int i = 0; i < n; i++) r->outlier[i] = 0;
   if (n < 3) return ORBG_OK;                                  // S/Optimizer.cc:1180-1181
-  // one pinned staging block: inputs in, results out (a per-thread cache keeps the allocation across calls); the stream comes from
-  // the library's pool (common.hpp: role "po" = M, non-blocking like all of the library's streams) or from pose_opt_set_stream
-  PoScratch& sc = po_scratch();
-  if (sc.device != p->device) { sc.drop(); sc.device = p->device; }
-  if (!sc.stream) { ORBG_HIP(orbg::create_stream(&sc.stream, "po")); sc.ext_stream = false; }
   const size_t in_bytes = ((size_t)n * 7 * 4 + 15) & ~(size_t)15;
   const size_t out_off = in_bytes;
   const size_t out_bytes = sizeof(PoseQ) + 8 * sizeof(int) + 4 * sizeof(double) + (size_t)n + 64;
@@ -965,10 +892,10 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   memcpy(hs + 4 * (size_t)n, p->v, (size_t)n * 4);
   memcpy(hs + 5 * (size_t)n, p->ur, (size_t)n * 4);
   memcpy(hs + 6 * (size_t)n, p->inv_sigma2, (size_t)n * 4);
-  // small problems: the kernel reads its inputs straight from this pinned block (once, into LDS); large ones get a device copy.
-  // Results always land in the pinned block, followed by a sequence number the host spins on.
+  // small problems: the wide kernel reads its inputs straight from this pinned block (once, into registers); large ones are re-read
+  // on every pass and get a device copy.  Results always land in the pinned block, followed by a sequence number the host spins on.
   const float* dX;
-  if (n <= kPoLdsN) dX = reinterpret_cast<const float*>(sc.stage.d);
+  if (n <= kPoPinnedN) dX = reinterpret_cast<const float*>(sc.stage.d);
   else {
     ORBG_HIP(hipMemcpyAsync(sc.dev.p, sc.stage.h, in_bytes, hipMemcpyHostToDevice, sc.stream));
     dX = reinterpret_cast<const float*>(sc.dev.p);
@@ -994,28 +921,20 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   if (po_seq == 0) po_seq = 1;
   volatile int* seq_word = reinterpret_cast<volatile int*>(sc.stage.h + out_off + sizeof(PoseQ) + 4 * sizeof(double)) + 7;
   *seq_word = 0;
+  // one launch site for every form: the five input arrays lie one after the other behind dX
+  auto launch = [&](auto kernel, int threads, const auto& camera) {
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n, dX + 5 * (size_t)n,
+                       dX + 6 * (size_t)n, camera, T0, dT, dflag, dstats, dchi, po_seq);
+  };
   if (p->rig) {
     // a Frame with camera models / a second camera: the wide kernel over CamRig, up to eight correspondences per thread
-#define ORBG_PO_RIG(NP)                                                                                                              \
-  hipLaunchKernelGGL((pose_opt_wide_kernel<NP, CamRig>), dim3(1), dim3(kPoWide), 0, sc.stream, n, dX, dX + 3 * (size_t)n,            \
-                     dX + 4 * (size_t)n, dX + 5 * (size_t)n, dX + 6 * (size_t)n, rig, T0, dT, dflag, dstats, dchi, po_seq)
-    if (n <= kPoWide) ORBG_PO_RIG(1);
-    else if (n <= 2 * kPoWide) ORBG_PO_RIG(2);
-    else if (n <= 4 * kPoWide) ORBG_PO_RIG(4);
-    else ORBG_PO_RIG(8);
-#undef ORBG_PO_RIG
-  } else if (n <= kPoWide)
-    hipLaunchKernelGGL(pose_opt_wide_kernel<1>, dim3(1), dim3(kPoWide), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n,
-                       dX + 5 * (size_t)n, dX + 6 * (size_t)n, cam, T0, dT, dflag, dstats, dchi, po_seq);
-  else if (n <= 2 * kPoWide)
-    hipLaunchKernelGGL(pose_opt_wide_kernel<2>, dim3(1), dim3(kPoWide), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n,
-                       dX + 5 * (size_t)n, dX + 6 * (size_t)n, cam, T0, dT, dflag, dstats, dchi, po_seq);
-  else if (n <= kPoLdsN)
-    hipLaunchKernelGGL(pose_opt_kernel<true>, dim3(1), dim3(kPoThreads), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n,
-                       dX + 5 * (size_t)n, dX + 6 * (size_t)n, cam, T0, dT, dflag, dstats, dchi, po_seq);
-  else
-    hipLaunchKernelGGL(pose_opt_kernel<false>, dim3(1), dim3(kPoThreads), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n,
-                       dX + 5 * (size_t)n, dX + 6 * (size_t)n, cam, T0, dT, dflag, dstats, dchi, po_seq);
+    if (n <= kPoWide) launch(pose_opt_wide_kernel<1, CamRig>, kPoWide, rig);
+    else if (n <= 2 * kPoWide) launch(pose_opt_wide_kernel<2, CamRig>, kPoWide, rig);
+    else if (n <= 4 * kPoWide) launch(pose_opt_wide_kernel<4, CamRig>, kPoWide, rig);
+    else launch(pose_opt_wide_kernel<8, CamRig>, kPoWide, rig);
+  } else if (n <= kPoWide) launch(pose_opt_wide_kernel<1, Cam>, kPoWide, cam);
+  else if (n <= 2 * kPoWide) launch(pose_opt_wide_kernel<2, Cam>, kPoWide, cam);
+  else launch(pose_opt_kernel, kPoThreads, cam);
   ORBG_HIP(hipGetLastError());
   {
     bool got = false;

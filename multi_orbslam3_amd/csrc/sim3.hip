@@ -367,10 +367,7 @@ int ransac_iterations(int n, double probability, int min_inliers, int max_iterat
   return std::max(1, std::min(nIterations, max_iterations));
 }
 
-struct Sim3Work {                // device and staging buffers of one launch (a handle's, or the calling thread's for the batch form)
-  int device = -1;
-  hipStream_t stream = nullptr;
-  bool ext_stream = false;
+struct Sim3Bufs {                // device and staging buffers of one launch (a handle's, or the calling thread's for the batch form)
   orbg::DevBuf<Sim3Desc> d_desc;
   orbg::DevBuf<float> d_pts, d_hyp;
   orbg::DevBuf<uint32_t> d_thr;
@@ -387,23 +384,13 @@ struct Sim3Work {                // device and staging buffers of one launch (a 
   std::vector<unsigned long long> h_rmasks, h_masks;
   std::vector<float> h_hyp;
   long long pts_resident = -1;   // >= 0: the handle's problem is on the device already
-  int open(int dev) {
-    int rc = select_device(dev);
-    if (rc) return rc;
-    if (device != dev) { release(); device = dev; }
-    if (!stream) { ORBG_HIP(orbg::create_stream(&stream, "misc")); ext_stream = false; }
-    return ORBG_OK;
-  }
-  void release() {
-    if (device < 0) return;
-    (void)hipSetDevice(device);
-    if (stream) { (void)hipStreamSynchronize(stream); if (!ext_stream) orbg::release_stream(stream); stream = nullptr; }
+  void release_buffers() {
     d_desc.release(); d_pts.release(); d_hyp.release(); d_thr.release(); d_draws.release(); d_counts.release(); d_masks.release();
     d_rmasks.release(); d_tickets.release(); d_recs.release();
-    tickets_ready = 0; device = -1; pts_resident = -1;
+    tickets_ready = 0; pts_resident = -1;
   }
-  ~Sim3Work() { release(); }
 };
+using Sim3Work = orbg::WorkArea<Sim3Bufs>;
 
 struct Sim3Job {                 // one problem of a launch, host view
   const orbm_sim3_problem* p;
@@ -537,7 +524,7 @@ extern "C" int orbm_sim3_create(int device, orbm_sim3** out) {
   int rc = select_device(device);
   if (rc) return rc;
   orbm_sim3* h = new orbm_sim3;
-  if ((rc = h->w.open(device))) { delete h; return rc; }
+  if ((rc = h->w.open(device, "misc"))) { delete h; return rc; }
   *out = h;
   return ORBG_OK;
 }
@@ -669,7 +656,7 @@ extern "C" int orbm_sim3_solve_batch(int device, const orbm_sim3_problem* proble
   }
   if (jobs.empty()) return ORBG_OK;
   Sim3Work& w = batch_work();
-  if ((rc = w.open(device))) return rc;
+  if ((rc = w.open(device, "misc"))) return rc;
   if ((rc = launch(w, jobs, false))) return rc;
   for (int b = 0; b < B; b++) {
     if (job_of[b] < 0) continue;

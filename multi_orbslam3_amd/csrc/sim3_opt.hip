@@ -15,7 +15,7 @@
 //   Reductions     28 upper-triangle entries of H, 7 of b, the robustified chi2: a DPP tree inside each wavefront, then the four wave
 //                  totals in wave order.  Fixed order: two runs give the same bits, and so does a problem alone or inside a batch (a
 //                  workgroup sees nothing but its own problem).
-//   Solve, control (H + lambda I) x = b on lanes 0..6 of every wavefront (s3o_solve: the 7-lane form of PoseOptimization's 6-lane solve);
+//   Solve, control (H + lambda I) x = b on lanes 0..6 of every wavefront (lm_block.hpp, lane_ldlt_solve<7>: PoseOptimization runs the <6> form);
 //                  lambda init, computeScale, the 1 - (2 rho - 1)^3 update, _ni, ten trials and the _nBad >= 3 stop as in
 //                  G/core/optimization_algorithm_levenberg.cpp:61-194.  The LM state is kept identically in every thread (all of
 //                  them read the same block sums and run the same arithmetic): the control flow needs no broadcast.
@@ -48,8 +48,11 @@
 
 #include "common.hpp"
 #include "wave.hpp"
+#include "lm_block.hpp"
 #include "se3.hpp"
 
+using orbg::block_sum;
+using orbg::lane_ldlt_solve;
 using orbg::select_device;
 using orbg::wave_sum_f64;
 using orbg_se3::quat_from_R;
@@ -213,57 +216,6 @@ __device__ __forceinline__ void s3o_huber(bool robust, double e, double delta, d
   else { const double sq = sqrt(e); *rho0 = 2 * sq * delta - dsqr; *rho1 = delta / sq; }
 }
 
-__device__ __forceinline__ double s3o_readlane(double v, int lane) {   // lane must be wave-uniform
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
-
-// (H + lambda I) x = b by LDL^T without pivoting on lanes 0..N-1 of a wavefront, lane `li` holding row li: the N-lane form of
-// pose_opt.hip's po_solve6, same operations in the same order (E-5).  false: a pivot was not positive and finite, x is untouched.
-template <int N>
-__device__ inline bool s3o_solve(const double* Hrow, double b_li, int li, double lambda, double* x) {
-  double A[N], D[N];
-#pragma unroll
-  for (int j = 0; j < N; j++) A[j] = Hrow[j] + (j == li ? lambda : 0.0);
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < N; k++) {
-    const double d = s3o_readlane(A[k], k);
-    if (!(d > 0.0) || fabs(d) == INFINITY) ok = false;
-    D[k] = d;
-    const double Lik = A[k] / d;
-#pragma unroll
-    for (int j = k + 1; j < N; j++) { const double Ljk = s3o_readlane(Lik, j); A[j] -= (Lik * Ljk) * d; }
-    A[k] = Lik;
-  }
-  if (!ok) return false;
-  double y = b_li;
-#pragma unroll
-  for (int k = 0; k < N - 1; k++) { const double yk = s3o_readlane(y, k); if (li > k) y -= A[k] * yk; }
-  double Di = D[0];
-#pragma unroll
-  for (int k = 1; k < N; k++) Di = (li == k) ? D[k] : Di;
-  y /= Di;
-#pragma unroll
-  for (int i = N - 1; i >= 0; i--) {
-    double sv = s3o_readlane(y, i);
-#pragma unroll
-    for (int k = i + 1; k < N; k++) sv -= s3o_readlane(A[i], k) * x[k];
-    x[i] = sv;
-  }
-  return true;
-}
-
-// Block-wide sum of one double per thread: DPP tree per wavefront, the four wave totals in wave order (`slot` alternates between
-// consecutive calls so that one barrier is enough)
-__device__ __forceinline__ double s3o_block_sum(double v, double (*wsum)[4], int slot) {
-  const double w = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) wsum[slot][threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((wsum[slot][0] + wsum[slot][1]) + wsum[slot][2]) + wsum[slot][3];
-}
-
 template <bool LDS_IN>      // LDS_IN: n <= kS3oTile, `in` points into LDS (typed accesses; a pointer that may be either is a flat load)
 __device__ __forceinline__ void s3o_run(const S3oDesc& D, const float* in, double* __restrict__ chi, uint8_t* __restrict__ rem, S3oRec* __restrict__ rec,
                         double (*s_est)[16], double (*s_part)[kS3oNV], double* s_tot, double (*s_wsum)[4]) {
@@ -381,7 +333,7 @@ __device__ __forceinline__ void s3o_run(const S3oDesc& D, const float* in, doubl
       double rho = 0;
       int qmax = 0;
       for (;;) {
-        const bool ok2 = s3o_solve<7>(Hrow, b_li, li, lambda, x);
+        const bool ok2 = lane_ldlt_solve<7>(Hrow, b_li, li, lambda, x);
         if (fix) x[6] = 0;                                     // oplusImpl writes the zero into the solver's x
         double E[16];
         s3o_oplus(est, x, true, E);                            // update() runs also after a refused solve, with the x that is there
@@ -400,7 +352,7 @@ __device__ __forceinline__ void s3o_run(const S3oDesc& D, const float* in, doubl
           s3o_huber(robust, c1, delta, dsqr, &r0, &r1); tchi += r0;
           s3o_huber(robust, c2, delta, dsqr, &r0, &r1); tchi += r0;
         }
-        double tempChi = s3o_block_sum(tchi, s_wsum, sum_slot); sum_slot ^= 1;
+        double tempChi = block_sum(tchi, s_wsum, sum_slot); sum_slot ^= 1;
         if (!ok2) tempChi = 1.7976931348623157e308;
         rho = cur - tempChi;
         double scale = 0;
@@ -446,7 +398,7 @@ __device__ __forceinline__ void s3o_run(const S3oDesc& D, const float* in, doubl
         const bool bad = cs1[i] > th2 || cs2[i] > th2;
         if (bad) { rem[i] = 1; bl += 1; }
       }
-      nBad = (int)s3o_block_sum(bl, s_wsum, sum_slot); sum_slot ^= 1;
+      nBad = (int)block_sum(bl, s_wsum, sum_slot); sum_slot ^= 1;
       robust = false;                                          // setRobustKernel(0)
       if (D.n_corr - nBad < 10) { early = true; break; }       // :4271
     } else {
@@ -465,7 +417,7 @@ __device__ __forceinline__ void s3o_run(const S3oDesc& D, const float* in, doubl
         cs1[i] = c1; cs2[i] = c2;
         if (c1 > th2 || c2 > th2) rem[i] = 2; else cnt += 1;
       }
-      nIn = (int)s3o_block_sum(cnt, s_wsum, sum_slot); sum_slot ^= 1;
+      nIn = (int)block_sum(cnt, s_wsum, sum_slot); sum_slot ^= 1;
     }
   }
   if (tid == 0) {
@@ -496,29 +448,14 @@ __global__ __launch_bounds__(kS3oThreads) void sim3_opt_kernel(const S3oDesc* __
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct S3oWork {                 // the calling thread's buffers: one pinned block in, one pinned block out, the device copies
-  int device = -1;
-  hipStream_t stream = nullptr;
+struct S3oBufs {                 // the calling thread's buffers: one pinned block in, one pinned block out, the device copies
   orbg::PinnedBuf<uint8_t> h_in, h_out;
   orbg::DevBuf<uint8_t> d_in, d_out;
   orbg::DevBuf<double> d_chi;
   std::vector<double> h_chi;
-  int open(int dev) {
-    int rc = select_device(dev);
-    if (rc) return rc;
-    if (device != dev) { release(); device = dev; }
-    if (!stream) ORBG_HIP(orbg::create_stream(&stream, "misc"));
-    return ORBG_OK;
-  }
-  void release() {
-    if (device < 0) return;
-    (void)hipSetDevice(device);
-    if (stream) { (void)hipStreamSynchronize(stream); orbg::release_stream(stream); stream = nullptr; }
-    h_in.release(); h_out.release(); d_in.release(); d_out.release(); d_chi.release();
-    device = -1;
-  }
-  ~S3oWork() { release(); }
+  void release_buffers() { h_in.release(); h_out.release(); d_in.release(); d_out.release(); d_chi.release(); }
 };
+using S3oWork = orbg::WorkArea<S3oBufs>;
 S3oWork& s3o_work() { static thread_local S3oWork w; return w; }
 
 bool finite_all(const double* v, int n) {
@@ -567,7 +504,7 @@ extern "C" int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* 
   std::vector<S3oDesc> descs(J);
   if (J > 0) {
     w = &s3o_work();
-    if ((rc = w->open(device))) return rc;
+    if ((rc = w->open(device, "misc"))) return rc;
     const size_t desc_bytes = align16((size_t)J * sizeof(S3oDesc));
     const size_t in_bytes = desc_bytes + n_tot * 12 * sizeof(float);
     const size_t rec_bytes = align16((size_t)J * sizeof(S3oRec));

@@ -47,6 +47,13 @@ __device__ __forceinline__ unsigned wave_min(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// the FP64 value of one lane, returned wave-uniform (`lane` must be wave-uniform): one v_readlane per 32-bit half
+__device__ __forceinline__ double wave_readlane_f64(double v, int lane) {
+  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
+  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
+  return __hiloint2double(hi, lo);
+}
+
 // FP64 sum over the lanes in a fixed (tree) order, returned in every lane: each DPP step moves the two 32-bit halves
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #define ORBG_DPP64(ctrl, rmask)                                                                    \
@@ -64,8 +71,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   ORBG_DPP64B(0x111) ORBG_DPP64B(0x112) ORBG_DPP64B(0x114) ORBG_DPP64B(0x118) ORBG_DPP64(0x142, 0xA) ORBG_DPP64(0x143, 0xC)
 #undef ORBG_DPP64B
 #undef ORBG_DPP64
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
-  return __hiloint2double(hi, lo);
+  return wave_readlane_f64(v, 63);
 }
 
 }  // namespace orbg

@@ -86,6 +86,43 @@ def test_no_gpu_means_loud_failure_not_fallback():
     with pytest.raises(capi.OrbGpuError) as e:
         api.ComputeStereoFishEyeMatches(v)
     assert e.value.code == capi.ORBG_NO_DEVICE
+    # the other entry points without a handle (buffers of the calling thread): the same answer, and what the caller's outputs held
+    # before the call is still there afterwards
+    vp = lambda a: C.c_void_p(a.ctypes.data)        # noqa: E731
+    pr = synth.make_pose_opt_problem(n=40, outlier_frac=0.0, mono_frac=0.5, seed=140)
+    p, keep = views.pose_opt_problem(pr["Xw"], pr["u"], pr["v"], pr["ur"], pr["inv_sigma2"], pr["cam"], pr["Tcw"])
+    out = views.PoseOptOutput(40)
+    out.outlier[:] = 0xA5
+    out.c.n_inliers, out.c.n_bad = -7, -7
+    for i in range(16):
+        out.c.Tcw[i] = -7.0
+    for i in range(4):
+        out.c.iters[i], out.c.chi2[i] = -7, -7.0
+    assert lib.pose_optimize(C.byref(p), C.byref(out.c)) == capi.ORBG_NO_DEVICE
+    assert (out.outlier == 0xA5).all() and (out.c.n_inliers, out.c.n_bad) == (-7, -7)
+    assert list(out.c.Tcw) == [-7.0] * 16 and list(out.c.iters) == [-7] * 4 and list(out.c.chi2) == [-7.0] * 4
+    desc = np.arange(3 * 32, dtype=np.uint8).reshape(3, 32); start = np.array([0, 1, 3, 3], np.int32)
+    best = np.full(3, -7, np.int32)
+    assert lib.orbm_distinctive_descriptors(0, vp(desc), vp(start), 3, vp(best)) == capi.ORBG_NO_DEVICE
+    assert (best == -7).all()
+    qw = np.array([1, 5], np.int32); qv = np.array([0.5, 0.5]); cs = np.array([0, 1, 3], np.int32)
+    cw = np.array([5, 1, 7], np.int32); cv = np.array([1.0, 0.25, 0.75]); score = np.full(2, -7.0)
+    assert lib.orbv_score_l1(0, vp(qw), vp(qv), 2, vp(cs), vp(cw), vp(cv), 2, vp(score)) == capi.ORBG_NO_DEVICE
+    assert (score == -7.0).all()
+    import sim3_model as sm
+    sc = sm.make_scene(1, 20, True, 0.3)
+    sp = api.Sim3Problem(sc["X1"], sc["X2"], sc["e1"], sc["e2"], sc["K1"], sc["K2"], True)
+    H = api.sim3_ransac_iterations(20)
+    draws = api.sim3_draws(20, H, np.random.default_rng(0))
+    mask = np.full(20, 0xA5, np.uint8)
+    r = capi.Sim3Result()
+    r.struct_size = C.sizeof(capi.Sim3Result)
+    r.inliers = capi.ptr(mask)
+    r.no_more, r.converged, r.n_inliers, r.iterations_done, r.best_iteration, r.have_best, r.s = -7, -7, -7, -7, -7, -7, -7.0
+    P = (capi.Sim3Problem * 1)(sp.struct()); Q = (capi.Sim3Params * 1)(capi.Sim3Params(0.99, 6, 300)); D = (C.c_void_p * 1)(draws.ctypes.data)
+    assert lib.orbm_sim3_solve_batch(0, P, 1, Q, D, C.byref(r)) == capi.ORBG_NO_DEVICE
+    assert (mask == 0xA5).all() and r.s == -7.0
+    assert (r.no_more, r.converged, r.n_inliers, r.iterations_done, r.best_iteration, r.have_best) == (-7,) * 6
 
 
 def test_product_never_references_the_oracle():
