@@ -560,6 +560,105 @@ typedef struct orbm_sim3opt_result {
 int orbm_sim3_optimize(int device, const orbm_sim3opt_problem* p, orbm_sim3opt_result* r);
 int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* problems, int B, orbm_sim3opt_result* results);
 
+/* ---------------------------------------------------------------- CreateNewMapPoints (LocalMapping, once per keyframe)
+ * void LocalMapping::CreateNewMapPoints(), S/LocalMapping.cc:520-865: ORBmatcher::SearchForTriangulation (S/ORBmatcher.cc:961-1202)
+ * of the current keyframe against each of its 10 (stereo) / 20 (mono) covisible neighbours and the triangulation of every match
+ * (:616-863).  In this reference vbMatched2 is declared and never set (:1007,1063), so inside one SearchForTriangulation call every
+ * feature of KF1 is matched independently of every other one; the only serial coupling is ACROSS neighbours: a feature idx1 that got
+ * a point from neighbour i (AddMapPoint(pMP, idx1), :852) is skipped for neighbours j > i (:1029-1035).  All B neighbours therefore go
+ * in ONE kernel launch -- one record per (neighbour, idx1): the match and what the triangulation of it gives -- and the host replays
+ * the integer bookkeeping over the records in neighbour order.
+ *
+ * Scope: pinhole keyframes without a second camera (mpCamera2 == NULL, NLeft == -1, mpCamera a Pinhole).  There is no way to pass
+ * any other keyframe: for a rig or a non-pinhole camera the glue must fall back to the reference's body.
+ *
+ * orbm_newpoints_kf -- one keyframe side.  frame: the resident keyframe (mvKeysUn, mDescriptors, mvuRight, mvDepth; a KeyFrame is an
+ * orbm_frame, see the server-side matchers above).  featvec: mFeatVec.  has_mp[n]: GetMapPoint(i) != NULL (:1029, :1060 -- ANY point,
+ * bad ones included).  keys_xy: mvKeys[i].pt, n x 2, read by KeyFrame::UnprojectStereo only (S/KeyFrame.cc:947-963); NULL = mvKeys ==
+ * mvKeysUn (no distortion, S/Frame.cc:723-727).  Tcw = GetPose() rows 0-2, Twc = GetPoseInverse() rows 0-2, Ow = GetCameraCenter(),
+ * AS THE KEYFRAME HOLDS THEM: nothing is re-derived from another (UnprojectStereo reads the stored Twc).  fx .. invfy, mb, mbf: the
+ * KeyFrame members.  scale_factors / level_sigma2: mvScaleFactors / mvLevelSigma2, n_levels entries; scale_factor: mfScaleFactor.
+ * struct_size = sizeof(the struct) as the caller was compiled. */
+#define ORBG_NEWPOINTS_MAX_NEIGHBOURS 64
+typedef struct orbm_newpoints_kf {
+  uint32_t struct_size;
+  orbm_frame* frame;
+  orbm_featvec_view featvec;
+  const uint8_t* has_mp;
+  const float* keys_xy;
+  float Tcw[12], Twc[12], Ow[3];
+  float fx, fy, cx, cy, invfx, invfy, mb, mbf;
+  int32_t n_levels;
+  const float* scale_factors;
+  const float* level_sigma2;
+  float scale_factor;
+} orbm_newpoints_kf;
+
+/* only_stereo / coarse: bOnlyStereo / bCoarse of SearchForTriangulation; check_orientation: mbCheckOrientation of the matcher
+ * (CreateNewMapPoints constructs ORBmatcher(0.6f, false): 0 there); far_points / th_far_points: mbFarPoints / mThFarPoints (:837). */
+typedef struct orbm_newpoints_params {
+  uint32_t struct_size;
+  int32_t only_stereo, coarse, check_orientation, far_points;
+  float th_far_points;
+} orbm_newpoints_params;
+
+/* status of a record: accepted, or the `continue` of the reference that ended it.  Codes 1-4: no match (idx2 = -1). */
+enum {
+  ORBM_NP_ACCEPTED = 0,
+  ORBM_NP_HAS_POINT = 1,       /* pMP1 != NULL, S/ORBmatcher.cc:1032 */
+  ORBM_NP_NOT_STEREO = 2,      /* bOnlyStereo && !bStereo1, :1039-1041 */
+  ORBM_NP_NO_NODE = 3,         /* the feature's vocabulary node is not in KF2's feature vector (or the feature is in no node) */
+  ORBM_NP_NO_MATCH = 4,        /* bestIdx2 < 0, :1135 */
+  ORBM_NP_W_ZERO = 5,          /* x3D.at<float>(3) == 0, S/LocalMapping.cc:742 */
+  ORBM_NP_LOW_PARALLAX = 6,    /* "No stereo and very low parallax", :757-760 */
+  ORBM_NP_EMPTY = 7,           /* UnprojectStereo returned an empty matrix (mvDepth <= 0), :764 */
+  ORBM_NP_Z1 = 8,              /* :767 */
+  ORBM_NP_Z2 = 9,              /* :771 */
+  ORBM_NP_REPROJ1 = 10,        /* :786 / :798 */
+  ORBM_NP_REPROJ2 = 11,        /* :812 / :823 */
+  ORBM_NP_DIST_ZERO = 12,      /* :834 */
+  ORBM_NP_FAR = 13,            /* :837 */
+  ORBM_NP_SCALE = 14           /* :843 */
+};
+/* One record per (neighbour b, feature idx1) at [b * n1 + idx1], independent of every other record: what SearchForTriangulation
+ * picks for idx1 in neighbour b given has_mp as passed (idx2, -1: none; dist: its Hamming distance) and what :707-844 make of that
+ * pair.  x3D: the point when one was formed (status 0 or >= 8); w: x3D.at<float>(3) of the linear triangulation (0 for the
+ * UnprojectStereo branches); cos_parallax: cosParallaxRays. */
+typedef struct orbm_newpoints_record {
+  int32_t idx2, dist, status;
+  float x3D[3];
+  float w;
+  float cos_parallax;
+} orbm_newpoints_record;
+/* One created point: new MapPoint(x3D, ...), observed at idx1 in the current keyframe and at idx2 in neighbours[neighbour]. */
+typedef struct orbm_newpoint {
+  int32_t neighbour, idx1, idx2;
+  float x3D[3];
+} orbm_newpoint;
+
+/* The loop :564-864 over neighbours[0 .. B) (the keyframes that passed the baseline gates :573-590, in vpNeighKFs order): one launch,
+ * then the replay in neighbour order.  Per neighbour the replay drops every idx1 claimed by an earlier neighbour (before the rotation
+ * vote, as :1029-1035 stand before :1143), applies the vote when check_orientation, and walks the surviving matches in ascending idx1
+ * (vMatchedPairs, :1194-1199); an accepted record appends to `out` and claims idx1.
+ * out[cap] / *n_out: the created points in the reference's creation order.  The loop's CheckNewKeyFrames() exit (:566) stops
+ * between two neighbours: what the reference has created by then is the PREFIX of `out` with neighbour < i, so a caller that polls
+ * the flag per neighbour boundary consumes a prefix and discards the rest.  More than cap points: ORBG_CAP_EXCEEDED (*n_out = the
+ * count needed).  records (optional, B * n1): the raw records before the replay.  matches (optional, B * n1): vMatches12 of each
+ * neighbour after the replay (-1: none).
+ * All frames must be on one device (else ORBG_BAD_ARG); B > ORBG_NEWPOINTS_MAX_NEIGHBOURS: ORBG_CAP_EXCEEDED; B == 0 or no common
+ * node needs no launch.  Arguments are checked before the device is looked for; no device: ORBG_NO_DEVICE (no CPU fallback).  The
+ * work is enqueued on kf1's frame stream, behind what is pending on the neighbours' streams; buffers belong to the calling thread.
+ * Arithmetic: csrc/newpoints.hip lists every choice (N-1 ...); the 4 x 4 null vector of the linear triangulation is the smallest
+ * eigenvector of A^T A in float64 (cv::SVD::compute is float32 one-sided Jacobi in the reference): points agree with an OpenCV build
+ * to float32 rounding, not to the bit.  No atomics: two runs give the same bits. */
+int orbm_create_new_points(const orbm_newpoints_kf* kf1, const orbm_newpoints_kf* neighbours, int B, const orbm_newpoints_params* params,
+                           orbm_newpoint* out, int cap, int* n_out, orbm_newpoints_record* records, int32_t* matches);
+/* int ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse), S/ORBmatcher.cc:961-1202 (the F12
+ * argument is unused there): the matcher alone.  pairs[cap x 2] = vMatchedPairs (idx1 ascending), *n = its size (the return value);
+ * more than cap pairs: ORBG_CAP_EXCEEDED with *n = the count needed.  far_points / th_far_points are not read. */
+int orbm_search_for_triangulation(const orbm_newpoints_kf* kf1, const orbm_newpoints_kf* kf2, const orbm_newpoints_params* params,
+                                  int32_t* pairs, int cap, int* n);
+
 /* ---------------------------------------------------------------- bag of words */
 
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> flattened (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:60-130,

@@ -185,6 +185,30 @@ class Sim3OptResult(C.Structure):
                 ("trace_len", C.c_int32), ("edge_chi2", C.c_void_p)]
 
 
+class NewPointsKF(C.Structure):
+    """orbm_newpoints_kf: one keyframe side of CreateNewMapPoints / SearchForTriangulation."""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_void_p), ("featvec", FeatVecView), ("has_mp", C.c_void_p),
+                ("keys_xy", C.c_void_p), ("Tcw", C.c_float * 12), ("Twc", C.c_float * 12), ("Ow", C.c_float * 3),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("invfx", C.c_float),
+                ("invfy", C.c_float), ("mb", C.c_float), ("mbf", C.c_float), ("n_levels", C.c_int32),
+                ("scale_factors", C.c_void_p), ("level_sigma2", C.c_void_p), ("scale_factor", C.c_float)]
+
+
+class NewPointsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("only_stereo", C.c_int32), ("coarse", C.c_int32), ("check_orientation", C.c_int32),
+                ("far_points", C.c_int32), ("th_far_points", C.c_float)]
+
+
+NEWPOINTS_MAX_NEIGHBOURS = 64
+# status codes of orbm_newpoints_record (include/orbgpu.h)
+(NP_ACCEPTED, NP_HAS_POINT, NP_NOT_STEREO, NP_NO_NODE, NP_NO_MATCH, NP_W_ZERO, NP_LOW_PARALLAX, NP_EMPTY, NP_Z1, NP_Z2, NP_REPROJ1,
+ NP_REPROJ2, NP_DIST_ZERO, NP_FAR, NP_SCALE) = range(15)
+NEWPOINTS_RECORD_DTYPE = np.dtype([("idx2", "<i4"), ("dist", "<i4"), ("status", "<i4"), ("x3D", "<f4", (3,)), ("w", "<f4"),
+                                   ("cos_parallax", "<f4")])
+NEWPOINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("x3D", "<f4", (3,))])
+assert NEWPOINTS_RECORD_DTYPE.itemsize == 32 and NEWPOINT_DTYPE.itemsize == 24
+
+
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
                 ("iters", C.c_int32 * 4), ("chi2", C.c_double * 4)]
@@ -222,6 +246,7 @@ EXPORTED_SYMBOLS = [
     "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
     "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
     "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
+    "orbm_create_new_points", "orbm_search_for_triangulation",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
@@ -264,6 +289,8 @@ def load():
     lib.orbm_sim3_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
     lib.orbm_sim3_optimize.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     lib.orbm_sim3_optimize_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.orbm_create_new_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orbm_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

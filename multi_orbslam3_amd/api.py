@@ -1211,3 +1211,110 @@ def sim3opt_collect(Tcw1, Tcw2, mp_of_kp1, keys1, octave1, inv_level_sigma2_1, k
     w2 = np.where(inside, s2[np.asarray(octave2, np.int64)[j2]] if len(keys2) else s2[0], s2[0]).astype(f)
     q, t, s = g2oS12
     return Sim3OptProblem(P1, P2, obs1, obs2, w1, w2, K1, K2, bFixScale, th2, q, t, s, index_edge=i)
+
+
+class NewPointsKeyFrame:
+    """orbm_newpoints_kf: one keyframe side of LocalMapping::CreateNewMapPoints / ORBmatcher::SearchForTriangulation.
+
+    frame: the resident keyframe (a Frame: mvKeysUn, mDescriptors, mvuRight, mvDepth); featvec = (node_id, start, feat_idx) of mFeatVec;
+    has_mp[i] = GetMapPoint(i) != NULL; Tcw / Twc (3x4 or 4x4) and Ow as the keyframe holds them; cam = (fx, fy, cx, cy); mb, mbf;
+    scale_factors / level_sigma2 = mvScaleFactors / mvLevelSigma2; scale_factor = mfScaleFactor; keys_xy = mvKeys[i].pt when the
+    keyframe's image is distorted (None: mvKeys == mvKeysUn); invf = (invfx, invfy), default 1.0f / fx as S/Frame.cc:140-141."""
+
+    def __init__(self, frame, featvec, has_mp, Tcw, Twc, Ow, cam, mb, mbf, scale_factors, level_sigma2, scale_factor, keys_xy=None, invf=None):
+        self.frame = frame
+        self.fv, self._fv_keep = views.featvec_view(*featvec)
+        self.has_mp = np.ascontiguousarray(has_mp, np.uint8)
+        self.keys_xy = None if keys_xy is None else np.ascontiguousarray(np.asarray(keys_xy, np.float32).reshape(-1, 2))
+        self.Tcw = np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1)[:12])
+        self.Twc = np.ascontiguousarray(np.asarray(Twc, np.float32).reshape(-1)[:12])
+        self.Ow = np.ascontiguousarray(np.asarray(Ow, np.float32).reshape(3))
+        self.cam = tuple(np.float32(c) for c in cam)
+        self.invf = tuple(np.float32(v) for v in invf) if invf is not None else (np.float32(1.0) / self.cam[0], np.float32(1.0) / self.cam[1])
+        self.mb, self.mbf = np.float32(mb), np.float32(mbf)
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        self.level_sigma2 = np.ascontiguousarray(level_sigma2, np.float32)
+        self.scale_factor = np.float32(scale_factor)
+
+    def fill(self, k):
+        k.struct_size = C.sizeof(capi.NewPointsKF)
+        k.frame = self.frame.h
+        k.featvec = self.fv
+        k.has_mp = capi.ptr(self.has_mp)
+        k.keys_xy = capi.ptr(self.keys_xy)
+        for i in range(12):
+            k.Tcw[i], k.Twc[i] = float(self.Tcw[i]), float(self.Twc[i])
+        for i in range(3):
+            k.Ow[i] = float(self.Ow[i])
+        k.fx, k.fy, k.cx, k.cy = [float(c) for c in self.cam]
+        k.invfx, k.invfy = float(self.invf[0]), float(self.invf[1])
+        k.mb, k.mbf = float(self.mb), float(self.mbf)
+        k.n_levels = len(self.scale_factors)
+        k.scale_factors, k.level_sigma2 = capi.ptr(self.scale_factors), capi.ptr(self.level_sigma2)
+        k.scale_factor = float(self.scale_factor)
+        return k
+
+
+def _newpoints_params(only_stereo, coarse, check_orientation, far_points, th_far_points):
+    p = capi.NewPointsParams()
+    p.struct_size = C.sizeof(capi.NewPointsParams)
+    p.only_stereo, p.coarse, p.check_orientation, p.far_points = int(only_stereo), int(coarse), int(check_orientation), int(far_points)
+    p.th_far_points = float(th_far_points)
+    return p
+
+
+class NewMapPoints:
+    """Outcome of CreateNewMapPoints: out (NEWPOINT_DTYPE, the reference's creation order; the points created before the loop's
+    CheckNewKeyFrames() exit at neighbour i are the prefix with neighbour < i), records (B x n1, NEWPOINTS_RECORD_DTYPE, before the
+    replay) and matches (B x n1, vMatches12 per neighbour after the replay)."""
+
+    def __init__(self, out, records, matches):
+        self.out, self.records, self.matches = out, records, matches
+
+
+class NewPointsCall:
+    """The flattened arguments of one orbm_create_new_points call, kept for repeated calls on the same keyframes (a timing loop);
+    run() is the call itself."""
+
+    def __init__(self, kf1, neighbours, only_stereo=False, coarse=False, check_orientation=False, far_points=False, th_far_points=0.0,
+                 cap=None):
+        self.lib = capi.load()
+        self.keep = (kf1, list(neighbours))
+        self.B, self.n1 = len(neighbours), kf1.frame.n
+        self.K1 = kf1.fill(capi.NewPointsKF())
+        self.KN = (capi.NewPointsKF * max(self.B, 1))()
+        for b, kf in enumerate(neighbours):
+            kf.fill(self.KN[b])
+        self.p = _newpoints_params(only_stereo, coarse, check_orientation, far_points, th_far_points)
+        self.cap = self.B * self.n1 if cap is None else int(cap)
+        self.out = np.zeros(max(self.cap, 1), capi.NEWPOINT_DTYPE)
+        self.records = np.zeros((self.B, self.n1), capi.NEWPOINTS_RECORD_DTYPE)
+        self.matches = np.full((self.B, self.n1), -1, np.int32)
+        self.n = C.c_int(0)
+
+    def run(self):
+        capi.check(self.lib.orbm_create_new_points(C.byref(self.K1), C.byref(self.KN), self.B, C.byref(self.p), capi.ptr(self.out), self.cap,
+                                                   C.byref(self.n), capi.ptr(self.records) if self.records.size else None,
+                                                   capi.ptr(self.matches) if self.matches.size else None), "orbm_create_new_points")
+        return NewMapPoints(self.out[: self.n.value].copy(), self.records, self.matches)
+
+
+def CreateNewMapPoints(kf1, neighbours, only_stereo=False, coarse=False, check_orientation=False, far_points=False, th_far_points=0.0,
+                       cap=None):
+    """LocalMapping::CreateNewMapPoints, S/LocalMapping.cc:520-865, for the neighbours that passed the baseline gates: ONE launch for
+    all of them, then the serial bookkeeping across neighbours on the host."""
+    return NewPointsCall(kf1, neighbours, only_stereo, coarse, check_orientation, far_points, th_far_points, cap).run()
+
+
+def SearchForTriangulation(kf1, kf2, only_stereo=False, coarse=False, check_orientation=True):
+    """ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo, bCoarse), S/ORBmatcher.cc:961-1202: returns
+    vMatchedPairs as an (n, 2) array, idx1 ascending."""
+    lib = capi.load()
+    K1, K2 = kf1.fill(capi.NewPointsKF()), kf2.fill(capi.NewPointsKF())
+    p = _newpoints_params(only_stereo, coarse, check_orientation, False, 0.0)
+    cap = max(kf1.frame.n, 1)
+    pairs = np.zeros((cap, 2), np.int32)
+    n = C.c_int(0)
+    capi.check(lib.orbm_search_for_triangulation(C.byref(K1), C.byref(K2), C.byref(p), capi.ptr(pairs), cap, C.byref(n)),
+               "orbm_search_for_triangulation")
+    return pairs[: n.value].copy()

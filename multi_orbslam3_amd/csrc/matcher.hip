@@ -20,6 +20,8 @@
 #include "common.hpp"
 #include "wave.hpp"
 #include "stereo_finalize.hpp"
+#include "rot_hist.hpp"
+#include "null_vector4.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -35,7 +37,10 @@ namespace {
 
 constexpr int TH_HIGH = 100;      // S/ORBmatcher.cc:36
 constexpr int TH_LOW = 50;        // :37
-constexpr int HISTO_LENGTH = 30;  // :38
+using orbg::HISTO_LENGTH;         // :38 (rot_hist.hpp)
+using orbg::RotHist;
+using orbg::rot_bin;
+using orbg::null_vector4;
 struct PoseF {   // Tcw split as the reference does (S/Frame.cc:439-445)
   float R[9], t[3], Ow[3];
 };
@@ -983,40 +988,6 @@ void make_pose(const float* T, PoseF* P) {
   }
 }
 
-// Rotation histogram without per-call allocations: bin counts + one reusable (bin, index) list in push order.
-struct RotHist {
-  int cnt[HISTO_LENGTH];
-  std::vector<uint32_t>& e;
-  explicit RotHist(std::vector<uint32_t>& store) : e(store) { for (int& c : cnt) c = 0; e.clear(); }
-  void add(int bin, int idx) { cnt[bin]++; e.push_back(((uint32_t)bin << 24) | (uint32_t)idx); }
-  // ORBmatcher::ComputeThreeMaxima, S/ORBmatcher.cc:2312-2353, on the bin sizes; calls drop(idx) for every entry outside
-  template <typename DropFn>
-  void reject_outside_three_maxima(DropFn drop) const {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < HISTO_LENGTH; i++) {
-      const int s = cnt[i];
-      if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-      else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-      else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-    for (const uint32_t v : e) {
-      const int bin = (int)(v >> 24);
-      if (bin != ind1 && bin != ind2 && bin != ind3) drop((int)(v & 0xFFFFFFu));
-    }
-  }
-};
-
-inline int rot_bin(float a1, float a2) {   // factor = 1/HISTO_LENGTH
-  const float factor = 1.0f / HISTO_LENGTH;
-  float rot = a1 - a2;
-  if (rot < 0.0) rot += 360.0f;
-  int bin = (int)std::round(rot * factor);
-  if (bin == HISTO_LENGTH) bin = 0;
-  return bin;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -1245,6 +1216,24 @@ void orbm_internal_set_n(orbm_frame* f, int n) {
   f->stream = f->own_stream;
 }
 
+// What CreateNewMapPoints reads from a resident keyframe (newpoints.hip): the feature arrays, the host mirror of the keypoints
+// (angles for the rotation vote), the device and the stream its work is enqueued on.  uright is NULL for a frame without mvuRight.
+int orbm_internal_kf_features(orbm_frame* f, const orbx_keypoint** d_kps, const uint8_t** d_desc, const float** d_uright,
+                              const float** d_depth, const orbx_keypoint** h_kps, int* n, int* device, hipStream_t* stream) {
+  if (!f || (f->fp.n > 0 && (!f->kps_p || !f->desc_p))) return ORBG_BAD_ARG;
+  *d_kps = f->kps_p; *d_desc = f->desc_p; *d_uright = f->has_uright ? f->uright_p : nullptr; *d_depth = f->depth_p;
+  *h_kps = f->hk; *n = f->fp.n; *device = f->device; *stream = f->stream;
+  return ORBG_OK;
+}
+
+// Orders what is enqueued on `st` from now on behind the work already enqueued on the frame's stream (no host wait).
+int orbm_internal_order_after(orbm_frame* f, hipStream_t st) {
+  if (f->stream == st) return ORBG_OK;
+  ORBG_HIP(hipEventRecord(f->ev[1], f->stream));
+  ORBG_HIP(hipStreamWaitEvent(st, f->ev[1], 0));
+  return ORBG_OK;
+}
+
 // device-resident descriptors of the frame's features (for the vocabulary transform in bow.hip)
 int orbm_internal_features(orbm_frame* f, const uint8_t** d_desc, int* n, hipStream_t* stream) {
   if (!f || !f->desc_p) return ORBG_BAD_ARG;
@@ -1398,45 +1387,6 @@ __device__ __forceinline__ void kb8_unproject(const RigCamF& c, float u, float v
     scale = (float)tan((double)theta) / theta_d;
   }
   ray[0] = pwx * scale; ray[1] = pwy * scale; ray[2] = 1.f;
-}
-
-__device__ __forceinline__ void null_vector4(double (&S)[4][4], double (&v)[4]) {   // eigenvector of the smallest eigenvalue of a symmetric 4 x 4: cyclic Jacobi
-  double V[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) V[i][j] = i == j ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0, diag = 0;
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-      diag += S[p][p] * S[p][p];
-#pragma unroll
-      for (int q = p + 1; q < 4; q++) off += S[p][q] * S[p][q];
-    }
-    if (off <= 1e-28 * diag) break;                         // eigenvectors to ~1e-14: far below the float32 the result is rounded to
-#pragma unroll
-    for (int p = 0; p < 4; p++)
-#pragma unroll
-      for (int q = p + 1; q < 4; q++) {
-        if (S[p][q] == 0.0) continue;
-        const double tau = (S[q][q] - S[p][p]) / (2.0 * S[p][q]);
-        const double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-        const double cs = 1.0 / sqrt(1.0 + t * t), sn = t * cs;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const double a = S[k][p], b = S[k][q]; S[k][p] = cs * a - sn * b; S[k][q] = sn * a + cs * b; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const double a = S[p][k], b = S[q][k]; S[p][k] = cs * a - sn * b; S[q][k] = sn * a + cs * b; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const double a = V[k][p], b = V[k][q]; V[k][p] = cs * a - sn * b; V[k][q] = sn * a + cs * b; }
-      }
-  }
-  int m = 0;
-  double smallest = S[0][0];                                // (compile-time indices only: a dynamically indexed array lives in scratch memory)
-#pragma unroll
-  for (int i = 1; i < 4; i++) if (S[i][i] < smallest) { smallest = S[i][i]; m = i; }
-#pragma unroll
-  for (int k = 0; k < 4; k++) v[k] = m == 0 ? V[k][0] : m == 1 ? V[k][1] : m == 2 ? V[k][2] : V[k][3];
 }
 
 // KannalaBrandt8::TriangulateMatches, :335-403 (Triangulate :405-420)
