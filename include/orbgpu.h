@@ -659,6 +659,80 @@ int orbm_create_new_points(const orbm_newpoints_kf* kf1, const orbm_newpoints_kf
 int orbm_search_for_triangulation(const orbm_newpoints_kf* kf1, const orbm_newpoints_kf* kf2, const orbm_newpoints_params* params,
                                   int32_t* pairs, int cap, int* n);
 
+/* ---------------------------------------------------------------- Fuse / SearchInNeighbors (LocalMapping, once per keyframe)
+ * int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, float th, bool bRight = false), S/ORBmatcher.cc:1395-1605,
+ * as LocalMapping::SearchInNeighbors (S/LocalMapping.cc:868-976) calls it for every target keyframe and once for the current one, and
+ * the Sim3 overload int ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint), :1607-1742 (LoopClosing::SearchAndFuse).
+ *
+ * For one (keyframe k, point i) pair everything up to bestIdx / bestDist (:1451-1566 | :1642-1716) depends on the keyframe's features
+ * and pose and on the point's position, normal, distance range and descriptor.  All K x P pairs go in ONE kernel launch, one record
+ * per pair at [k * P + i]; the serial part (:1431-1448 and :1569-1590: isBad, IsInKeyFrame, GetMapPoint, Observations, Replace,
+ * AddObservation, AddMapPoint) stays with the caller, who replays it over the records in the reference's order
+ * (include/orbgpu_localmapping.hpp).  The only input that changes while SearchInNeighbors runs is a point's descriptor (Replace ends in
+ * ComputeDistinctiveDescriptors on the survivor): the candidates that passed the level and chi2 gates do not depend on it, so the
+ * record carries them -- `cand` holds the first ORBG_FUSE_CAND_CAP = 16 of them in vIndices order, n_cand the exact count -- and the
+ * caller rescores over that list (first strict minimum, from bestDist = 256 | INT_MAX); with n_cand > ORBG_FUSE_CAND_CAP it
+ * re-evaluates that single pair (K = 1, P = 1) with the new descriptor.
+ *
+ * Scope: pinhole keyframes, bRight = false.  A keyframe of a rig (NLeft != -1) cannot be passed: the glue falls back.
+ *
+ * orbm_fuse_kf -- one target keyframe.  frame: the resident keyframe (mvKeysUn, mDescriptors, mvuRight, the grid and the image bounds
+ * mnMinX .. mnMaxY).  LocalMapping form: Tcw = GetPose() rows 0-2 (GetRotation / GetTranslation, :1408-1409), Ow = GetCameraCenter(),
+ * AS THE KEYFRAME HOLDS THEM; Scw is not read.  Sim3 form: Scw (4 x 4, row-major) is decomposed as :1616-1620, the way
+ * orbm_search_by_projection_sim3 does it; Tcw / Ow are not read.  fx .. cy, mbf: the KeyFrame members.  scale_factors /
+ * inv_level_sigma2: mvScaleFactors / mvInvLevelSigma2, n_levels entries; log_scale_factor: mfLogScaleFactor.
+ * struct_size = sizeof(the struct) as the caller was compiled. */
+#define ORBG_FUSE_MAX_KEYFRAMES 512      /* 20 neighbours + 20 x 20 second neighbours + 20 temporal ones, S/LocalMapping.cc:871-917 */
+#define ORBG_FUSE_CAND_CAP 16
+typedef struct orbm_fuse_kf {
+  uint32_t struct_size;
+  orbm_frame* frame;
+  float Tcw[12], Ow[3];
+  float Scw[16];
+  float fx, fy, cx, cy, mbf;
+  int32_t n_levels;
+  const float* scale_factors;
+  const float* inv_level_sigma2;
+  float log_scale_factor;
+} orbm_fuse_kf;
+
+/* th: the search radius factor (3.0 in SearchInNeighbors, I/ORBmatcher.h:85); sim3_form: 0 = :1395 (chi2 gates 7.8 / 5.99, ur,
+ * bestDist from 256), 1 = :1607 (the level gate only, bestDist from INT_MAX). */
+typedef struct orbm_fuse_params {
+  uint32_t struct_size;
+  float th;
+  int32_t sim3_form;
+} orbm_fuse_params;
+
+/* status of a record: it reached the candidate loop with at least one candidate, or the `continue` of the reference that ended it. */
+enum {
+  ORBM_FUSE_CANDIDATES = 0,    /* best_idx / best_dist are set: the caller compares best_dist with TH_LOW (:1569) | 100 (:1722) */
+  ORBM_FUSE_NEG_DEPTH = 1,     /* p3Dc.at<float>(2) < 0.0f, :1455 | :1648 */
+  ORBM_FUSE_NOT_IN_IMAGE = 2,  /* !pKF->IsInImage(uv.x, uv.y), :1469 | :1659 */
+  ORBM_FUSE_DISTANCE = 3,      /* dist3D outside [minDistance, maxDistance], :1483 | :1669 */
+  ORBM_FUSE_NORMAL = 4,        /* PO.dot(Pn) < 0.5 * dist3D, :1492 | :1676 */
+  ORBM_FUSE_EMPTY_WINDOW = 5,  /* vIndices.empty(), :1505 | :1688 */
+  ORBM_FUSE_NO_CANDIDATE = 6,  /* nothing passed the level / chi2 gates: bestDist keeps its start value, :1569 | :1722 fails */
+  ORBM_FUSE_SKIPPED = 7        /* skip[k * P + i] (or bad[i] / skip[i] of the points view): no work was done */
+};
+/* level: nPredictedLevel (-1 when the pair ended before PredictScale); best_idx = -1 and best_dist = 256 | INT_MAX unless status is
+ * ORBM_FUSE_CANDIDATES; n_cand: how many features passed the gates (status 0 <=> n_cand > 0). */
+typedef struct orbm_fuse_record {
+  int32_t status, best_idx, best_dist, level, n_cand;
+} orbm_fuse_record;
+
+/* One launch for kfs[0 .. K) x the m points of `pts` (pos, normal, min_dist, max_dist -- raw, the 0.8 / 1.2 factors are applied as
+ * S/MapPoint.cc:617-627 -- and desc are read; bad[i] / skip[i], when given, skip point i for every keyframe; n_obs is not read).
+ * skip (K x m, or NULL): skip[k * m + i] marks a pair whose point is bad or already in keyframe k at entry (:1439-1448 | :1638); both
+ * conditions only ever become true during a call, so such a pair stays skipped in the replay.  records (K x m) and cand
+ * (K x m x ORBG_FUSE_CAND_CAP, unused slots 0xFFFF) are host arrays.
+ * K > ORBG_FUSE_MAX_KEYFRAMES, or a frame of ORBG_MAX_FRAME_FEATURES features or more (indices travel in 16 bits): ORBG_CAP_EXCEEDED.  All frames must be on one device (else ORBG_BAD_ARG).  Arguments are checked before
+ * the device is looked for; no device: ORBG_NO_DEVICE (no CPU fallback).  K == 0 or m == 0 needs no launch.  The work is enqueued on
+ * the calling thread's stream, behind what is pending on the keyframes' streams; buffers belong to the calling thread.  Arithmetic:
+ * csrc/fuse.hip lists every choice.  No atomics: two runs give the same bits. */
+int orbm_fuse(const orbm_fuse_kf* kfs, int K, const orbm_worldpoints_view* pts, const uint8_t* skip, const orbm_fuse_params* params,
+              orbm_fuse_record* records, uint16_t* cand);
+
 /* ---------------------------------------------------------------- bag of words */
 
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> flattened (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:60-130,

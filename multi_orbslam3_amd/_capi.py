@@ -209,6 +209,26 @@ NEWPOINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"
 assert NEWPOINTS_RECORD_DTYPE.itemsize == 32 and NEWPOINT_DTYPE.itemsize == 24
 
 
+class FuseKF(C.Structure):
+    """orbm_fuse_kf: one target keyframe of ORBmatcher::Fuse."""
+    _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_void_p), ("Tcw", C.c_float * 12), ("Ow", C.c_float * 3),
+                ("Scw", C.c_float * 16), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("mbf", C.c_float), ("n_levels", C.c_int32), ("scale_factors", C.c_void_p), ("inv_level_sigma2", C.c_void_p),
+                ("log_scale_factor", C.c_float)]
+
+
+class FuseParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("th", C.c_float), ("sim3_form", C.c_int32)]
+
+
+FUSE_MAX_KEYFRAMES, FUSE_CAND_CAP = 512, 16
+# status codes of orbm_fuse_record (include/orbgpu.h)
+(FUSE_CANDIDATES, FUSE_NEG_DEPTH, FUSE_NOT_IN_IMAGE, FUSE_DISTANCE, FUSE_NORMAL, FUSE_EMPTY_WINDOW, FUSE_NO_CANDIDATE,
+ FUSE_SKIPPED) = range(8)
+FUSE_RECORD_DTYPE = np.dtype([("status", "<i4"), ("best_idx", "<i4"), ("best_dist", "<i4"), ("level", "<i4"), ("n_cand", "<i4")])
+assert FUSE_RECORD_DTYPE.itemsize == 20
+
+
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
                 ("iters", C.c_int32 * 4), ("chi2", C.c_double * 4)]
@@ -246,7 +266,7 @@ EXPORTED_SYMBOLS = [
     "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
     "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
     "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
-    "orbm_create_new_points", "orbm_search_for_triangulation",
+    "orbm_create_new_points", "orbm_search_for_triangulation", "orbm_fuse",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
@@ -291,6 +311,7 @@ def load():
     lib.orbm_sim3_optimize_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     lib.orbm_create_new_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orbm_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.orbm_fuse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

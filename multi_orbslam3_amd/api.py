@@ -1318,3 +1318,61 @@ def SearchForTriangulation(kf1, kf2, only_stereo=False, coarse=False, check_orie
     capi.check(lib.orbm_search_for_triangulation(C.byref(K1), C.byref(K2), C.byref(p), capi.ptr(pairs), cap, C.byref(n)),
                "orbm_search_for_triangulation")
     return pairs[: n.value].copy()
+
+
+class FuseKeyFrame:
+    """orbm_fuse_kf: one target keyframe of ORBmatcher::Fuse.
+
+    frame: the resident keyframe (a Frame: mvKeysUn, mDescriptors, mvuRight, the grid, the image bounds); cam = (fx, fy, cx, cy); mbf;
+    scale_factors / inv_level_sigma2 = mvScaleFactors / mvInvLevelSigma2; log_scale_factor = mfLogScaleFactor.  LocalMapping form: Tcw
+    (3x4 or 4x4) and Ow as the keyframe holds them.  Sim3 form: Scw (4x4)."""
+
+    def __init__(self, frame, cam, mbf, scale_factors, inv_level_sigma2, log_scale_factor, Tcw=None, Ow=None, Scw=None):
+        self.frame = frame
+        self.Tcw = np.zeros(12, np.float32) if Tcw is None else np.ascontiguousarray(np.asarray(Tcw, np.float32).reshape(-1)[:12])
+        self.Ow = np.zeros(3, np.float32) if Ow is None else np.ascontiguousarray(np.asarray(Ow, np.float32).reshape(3))
+        self.Scw = np.zeros(16, np.float32) if Scw is None else np.ascontiguousarray(np.asarray(Scw, np.float32).reshape(16))
+        self.cam = tuple(np.float32(c) for c in cam)
+        self.mbf = np.float32(mbf)
+        self.scale_factors = np.ascontiguousarray(scale_factors, np.float32)
+        self.inv_level_sigma2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        self.log_scale_factor = np.float32(log_scale_factor)
+
+    def fill(self, k):
+        k.struct_size = C.sizeof(capi.FuseKF)
+        k.frame = self.frame.h
+        for i in range(12):
+            k.Tcw[i] = float(self.Tcw[i])
+        for i in range(3):
+            k.Ow[i] = float(self.Ow[i])
+        for i in range(16):
+            k.Scw[i] = float(self.Scw[i])
+        k.fx, k.fy, k.cx, k.cy = [float(c) for c in self.cam]
+        k.mbf = float(self.mbf)
+        k.n_levels = len(self.scale_factors)
+        k.scale_factors, k.inv_level_sigma2 = capi.ptr(self.scale_factors), capi.ptr(self.inv_level_sigma2)
+        k.log_scale_factor = float(self.log_scale_factor)
+        return k
+
+
+def Fuse(kfs, points, th=3.0, sim3_form=False, skip=None):
+    """ORBmatcher::Fuse up to bestIdx / bestDist (S/ORBmatcher.cc:1451-1566, or :1642-1716 with sim3_form) for every (keyframe, point)
+    pair in ONE launch.  kfs: FuseKeyFrame list; points: (orbm_worldpoints_view, keepalive) of views.worldpoints_view; skip: K x P bytes or
+    None.  Returns (records K x P of FUSE_RECORD_DTYPE, candidate lists K x P x FUSE_CAND_CAP uint16, 0xFFFF = unused); the serial
+    part of Fuse is the caller's replay."""
+    lib = capi.load()
+    view = points[0] if isinstance(points, tuple) else points
+    K, P = len(kfs), int(view.m)
+    arr = (capi.FuseKF * max(K, 1))()
+    for k, kf in enumerate(kfs):
+        kf.fill(arr[k])
+    p = capi.FuseParams()
+    p.struct_size, p.th, p.sim3_form = C.sizeof(capi.FuseParams), float(th), int(bool(sim3_form))
+    rec = np.zeros((K, P), capi.FUSE_RECORD_DTYPE)
+    cand = np.full((K, P, capi.FUSE_CAND_CAP), 0xFFFF, np.uint16)
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, np.uint8)
+        assert skip.shape == (K, P)
+    capi.check(lib.orbm_fuse(C.byref(arr), K, C.byref(view), capi.ptr(skip) if skip is not None and skip.size else None, C.byref(p),
+                             capi.ptr(rec) if rec.size else None, capi.ptr(cand) if cand.size else None), "orbm_fuse")
+    return rec, cand

@@ -1226,6 +1226,14 @@ int orbm_internal_kf_features(orbm_frame* f, const orbx_keypoint** d_kps, const 
   return ORBG_OK;
 }
 
+// What Fuse reads on top of that (fuse.hip): the keyframe's grid (CSR, cell = ix * 48 + iy) and the frame parameters (image bounds,
+// mfGridElementWidthInv / HeightInv).
+int orbm_internal_kf_grid(orbm_frame* f, const int** d_cell_start, const int** d_cell_items, FrameParams* fp) {
+  if (!f || !f->d_cell_start.p || !f->d_cell_items.p) return ORBG_BAD_ARG;
+  *d_cell_start = f->d_cell_start.p; *d_cell_items = f->d_cell_items.p; *fp = f->fp;
+  return ORBG_OK;
+}
+
 // Orders what is enqueued on `st` from now on behind the work already enqueued on the frame's stream (no host wait).
 int orbm_internal_order_after(orbm_frame* f, hipStream_t st) {
   if (f->stream == st) return ORBG_OK;
