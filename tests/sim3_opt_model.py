@@ -667,11 +667,16 @@ _FAMILY = {}
 def measure_family():
     """Every scene of family() in float64 and in long double.  -> dict(scenes = [dict(entry, problem, f64, ld, diff, ill, band, cmp)],
     band_max = {band: largest well-conditioned |q t s (f64) - q t s (ld)| over the scenes with a non-zero return})."""
-    if _FAMILY:
-        return _FAMILY
+    if not _FAMILY:
+        _FAMILY.update(measure_entries(family()))
+    return _FAMILY
+
+
+def measure_entries(entries):
+    """measure_family's measurement on any list of family() entries (the boundary family of tests/path_boundary_cases.py)."""
     scenes = []
     band_max = {}
-    for e in family():
+    for e in entries:
         p = family_problem(e)
         a, b = optimize_sim3(p, np.float64), optimize_sim3(p, L)
         d = est_diff(a, b)
@@ -680,5 +685,4 @@ def measure_family():
         scenes.append(rec)
         if b["n_in"] > 0 and not rec["ill"]:
             band_max[rec["band"]] = max(band_max.get(rec["band"], 0.0), d)
-    _FAMILY.update(scenes=scenes, band_max=band_max)
-    return _FAMILY
+    return dict(scenes=scenes, band_max=band_max)

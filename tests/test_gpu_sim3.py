@@ -65,13 +65,12 @@ HYP_CASES = [(n, fs, of, seed, 300) for n, fs, of, seed in sm.family_scenes()] +
              (513, False, 0.3, 46, 300), (2000, True, 0.3, 47, 300), (2000, False, 0.5, 48, 65)]
 
 
-def test_every_hypothesis_against_the_float32_model():
-    """Test 6 of the issue.  Masks: equal, leaving out the decisions whose float64-model error lies within a relative 1e-3 of its
-    threshold (at most 0.1 % of all decisions).  T12: hypotheses with a float64 eigen gap >= 0.01 (at least 95 % of them), tolerance 4 x
-    the model's own float32-vs-float64 difference in the same band.  NaN hypotheses are NaN in both and have no inliers."""
+def _compare_hypotheses(cases):
+    """Every hypothesis of every case (n, fix_scale, outlier fraction, seed, H) against the float32 model: the assertions of test 6.
+    -> (decisions, decisions left out, hypotheses, those with an eigen gap < 0.01, NaN hypotheses)."""
     bands = _bands()
     decisions = left_out = hyps = low_gap = nan_hyps = 0
-    for n, fs, of, seed, H in HYP_CASES:
+    for n, fs, of, seed, H in cases:
         sc = sm.make_scene(seed, n, fs, of)
         if n == 64:
             sc = _degenerate(sc)
@@ -103,6 +102,14 @@ def test_every_hypothesis_against_the_float32_model():
             if sel.any():
                 print("n=%d H=%d gap [%g, %g): %d hypotheses, max |T12 - model| = %.3g (tolerance %.3g)" % (n, H, lo, hi, sel.sum(), d[sel].max(), 4 * bands[(lo, hi)]))
                 assert d[sel].max() <= 4 * bands[(lo, hi)], (n, fs, of, H, lo, float(d[sel].max()))
+    return decisions, left_out, hyps, low_gap, nan_hyps
+
+
+def test_every_hypothesis_against_the_float32_model():
+    """Test 6 of the issue.  Masks: equal, leaving out the decisions whose float64-model error lies within a relative 1e-3 of its
+    threshold (at most 0.1 % of all decisions).  T12: hypotheses with a float64 eigen gap >= 0.01 (at least 95 % of them), tolerance 4 x
+    the model's own float32-vs-float64 difference in the same band.  NaN hypotheses are NaN in both and have no inliers."""
+    decisions, left_out, hyps, low_gap, nan_hyps = _compare_hypotheses(HYP_CASES)
     print("decisions %d, left out %d; hypotheses %d, gap < 0.01: %d, NaN: %d" % (decisions, left_out, hyps, low_gap, nan_hyps))
     assert left_out <= 1e-3 * decisions
     assert low_gap <= 0.05 * hyps

@@ -35,20 +35,9 @@ def _same_bits(a, b):
 
 # ------------------------------------------------------------------ 6. against the float64 model
 
-@needs_long_double
-def test_device_against_the_float64_model_on_the_family(capsys):
-    """Same scene family as the CPU yardstick.  `removed` and n_in equal outside the band of decisions whose long double chi2 lies
-    within 1e-3 of th2 (at most 0.1 % of the decisions left out); returned_early equal and the input estimate returned untouched;
-    round-1 trace equal wherever the two model precisions agree on it; q / t / s of well-conditioned scenes with identical inlier sets
-    within 4 x the float64-vs-long-double difference of the scene's (n band, scale mode): two float64 evaluations in different
-    operation orders can each sit that far from the exact value on opposite sides (x 2), and a maximum over a few dozen scenes
-    underestimates the population's (x 2).  The measured maxima are printed.
-    The band's n is the number of pairs the second round optimises (sim3_opt_model.band_of).  A first version of this test banded
-    by the number of pairs handed in; one scene then missed its bound (200 pairs, free scale, 50 % wrong matches, 10 survivors:
-    1.59e-7 against 4 x 3.1e-8, the figure of scenes with 40 - 240 survivors).  The same scene among those with fewer than 100
-    survivors, where its conditioning puts it: 1.59e-7 against 4 x 6.87e-8; the largest device / model ratio over the six bands
-    fell from 5.1 to 2.4."""
-    fam = om.measure_family()
+def _judge_family(fam):
+    """A measured family (sim3_opt_model.measure_family / measure_entries) on the device, judged scene by scene.
+    -> (device results, decisions, decisions left out, {band: largest device-vs-model difference}, report lines, failures)."""
     probs = [_api_problem(s["problem"]) for s in fam["scenes"]]
     got = api.OptimizeSim3.batch(probs, edge_chi2=True)
     decisions = left_out = 0
@@ -81,6 +70,24 @@ def test_device_against_the_float64_model_on_the_family(capsys):
             worst[s["band"]] = max(worst.get(s["band"], 0.0), d)
             if not d <= 4 * fam["band_max"][s["band"]]:
                 failures.append(("estimate", s["entry"], d, 4 * fam["band_max"][s["band"]]))
+    return got, decisions, left_out, worst, lines, failures
+
+
+@needs_long_double
+def test_device_against_the_float64_model_on_the_family(capsys):
+    """Same scene family as the CPU yardstick.  `removed` and n_in equal outside the band of decisions whose long double chi2 lies
+    within 1e-3 of th2 (at most 0.1 % of the decisions left out); returned_early equal and the input estimate returned untouched;
+    round-1 trace equal wherever the two model precisions agree on it; q / t / s of well-conditioned scenes with identical inlier sets
+    within 4 x the float64-vs-long-double difference of the scene's (n band, scale mode): two float64 evaluations in different
+    operation orders can each sit that far from the exact value on opposite sides (x 2), and a maximum over a few dozen scenes
+    underestimates the population's (x 2).  The measured maxima are printed.
+    The band's n is the number of pairs the second round optimises (sim3_opt_model.band_of).  A first version of this test banded
+    by the number of pairs handed in; one scene then missed its bound (200 pairs, free scale, 50 % wrong matches, 10 survivors:
+    1.59e-7 against 4 x 3.1e-8, the figure of scenes with 40 - 240 survivors).  The same scene among those with fewer than 100
+    survivors, where its conditioning puts it: 1.59e-7 against 4 x 6.87e-8; the largest device / model ratio over the six bands
+    fell from 5.1 to 2.4."""
+    fam = om.measure_family()
+    got, decisions, left_out, worst, lines, failures = _judge_family(fam)
     with capsys.disabled():
         print("\nOptimizeSim3, device vs float64 model: %d scenes, %d decisions, %d left out" % (len(got), decisions, left_out))
         for ln in lines:
