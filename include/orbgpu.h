@@ -560,6 +560,79 @@ typedef struct orbm_sim3opt_result {
 int orbm_sim3_optimize(int device, const orbm_sim3opt_problem* p, orbm_sim3opt_result* r);
 int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* problems, int B, orbm_sim3opt_result* results);
 
+/* ---------------------------------------------------------------- TwoViewReconstruction (monocular initialisation)
+ * bool TwoViewReconstruction::Reconstruct(vKeys1, vKeys2, vMatches12, R21, t21, vP3D, vbTriangulated), S/TwoViewReconstruction.cc:39-127,
+ * what Tracking::MonocularInitialization runs through Pinhole::ReconstructWithTwoViews (S/CameraModels/Pinhole.cpp:105): the
+ * homography RANSAC and the fundamental-matrix RANSAC (`iterations` hypotheses each, every one scored against every match), the
+ * choice between the two models, and ReconstructH / ReconstructF with CheckRT over all 8 / 4 motion hypotheses.  Two kernel launches
+ * on one stream, no host round trip between them; the serial rules ("first iteration with the strictly largest score") are replayed
+ * on the device over the scores in iteration order, so the outcome is the one the serial loops give for the same draws.
+ *
+ * keys1 / keys2: the mvKeysUn points of the two frames (n1 x 2 / n2 x 2 float); Normalize (:753-799) runs over ALL of them.
+ * matches12: n1 entries, index into keys2 or -1 (any negative value) for "no match"; N = the number of matched keypoints.
+ * fx .. cy: mK.  sigma / iterations: the constructor's arguments (1.0 / 200).
+ * struct_size = sizeof(the struct) as the caller was compiled. */
+#define ORBI_TWO_VIEW_MAX_MATCHES 8192
+#define ORBI_TWO_VIEW_MAX_ITERATIONS 4096
+typedef struct orbi_two_view_problem {
+  uint32_t struct_size;
+  int32_t  n1, n2;
+  const float* keys1;              /* n1 x 2 */
+  const float* keys2;              /* n2 x 2 */
+  const int32_t* matches12;        /* n1 */
+  float fx, fy, cx, cy;
+  float sigma;
+  int32_t iterations;
+} orbi_two_view_problem;
+
+/* model: 0 = none (SH + SF == 0, :111), 1 = ReconstructH (RH > 0.50), 2 = ReconstructF.  SH / SF: the best scores; best_iteration_H /
+ * _F: the 0-based iteration that holds them, -1 when no hypothesis scored above 0 (H21 / F21 are zero then).  R21 / t21 / vP3D /
+ * vbTriangulated are written when success (zero otherwise; the reference leaves its outputs untouched on failure).  vP3D (n1 x 3)
+ * and vbTriangulated (n1 bytes) are the caller's buffers, indexed by the keypoint index of frame 1 (NULL: not wanted).
+ * n_motions: 8 (H), 4 (F), or 0 when no CheckRT ran (model 0, or ReconstructH's d1 / d2 < 1.00001 || d2 / d3 < 1.00001 return, for
+ * which h_degenerate is set); motion_nGood / motion_parallax / motion_R / motion_t: per motion hypothesis tried, in the reference's
+ * order; best_motion: the one returned, or -1.  n_inliers: N of ReconstructH / F (the inlier count of the chosen model's best mask).
+ * T1 / T2: Normalize's matrices of frame 1 / 2.
+ * hyp_*: optional per-hypothesis outputs for checkers (NULL: not read back), H hypotheses then F hypotheses: hyp_scores
+ * (2 x iterations), hyp_models (2 x iterations x 9: H21i / F21i), hyp_masks (2 x iterations x ceil(N / 64) words; bit i & 63 of
+ * word i >> 6 is match i in matches12 order) and hyp_sets (iterations x 8 resolved match indices). */
+typedef struct orbi_two_view_result {
+  uint32_t struct_size;
+  int32_t  success;
+  int32_t  model;
+  int32_t  best_iteration_H, best_iteration_F;
+  int32_t  n_matches;
+  int32_t  n_inliers;
+  int32_t  n_motions;
+  int32_t  best_motion;
+  int32_t  h_degenerate;
+  float    SH, SF;
+  float    H21[9], F21[9];
+  float    R21[9], t21[3];
+  float    T1[9], T2[9];
+  int32_t  motion_nGood[8];
+  float    motion_parallax[8];
+  float    motion_R[72];
+  float    motion_t[24];
+  float*   vP3D;
+  uint8_t* vbTriangulated;
+  float*   hyp_scores;
+  float*   hyp_models;
+  uint64_t* hyp_masks;
+  int32_t* hyp_sets;
+} orbi_two_view_result;
+
+/* The minimal sets of :76-96: draws = the raw DUtils::Random::RandomInt(0, size - 1) results, eight per iteration (iteration k draws
+ * from lists of n, n - 1, ..., n - 7 entries; anything else is ORBG_BAD_ARG); idx = the eight match indices the swap-with-back
+ * removal on vAllIndices gives.  Host only, runs without a device; the kernel uses the same closed form. */
+int orbi_two_view_resolve_draws(int n, const int32_t* draws, int iterations, int32_t* idx);
+/* Reconstruct().  draws: 8 * iterations raw draws for N matches, as above.  Fewer than 8 matches cannot draw a set (the reference
+ * would index an empty list): ORBG_BAD_ARG, as are a struct_size too small, NULL arrays, a match index outside keys2, iterations < 1
+ * and a draw out of range.  N > ORBI_TWO_VIEW_MAX_MATCHES or iterations > ORBI_TWO_VIEW_MAX_ITERATIONS: ORBG_CAP_EXCEEDED.  The
+ * arguments are checked before the device is looked for; no device: ORBG_NO_DEVICE (there is no CPU fallback).  The work runs on
+ * the library's M stream of `device` with buffers that belong to the calling thread. */
+int orbi_two_view_reconstruct(int device, const orbi_two_view_problem* p, const int32_t* draws, orbi_two_view_result* r);
+
 /* ---------------------------------------------------------------- CreateNewMapPoints (LocalMapping, once per keyframe)
  * void LocalMapping::CreateNewMapPoints(), S/LocalMapping.cc:520-865: ORBmatcher::SearchForTriangulation (S/ORBmatcher.cc:961-1202)
  * of the current keyframe against each of its 10 (stereo) / 20 (mono) covisible neighbours and the triangulation of every match

@@ -16,6 +16,7 @@
 //   int  PoseOptimization(Frame*)                                                             I/Optimizer.h:47,   S/Optimizer.cc:964-1278
 //   class Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bFixScale, vpKeyFrameMatchedMP)  I/Sim3Solver.h:36-131, S/Sim3Solver.cc (orbgpu::Sim3Solver, at the end)
 //   int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)   S/Optimizer.cc:4031-4310 (orbgpu::OptimizeSim3, at the end)
+//   class TwoViewReconstruction(cv::Mat& K, float sigma, int iterations), bool Reconstruct(...)   I/TwoViewReconstruction.h, S/TwoViewReconstruction.cc (orbgpu::TwoViewReconstruction, at the end)
 //
 // Matrix access goes through mat_f32 / mat_u8 / make_mat (overloads for cv::Mat below, for the mock in the test header).
 #ifndef ORBGPU_DROPIN_HPP_
@@ -1537,6 +1538,83 @@ inline int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*
   g2oS12 = Sim3T(QuatT(r.q[3], r.q[0], r.q[1], r.q[2]), VecT(r.t[0], r.t[1], r.t[2]), r.s);   // :4306
   return r.n_in;
 }
+
+// ------------------------------------------------------------------------------------------------ TwoViewReconstruction
+// DUtils::Random::RandomInt(min, max) after DUtils::Random::SeedRandOnce(0) (S/TwoViewReconstruction.cc:79,88;
+// Thirdparty/DBoW2/DUtils/Random.cpp:38-50): the first draw of the PROCESS seeds rand() with 0, whoever takes it.  The reference keeps
+// that flag in DUtils::Random; a tree that links DUtils passes a functor that calls DUtils::Random::SeedRandOnce(0) and
+// DUtils::Random::RandomInt instead, so that both sides share one flag ("TwoViewReconstruction").
+struct TwoViewRandomInt {
+  int operator()(int min, int max) const {
+    static const bool seeded = (srand(0), true);
+    (void)seeded;
+    const int d = max - min + 1;
+    return int(((double)rand() / ((double)RAND_MAX + 1.0)) * d) + min;
+  }
+};
+
+// ORB_SLAM3::TwoViewReconstruction (I/TwoViewReconstruction.h) with the reference's constructor and Reconstruct signature; MatT is
+// cv::Mat, KeyPointT cv::KeyPoint, Point3fT cv::Point3f there.  All 8 * iterations draws are taken before the launch, as the
+// reference takes them before its two threads start (:81-96).  R21 / t21 / vP3D / vbTriangulated are written only when the call
+// returns true, as in the reference.  Fewer than eight matches: the reference indexes an empty list (:88-89); here the call
+// returns false without a launch.
+template <class MatT, class KeyPointT, class Point3fT, class RandomIntT = TwoViewRandomInt>
+class TwoViewReconstruction {
+ public:
+  TwoViewReconstruction(MatT& K, float sigma = 1.0, int iterations = 200, int device = 0, RandomIntT random_int = RandomIntT())
+      : mSigma(sigma), mMaxIterations(iterations), mDevice(device), mRandomInt(random_int) {
+    const float* k = dropin::mat_f32(K);              // mK = K.clone(): fx, fy, cx, cy are all CheckRT and K^T F K read
+    mK[0] = k[0]; mK[1] = k[4]; mK[2] = k[2]; mK[3] = k[5];
+  }
+
+  bool Reconstruct(const std::vector<KeyPointT>& vKeys1, const std::vector<KeyPointT>& vKeys2, const std::vector<int>& vMatches12,
+                   MatT& R21, MatT& t21, std::vector<Point3fT>& vP3D, std::vector<bool>& vbTriangulated) {
+    const int n1 = (int)vKeys1.size(), n2 = (int)vKeys2.size();
+    std::vector<float> k1(2 * (size_t)std::max(n1, 1)), k2(2 * (size_t)std::max(n2, 1));
+    for (int i = 0; i < n1; i++) { k1[2 * i] = vKeys1[i].pt.x; k1[2 * i + 1] = vKeys1[i].pt.y; }
+    for (int i = 0; i < n2; i++) { k2[2 * i] = vKeys2[i].pt.x; k2[2 * i + 1] = vKeys2[i].pt.y; }
+    std::vector<int32_t> m12(std::max(n1, 1), -1);    // (:53-62 runs over vMatches12.size() entries)
+    int N = 0;
+    for (int i = 0; i < n1 && i < (int)vMatches12.size(); i++) { m12[i] = vMatches12[i] >= 0 ? vMatches12[i] : -1; N += vMatches12[i] >= 0; }
+    mLast = orbi_two_view_result{};
+    if (N < 8 || mMaxIterations < 1) return false;
+    mDraws.clear();
+    mDraws.reserve(8 * (size_t)mMaxIterations);
+    for (int it = 0; it < mMaxIterations; it++)
+      for (int j = 0; j < 8; j++) mDraws.push_back(mRandomInt(0, N - j - 1));
+    orbi_two_view_problem p;
+    std::memset(&p, 0, sizeof(p));
+    p.struct_size = sizeof(p); p.n1 = n1; p.n2 = n2; p.keys1 = k1.data(); p.keys2 = k2.data(); p.matches12 = m12.data();
+    p.fx = mK[0]; p.fy = mK[1]; p.cx = mK[2]; p.cy = mK[3]; p.sigma = mSigma; p.iterations = mMaxIterations;
+    std::vector<float> P3D(3 * (size_t)std::max(n1, 1));
+    std::vector<uint8_t> tri(std::max(n1, 1));
+    orbi_two_view_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.struct_size = sizeof(r); r.vP3D = P3D.data(); r.vbTriangulated = tri.data();
+    check(orbi_two_view_reconstruct(mDevice, &p, mDraws.data(), &r), "orbi_two_view_reconstruct");
+    mLast = r; mLast.vP3D = nullptr; mLast.vbTriangulated = nullptr;
+    if (!r.success) return false;
+    dropin::make_mat(R21, 3, 3, r.R21);
+    dropin::make_mat(t21, 3, 1, r.t21);
+    vP3D.resize(n1);
+    vbTriangulated.assign(n1, false);
+    for (int i = 0; i < n1; i++) {
+      Point3fT q; q.x = P3D[3 * i]; q.y = P3D[3 * i + 1]; q.z = P3D[3 * i + 2];
+      vP3D[i] = q; vbTriangulated[i] = tri[i] != 0;
+    }
+    return true;
+  }
+
+  const orbi_two_view_result& last() const { return mLast; }         // SH, SF, the model, nGood / parallax per motion hypothesis
+  const std::vector<int32_t>& last_draws() const { return mDraws; }
+
+ private:
+  float mK[4], mSigma;
+  int mMaxIterations, mDevice;
+  RandomIntT mRandomInt;
+  std::vector<int32_t> mDraws;
+  orbi_two_view_result mLast{};
+};
 
 }  // namespace orbgpu
 

@@ -185,6 +185,26 @@ class Sim3OptResult(C.Structure):
                 ("trace_len", C.c_int32), ("edge_chi2", C.c_void_p)]
 
 
+class TwoViewProblem(C.Structure):
+    """orbi_two_view_problem: the arguments of TwoViewReconstruction's constructor and of Reconstruct, flat."""
+    _fields_ = [("struct_size", C.c_uint32), ("n1", C.c_int32), ("n2", C.c_int32), ("keys1", C.c_void_p), ("keys2", C.c_void_p),
+                ("matches12", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("sigma", C.c_float), ("iterations", C.c_int32)]
+
+
+class TwoViewResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("success", C.c_int32), ("model", C.c_int32), ("best_iteration_H", C.c_int32),
+                ("best_iteration_F", C.c_int32), ("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("n_motions", C.c_int32),
+                ("best_motion", C.c_int32), ("h_degenerate", C.c_int32), ("SH", C.c_float), ("SF", C.c_float),
+                ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("R21", C.c_float * 9), ("t21", C.c_float * 3),
+                ("T1", C.c_float * 9), ("T2", C.c_float * 9), ("motion_nGood", C.c_int32 * 8), ("motion_parallax", C.c_float * 8),
+                ("motion_R", C.c_float * 72), ("motion_t", C.c_float * 24), ("vP3D", C.c_void_p), ("vbTriangulated", C.c_void_p),
+                ("hyp_scores", C.c_void_p), ("hyp_models", C.c_void_p), ("hyp_masks", C.c_void_p), ("hyp_sets", C.c_void_p)]
+
+
+TWO_VIEW_MAX_MATCHES, TWO_VIEW_MAX_ITERATIONS = 8192, 4096
+
+
 class NewPointsKF(C.Structure):
     """orbm_newpoints_kf: one keyframe side of CreateNewMapPoints / SearchForTriangulation."""
     _fields_ = [("struct_size", C.c_uint32), ("frame", C.c_void_p), ("featvec", FeatVecView), ("has_mp", C.c_void_p),
@@ -270,6 +290,10 @@ EXPORTED_SYMBOLS = [
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
+# The initialisers (prefix orbi_): a list of its own, because tests/test_capi_cpu.py holds EXPORTED_SYMBOLS against the header's
+# declarations under the prefixes above only.  build() and load() treat both lists alike; tests/test_two_view_cpu.py holds this one.
+INITIALISER_SYMBOLS = ["orbi_two_view_resolve_draws", "orbi_two_view_reconstruct"]
+
 _lib = None
 
 
@@ -309,10 +333,12 @@ def load():
     lib.orbm_sim3_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int]
     lib.orbm_sim3_optimize.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     lib.orbm_sim3_optimize_batch.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.orbi_two_view_resolve_draws.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    lib.orbi_two_view_reconstruct.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orbm_create_new_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orbm_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.orbm_fuse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    for name in EXPORTED_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

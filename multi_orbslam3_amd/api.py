@@ -1056,6 +1056,99 @@ class Sim3Solver:
         return [_sim3_unpack(p, R[b], outs[b][1], outs[b][2], its[b] if p.n >= params[b][1] else 0) for b, p in enumerate(problems)]
 
 
+# ---------------------------------------------------------------- TwoViewReconstruction (S/TwoViewReconstruction.cc)
+
+def two_view_draws(n, iterations, rng):
+    """The raw DUtils::Random::RandomInt(0, size - 1) results of `iterations` RANSAC iterations (S/TwoViewReconstruction.cc:88): int32
+    (iterations, 8), column j uniform in [0, n - j).  rng: a numpy Generator or a seed."""
+    if not isinstance(rng, np.random.Generator):
+        rng = np.random.default_rng(rng)
+    d = np.empty((int(iterations), 8), np.int32)
+    for j in range(8):
+        d[:, j] = rng.integers(0, max(int(n) - j, 1), size=int(iterations))
+    return d
+
+
+def two_view_resolve_draws(n, draws):
+    """Raw draws -> the eight match indices of each minimal set (swap-with-back removal on vAllIndices, :81-96).  Host code."""
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1, 8)
+    idx = np.zeros_like(d)
+    capi.check(capi.load().orbi_two_view_resolve_draws(int(n), _vp(d), len(d), _vp(idx)), "orbi_two_view_resolve_draws")
+    return idx
+
+
+class TwoViewResult:
+    """What one Reconstruct() call returned.  ok is the reference's return value; R21 (3 x 3), t21 (3), vP3D (n1 x 3) and vbTriangulated
+    (n1 bool) are its outputs (zero when not ok).  model: 0 none, 1 homography, 2 fundamental.  motion_*: nGood / parallax / R / t of
+    every motion hypothesis CheckRT ran, in the reference's order.  hyp_* (per_hypothesis=True): scores (2, iterations), models
+    (2, iterations, 3, 3), masks (2, iterations, N) bool and the resolved sets (iterations, 8); row 0 is H, row 1 is F."""
+
+    def __init__(self, r, vP3D, tri, hyp, iterations):
+        self.ok = bool(r.success)
+        self.model, self.n_matches, self.n_inliers = r.model, r.n_matches, r.n_inliers
+        self.best_iteration_H, self.best_iteration_F = r.best_iteration_H, r.best_iteration_F
+        self.SH, self.SF = np.float32(r.SH), np.float32(r.SF)
+        self.H21 = np.array(r.H21, np.float32).reshape(3, 3)
+        self.F21 = np.array(r.F21, np.float32).reshape(3, 3)
+        self.R21 = np.array(r.R21, np.float32).reshape(3, 3)
+        self.t21 = np.array(r.t21, np.float32)
+        self.T1 = np.array(r.T1, np.float32).reshape(3, 3)
+        self.T2 = np.array(r.T2, np.float32).reshape(3, 3)
+        self.n_motions, self.best_motion, self.h_degenerate = r.n_motions, r.best_motion, bool(r.h_degenerate)
+        self.motion_nGood = np.array(r.motion_nGood, np.int32)[: r.n_motions]
+        self.motion_parallax = np.array(r.motion_parallax, np.float32)[: r.n_motions]
+        self.motion_R = np.array(r.motion_R, np.float32).reshape(8, 3, 3)[: r.n_motions]
+        self.motion_t = np.array(r.motion_t, np.float32).reshape(8, 3)[: r.n_motions]
+        self.vP3D, self.vbTriangulated = vP3D, tri.astype(bool)
+        self.hyp_scores = self.hyp_models = self.hyp_masks = self.hyp_sets = None
+        if hyp is not None:
+            sc, mo, ma, se = hyp
+            self.hyp_scores = sc.reshape(2, iterations)
+            self.hyp_models = mo.reshape(2, iterations, 3, 3)
+            self.hyp_masks = np.unpackbits(ma.view(np.uint8), axis=1, bitorder="little")[:, : r.n_matches].astype(bool).reshape(2, iterations, -1)
+            self.hyp_sets = se.reshape(iterations, 8)
+
+
+class TwoViewReconstruction:
+    """ORB_SLAM3::TwoViewReconstruction (I/TwoViewReconstruction.h): both RANSACs of a call in one kernel launch, every motion
+    hypothesis of ReconstructH / ReconstructF in a second one.  K: 3 x 3 (or (fx, fy, cx, cy)).  Draws come from the caller (`draws`,
+    raw RandomInt results as two_view_draws makes them) or from the object's own seeded generator."""
+
+    def __init__(self, K, sigma=1.0, iterations=200, device=0, seed=0):
+        K = np.asarray(K, np.float32)
+        self.K = (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])) if K.ndim == 2 else tuple(float(v) for v in K)
+        self.mSigma, self.mMaxIterations = float(sigma), int(iterations)
+        self.device = int(device)
+        self.rng = np.random.default_rng(seed)
+        self.lib = capi.load()
+
+    def Reconstruct(self, vKeys1, vKeys2, vMatches12, draws=None, per_hypothesis=False):
+        """vKeys1 / vKeys2: (n, 2) undistorted keypoint positions; vMatches12: n1 indices into vKeys2, -1 for none.  -> TwoViewResult."""
+        k1 = np.ascontiguousarray(vKeys1, np.float32).reshape(-1, 2)
+        k2 = np.ascontiguousarray(vKeys2, np.float32).reshape(-1, 2)
+        m12 = np.ascontiguousarray(vMatches12, np.int32).reshape(-1)
+        assert len(m12) == len(k1), "one entry of vMatches12 per keypoint of frame 1"
+        n, H = int((m12 >= 0).sum()), self.mMaxIterations
+        if draws is None:
+            draws = two_view_draws(n, H, self.rng) if n >= 8 else np.zeros((max(H, 1), 8), np.int32)
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1, 8)
+        assert len(d) >= H, "eight raw draws per iteration"
+        p = capi.TwoViewProblem(C.sizeof(capi.TwoViewProblem), len(k1), len(k2), capi.ptr(k1), capi.ptr(k2), capi.ptr(m12), *self.K,
+                                self.mSigma, H)
+        r = capi.TwoViewResult()
+        r.struct_size = C.sizeof(capi.TwoViewResult)
+        vP3D, tri = np.zeros((max(len(k1), 1), 3), np.float32), np.zeros(max(len(k1), 1), np.uint8)
+        r.vP3D, r.vbTriangulated = capi.ptr(vP3D), capi.ptr(tri)
+        hyp = None
+        if per_hypothesis:
+            Hc = max(H, 1)
+            hyp = (np.zeros(2 * Hc, np.float32), np.zeros((2 * Hc, 9), np.float32), np.zeros((2 * Hc, max((n + 63) // 64, 1)), np.uint64),
+                   np.zeros((Hc, 8), np.int32))
+            r.hyp_scores, r.hyp_models, r.hyp_masks, r.hyp_sets = (capi.ptr(a) for a in hyp)
+        capi.check(self.lib.orbi_two_view_reconstruct(self.device, C.byref(p), _vp(d), C.byref(r)), "orbi_two_view_reconstruct")
+        return TwoViewResult(r, vP3D[: len(k1)], tri[: len(k1)], hyp, H)
+
+
 # ---------------------------------------------------------------- OptimizeSim3 (S/Optimizer.cc:4031-4310)
 
 class Sim3OptProblem:

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "resolve_draws.hpp"
 
 using orbg::select_device;
 
@@ -62,13 +63,12 @@ struct Sim3Rec {                 // what the host reads back per problem
 };
 
 // vAvailableIndices = mvAllIndices (the identity) with swap-with-back removal, :191-206, for raw draws r0 in [0, n), r1 in [0, n-1),
-// r2 in [0, n-2): position r0 holds n-1 after the first removal; after the second, position r1 holds what stood at the back (position
-// n-2), which is n-1 when the first removal had put it there.  The later write wins where positions coincide.
+// r2 in [0, n-2): the closed form of resolve_draws.hpp with three draws.
 __host__ __device__ inline void sim3_resolve_draws(int n, int r0, int r1, int r2, int* idx) {
-  idx[0] = r0;
-  idx[1] = (r1 == r0) ? n - 1 : r1;
-  const int back = (r0 == n - 2) ? n - 1 : n - 2;
-  idx[2] = (r2 == r1) ? back : (r2 == r0) ? n - 1 : r2;
+  const int r[3] = {r0, r1, r2};
+  int o[3];
+  orbg::resolve_draws<3>(n, r, o);
+  idx[0] = o[0]; idx[1] = o[1]; idx[2] = o[2];
 }
 
 // C-2: one row of a 3x3 product, double accumulation in k order
