@@ -806,6 +806,50 @@ typedef struct orbm_fuse_record {
 int orbm_fuse(const orbm_fuse_kf* kfs, int K, const orbm_worldpoints_view* pts, const uint8_t* skip, const orbm_fuse_params* params,
               orbm_fuse_record* records, uint16_t* cand);
 
+/* ---------------------------------------------------------------- ORBmatcher::SearchForInitialization (S/ORBmatcher.cc:702-817)
+ *
+ * The matcher of Tracking::MonocularInitialization (S/Tracking.cc:2217).  f1 = mInitialFrame, f2 = mCurrentFrame, both monocular
+ * (Nleft == -1) and resident: uploaded, views of an extractor, or left by the monocular constructor.  prev_matched is vbPrevMatched
+ * (n1 x {x, y}): the query point of feature i1 on entry, overwritten with F2.mvKeysUn[matches12[i1]].pt for the surviving matches
+ * (:812-814) -- also when the call answers ORBG_CAP_EXCEEDED for the debug entries, so a caller that repeats the call hands in the
+ * original again.  matches12 (n1) is vnMatches12, *n_matches the return value.  n_prev must be n1.
+ *
+ * The device gathers, per octave-0 feature of F1, the list Frame::GetFeaturesInArea(x, y, window_size, 0, 0) returns, in its order and
+ * with the Hamming distances; the host applies :733-814 to the lists (csrc/init_replay.hpp).  Every output equals the reference's.
+ *
+ * window_size: windowSize (100 at the call site).  nn_ratio: mfNNratio (0.9).  check_orientation: mbCheckOrientation.
+ * list_capacity: entries of the candidate buffer, 0 = the default (2^20, or what an earlier call of the thread grew it to).  Lists
+ * that do not fit are never cut: the kernel reports the total, the buffer grows to it and the search runs again (n_regrown).  A total
+ * above ORBM_INIT_SEARCH_MAX_LIST entries answers ORBG_CAP_EXCEEDED.  The total is an upper bound per query: every octave-0 feature of
+ * the cells its window touches.
+ *
+ * debug (may be NULL): list_start (n1 + 1) receives the lists' CSR offsets, entries the lists as the replay saw them
+ * (index2 | dist << 16), when all n_candidates of them fit into entries_cap; otherwise everything else is complete and the call
+ * answers ORBG_CAP_EXCEEDED.  n_queries: octave-0 features of F1; n_evictions: :760-764; n_rot_rejected: :801-805.
+ *
+ * NULL pointers, n_prev != n1, window_size <= 0, list_capacity < 0, a struct_size below the struct's, frames on two devices:
+ * ORBG_BAD_ARG, before anything is launched.  No device: ORBG_NO_DEVICE.  A side without features, or without an octave-0 feature:
+ * 0 matches, no launch.  Per call: one upload (prev_matched) and two waits for results (the records and the total; the lists), one
+ * more per regrowth.  Besides those, a frame built from a wire block is waited for once, since its host keypoints are written by its
+ * own stream, and the call leaves its stream drained.  The level-0 view of f2 is built by the first call after its content changed
+ * and kept on the frame.  The work is enqueued on the calling thread's stream behind what is pending on the frames' streams; buffers
+ * belong to the calling thread.
+ *
+ * A frame that views an extractor handle (orbm_frame_from_extractor, orbx_frame_mono) reads that handle's feature buffers.  A later
+ * extraction on the handle overwrites them without the frame noticing: while such a frame is still wanted as F1, its handle must not
+ * extract again.  Extract the following frames on another handle (the constructor test keeps one per frame), or upload F1. */
+#define ORBM_INIT_SEARCH_MAX_LIST (1 << 26)
+typedef struct orbm_init_search_params {
+  uint32_t struct_size; int32_t window_size; float nn_ratio; int32_t check_orientation; int32_t list_capacity;
+} orbm_init_search_params;
+typedef struct orbm_init_search_debug {   /* optional, for checkers: the candidate lists as the replay saw them */
+  int32_t* list_start;  /* n1 + 1 */  uint32_t* entries; int32_t entries_cap;
+  int32_t n_queries, n_candidates, n_evictions, n_rot_rejected, n_regrown;
+} orbm_init_search_debug;
+int orbm_search_for_initialization(orbm_frame* f1, orbm_frame* f2, float* prev_matched /* n1 x {x, y}, in/out */, int n_prev,
+                                   const orbm_init_search_params* params, int32_t* matches12 /* n1 */, int* n_matches,
+                                   orbm_init_search_debug* debug /* may be NULL */);
+
 /* ---------------------------------------------------------------- bag of words */
 
 /* DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> flattened (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:60-130,

@@ -270,6 +270,17 @@ class ORBmatcher {
                                          vpMatched.data(), &n), "orbm_search_by_projection_sim3");
     return n;
   }
+  // int SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched, vector<int> &vnMatches12, int windowSize),
+  // :702-817.  vbPrevMatched is F1.N x {x, y}, read and written as the reference does; both frames are monocular.
+  int SearchForInitialization(FrameOnDevice& F1, FrameOnDevice& F2, std::vector<float>& vbPrevMatched, std::vector<int32_t>& vnMatches12,
+                              int windowSize = 10) {
+    int n = 0;
+    vnMatches12.assign(F1.N(), -1);
+    const orbm_init_search_params prm{(uint32_t)sizeof(orbm_init_search_params), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0, 0};
+    check(orbm_search_for_initialization(F1.handle(), F2.handle(), vbPrevMatched.data(), (int)(vbPrevMatched.size() / 2), &prm,
+                                         vnMatches12.data(), &n, nullptr), "orbm_search_for_initialization");
+    return n;
+  }
   // int SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12), :819-959.  vpMatches12[idx1] = idx2.
   int SearchByBoW(FrameOnDevice& pKF2, const orbm_featvec_view& fv2, const uint8_t* mp_valid2, const uint8_t* desc1, int n1,
                   const uint8_t* mp_valid1, const float* angle1, const orbm_featvec_view& fv1, std::vector<int32_t>& vpMatches12) {

@@ -16,6 +16,7 @@
 //   int  PoseOptimization(Frame*)                                                             I/Optimizer.h:47,   S/Optimizer.cc:964-1278
 //   class Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bFixScale, vpKeyFrameMatchedMP)  I/Sim3Solver.h:36-131, S/Sim3Solver.cc (orbgpu::Sim3Solver, at the end)
 //   int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)   S/Optimizer.cc:4031-4310 (orbgpu::OptimizeSim3, at the end)
+//   int ORBmatcher::SearchForInitialization(Frame&, Frame&, vector<cv::Point2f>&, vector<int>&, int)  S/ORBmatcher.cc:702 (dropin::SearchForInitialization)
 //   class TwoViewReconstruction(cv::Mat& K, float sigma, int iterations), bool Reconstruct(...)   I/TwoViewReconstruction.h, S/TwoViewReconstruction.cc (orbgpu::TwoViewReconstruction, at the end)
 //
 // Matrix access goes through mat_f32 / mat_u8 / make_mat (overloads for cv::Mat below, for the mock in the test header).
@@ -205,6 +206,12 @@ struct GpuOps {
     return ORBG_OK;
   }
   static int pose_opt(const pose_opt_problem& p, pose_opt_result& r) { return pose_optimize(&p, &r); }
+  static int search_init(const FrameKey& k1, const orbm_frame_view& v1, const FrameKey& k2, const orbm_frame_view& v2, float* prev, int n_prev,
+                         const orbm_init_search_params& prm, int32_t* matches12, int* n) {
+    FrameOnDevice& f1 = frame(k1, v1);         // (two keys, two slots: the second look-up cannot take the first one's)
+    FrameOnDevice& f2 = frame(k2, v2);
+    return orbm_search_for_initialization(f1.handle(), f2.handle(), prev, n_prev, &prm, matches12, n, nullptr);
+  }
 };
 
 // ------------------------------------------------------------------------------------------------ flattening helpers
@@ -1239,6 +1246,28 @@ int PoseOptimization(FrameT* pFrame) {
   decltype(pFrame->mTcw) T; make_mat(T, 4, 4, R.Tcw);
   pFrame->SetPose(T);                                                                        // :1273-1275
   return R.n_inliers;                                                                        // nInitialCorrespondences - nBad
+}
+
+// int ORBmatcher::SearchForInitialization(Frame &F1, Frame &F2, vector<cv::Point2f> &vbPrevMatched, vector<int> &vnMatches12,
+// int windowSize), S/ORBmatcher.cc:702-817: the matcher of Tracking::MonocularInitialization (S/Tracking.cc:2217).  Both frames are
+// monocular; a Frame that carries its resident copy (mpGpuFrame, left by the monocular constructor) is searched where it is.
+template <class Ops = GpuOps, class FrameT, class Point2fT>
+int SearchForInitialization(FrameT& F1, FrameT& F2, std::vector<Point2fT>& vbPrevMatched, std::vector<int>& vnMatches12, int windowSize,
+                            float mfNNratio, bool mbCheckOrientation) {
+  if (F1.Nleft != -1 || F2.Nleft != -1) throw std::runtime_error("orbgpu dropin: SearchForInitialization is the monocular matcher");
+  FrameFlat f1, f2; flatten_frame<Ops>(F1, f1); flatten_frame<Ops>(F2, f2);
+  const int n1 = F1.N;
+  if ((int)vbPrevMatched.size() != n1) throw std::runtime_error("orbgpu dropin: vbPrevMatched must hold one point per feature of F1");
+  std::vector<float> prev((size_t)n1 * 2);
+  for (int i = 0; i < n1; i++) { prev[2 * i] = vbPrevMatched[i].x; prev[2 * i + 1] = vbPrevMatched[i].y; }
+  std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+  const orbm_init_search_params prm{(uint32_t)sizeof(orbm_init_search_params), windowSize, mfNNratio, mbCheckOrientation ? 1 : 0, 0};
+  int n = 0;
+  check(Ops::search_init(f1.key, f1.v, f2.key, f2.v, prev.data(), n1, prm, m12.data(), &n), "SearchForInitialization");
+  vnMatches12.assign(m12.begin(), m12.begin() + n1);                                       // :705
+  for (int i = 0; i < n1; i++)
+    if (vnMatches12[i] >= 0) { vbPrevMatched[i].x = prev[2 * i]; vbPrevMatched[i].y = prev[2 * i + 1]; }   // :812-814
+  return n;
 }
 
 }  // namespace dropin

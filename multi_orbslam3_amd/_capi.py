@@ -249,6 +249,20 @@ FUSE_RECORD_DTYPE = np.dtype([("status", "<i4"), ("best_idx", "<i4"), ("best_dis
 assert FUSE_RECORD_DTYPE.itemsize == 20
 
 
+class InitSearchParams(C.Structure):
+    """orbm_init_search_params: windowSize, mfNNratio, mbCheckOrientation; list_capacity 0 = the default."""
+    _fields_ = [("struct_size", C.c_uint32), ("window_size", C.c_int32), ("nn_ratio", C.c_float), ("check_orientation", C.c_int32),
+                ("list_capacity", C.c_int32)]
+
+
+class InitSearchDebug(C.Structure):
+    _fields_ = [("list_start", C.c_void_p), ("entries", C.c_void_p), ("entries_cap", C.c_int32), ("n_queries", C.c_int32),
+                ("n_candidates", C.c_int32), ("n_evictions", C.c_int32), ("n_rot_rejected", C.c_int32), ("n_regrown", C.c_int32)]
+
+
+INIT_SEARCH_MAX_LIST = 1 << 26
+
+
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
                 ("iters", C.c_int32 * 4), ("chi2", C.c_double * 4)]
@@ -286,7 +300,7 @@ EXPORTED_SYMBOLS = [
     "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
     "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
     "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
-    "orbm_create_new_points", "orbm_search_for_triangulation", "orbm_fuse",
+    "orbm_create_new_points", "orbm_search_for_triangulation", "orbm_fuse", "orbm_search_for_initialization",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
 ]
 
@@ -338,6 +352,7 @@ def load():
     lib.orbm_create_new_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orbm_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.orbm_fuse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orbm_search_for_initialization.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

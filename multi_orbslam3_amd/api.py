@@ -498,6 +498,36 @@ class ORBmatcher:
         capi.check(self.lib.orbm_hamming_best2(self.device, _vp(q), len(q), _vp(t), len(t), _vp(o)), "orbm_hamming_best2")
         return o
 
+    def SearchForInitialization(self, F1, F2, vbPrevMatched, windowSize=10, debug=False, list_capacity=0):
+        """(Frame& F1, Frame& F2, vbPrevMatched, vnMatches12, windowSize): S/ORBmatcher.cc:702-817, on two resident monocular frames.
+        -> (nmatches, vnMatches12, vbPrevMatched[, lists]); the input array is not modified.  lists (debug=True): list_start (n1 + 1),
+        entries (index2 | dist << 16, in the reference's candidate order) and the counters of orbm_init_search_debug."""
+        prev_in = np.ascontiguousarray(vbPrevMatched, np.float32).reshape(-1, 2)
+        n1 = len(prev_in)
+        prm = capi.InitSearchParams(C.sizeof(capi.InitSearchParams), int(windowSize), self.mfNNratio, int(self.mbCheckOrientation),
+                                    int(list_capacity))
+        cap = 1 << 18
+        while True:
+            prev = prev_in.copy()
+            m12 = np.full(max(n1, 1), -1, np.int32)
+            n = C.c_int(0)
+            dbg = start = entries = None
+            if debug:
+                start = np.zeros(n1 + 1, np.int32); entries = np.zeros(cap, np.uint32)
+                dbg = capi.InitSearchDebug(capi.ptr(start), capi.ptr(entries), cap, 0, 0, 0, 0, 0)
+            rc = self.lib.orbm_search_for_initialization(F1.h, F2.h, _vp(prev), n1, C.byref(prm), _vp(m12), C.byref(n),
+                                                         C.byref(dbg) if debug else None)
+            if debug and rc == capi.ORBG_CAP_EXCEEDED and dbg.n_candidates > cap:      # the lists need more room: the same call again
+                cap = int(dbg.n_candidates)
+                continue
+            capi.check(rc, "orbm_search_for_initialization")
+            break
+        if not debug:
+            return n.value, m12[:n1], prev
+        lists = dict(list_start=start, entries=entries[: int(start[n1])].copy(), n_queries=dbg.n_queries, n_candidates=dbg.n_candidates,
+                     n_evictions=dbg.n_evictions, n_rot_rejected=dbg.n_rot_rejected, n_regrown=dbg.n_regrown)
+        return n.value, m12[:n1], prev, lists
+
     def SearchByProjection(self, F, mv, th=1.0, bFarPoints=False, thFarPoints=50.0, assigned_mp=None, assigned_obs=None):
         """(Frame&, vector<MapPoint*>&, th, bFarPoints, thFarPoints): S/ORBmatcher.cc:44-214."""
         amp = np.ascontiguousarray(assigned_mp, np.int32).copy()

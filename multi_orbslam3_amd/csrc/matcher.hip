@@ -1048,6 +1048,11 @@ struct orbm_frame {
                                          // mapped pinned memory, read by the host only when a query's top-4 cannot decide
   PinnedBuf<QResult> results;
   float last_ms = 0;
+  // what another translation unit keeps per frame content (search_init.hip: the level-0 view): content_gen counts the changes of the
+  // frame's features, side_free(side_cache) runs when the frame goes
+  unsigned content_gen = 0;
+  void* side_cache = nullptr;
+  void (*side_free)(void*) = nullptr;
 };
 
 static int frame_set_params(orbm_frame* f, const orbm_frame_view* v, int n) {
@@ -1055,6 +1060,7 @@ static int frame_set_params(orbm_frame* f, const orbm_frame_view* v, int n) {
   // feature indices travel in 16 bits (candidate lists idx | dist << 16, QResult.idx with 0xFFFF = none)
   if (n >= ORBG_MAX_FRAME_FEATURES) return ORBG_CAP_EXCEEDED;
   FrameParams& p = f->fp;
+  f->content_gen++;
   p.n = n;
   p.min_x = v->min_x; p.max_x = v->max_x; p.min_y = v->min_y; p.max_y = v->max_y;
   p.w_inv = static_cast<float>(ORBG_GRID_COLS) / static_cast<float>(v->max_x - v->min_x);
@@ -1116,6 +1122,7 @@ extern "C" int orbm_frame_destroy(orbm_frame* f) {
   f->d_kps.release(); f->d_desc.release(); f->d_uright.release(); f->d_depth.release(); f->d_cell_of.release();
   f->d_cell_start.release(); f->d_cell_items.release(); f->stage.release(); f->d_stage.release();
   f->d_counter.release(); f->list.release(); f->results.release(); f->sig.release(); f->h_kps_pin.release(); f->d_qflag.release(); f->d_blk_cnt.release(); f->d_slot_pt.release(); f->d_total.release(); f->h_slot_pt.release(); f->h_vis.release();
+  if (f->side_cache && f->side_free) f->side_free(f->side_cache);
   for (auto& e : f->ev) if (e) (void)hipEventDestroy(e);
   if (!f->ext_stream) orbg::release_stream(f->own_stream);
   delete f;
@@ -1213,6 +1220,7 @@ int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v
 // Frame(t+2)): the frame goes back to its own stream.
 void orbm_internal_set_n(orbm_frame* f, int n) {
   f->fp.n = n; f->hk_cached_n = -1;
+  f->content_gen++;
   f->stream = f->own_stream;
 }
 
@@ -1231,6 +1239,15 @@ int orbm_internal_kf_features(orbm_frame* f, const orbx_keypoint** d_kps, const 
 int orbm_internal_kf_grid(orbm_frame* f, const int** d_cell_start, const int** d_cell_items, FrameParams* fp) {
   if (!f || !f->d_cell_start.p || !f->d_cell_items.p) return ORBG_BAD_ARG;
   *d_cell_start = f->d_cell_start.p; *d_cell_items = f->d_cell_items.p; *fp = f->fp;
+  return ORBG_OK;
+}
+
+// The per-content cache slot of the frame (search_init.hip).  A host mirror that a kernel of the frame's own stream writes
+// (orbk_frame_from_wire) is complete once that stream has drained: the caller reads it next.
+int orbm_internal_side_cache(orbm_frame* f, unsigned* content_gen, void*** slot, void (***free_fn)(void*)) {
+  if (!f) return ORBG_BAD_ARG;
+  if (f->hk && f->hk == f->h_kps_pin.h) ORBG_HIP(hipStreamSynchronize(f->stream));
+  *content_gen = f->content_gen; *slot = &f->side_cache; *free_fn = &f->side_free;
   return ORBG_OK;
 }
 

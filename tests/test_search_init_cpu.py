@@ -1,0 +1,177 @@
+"""ORBmatcher::SearchForInitialization without a device: the numpy model against a brute-force variant, the property every named case
+exists for, the serial C++ restatement (tests/cpp/search_init_ref.hpp, through tests/cpp/search_init_glue --ref) and the library's
+own replay header (csrc/init_replay.hpp, as a stand-alone program under AddressSanitizer and UBSan) against the model, and the
+argument checks of the C-ABI."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import search_init_model as sm
+from multi_orbslam3_amd import _capi as capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GLUE = os.path.join(ROOT, "tests", "cpp", "search_init_glue")
+
+
+@pytest.fixture(scope="module")
+def family():
+    """name -> (case, model result); computed once, shared, never modified."""
+    return {name: (c, sm.run_case(c)) for name, c in sm.cases().items()}
+
+
+@pytest.fixture(scope="module")
+def chain():
+    c = sm.case_chain()
+    return c, sm.run_chain(c)
+
+
+def test_grid_walk_equals_all_pairs_sorted_by_cell_and_index(family):
+    for name, (c, r) in family.items():
+        start, ent = sm.brute_lists(c["F1"], c["F2"], c["prev"], c["window"])
+        assert np.array_equal(start, r["list_start"]) and np.array_equal(ent, r["entries"]), name
+
+
+def test_small_has_evictions_and_needs_the_matched_distance_skip(family):
+    c, r = family["small"]
+    assert (c["F1"].n, c["F2"].n) == (600, 670) and set(np.unique(c["F1"].kps["octave"])) == set(range(8))
+    assert r["n_evictions"] >= 1 and r["nmatches"] > 50
+    without = sm.run_case(c, skip_rule=False)
+    assert int((without["matches12"] != r["matches12"]).sum()) >= 1
+    longest = int(np.diff(r["list_start"]).max())
+    print("small: %d queries, %d evictions, %d results change without the skip, longest list %d" %
+          (r["n_queries"], r["n_evictions"], int((without["matches12"] != r["matches12"]).sum()), longest))
+
+
+def test_crowded_has_long_lists_ties_and_more_candidates_than_a_small_buffer(family):
+    c, r = family["crowded"]
+    ll = np.diff(r["list_start"])
+    assert ll.max() > 256 and r["n_candidates"] > 4096 and r["n_queries"] == 300
+    ties = 0
+    for i in np.nonzero(ll > 0)[0]:
+        d = np.sort(r["entries"][r["list_start"][i]: r["list_start"][i + 1]] >> 16)
+        ties += len(d) > 1 and d[0] == d[1]
+    assert ties > 50 and r["n_evictions"] >= 1
+
+
+def test_ties_first_in_reference_order_wins_and_equal_best_and_second_is_no_match(family):
+    c, r = family["ties"]
+    s = r["list_start"]
+    first = r["entries"][s[0]: s[1]]
+    assert list(first & 0xFFFF) == c["expect_order"] and len(set(first >> 16)) == 1        # four copies, one distance, reference order
+    assert r["matches12"][0] == -1                                                          # best == second: the ratio test fails
+    assert r["matches12"][1] == 4 and r["matches12"][2] == -1
+    loose = family["ties_loose"][1]                                                         # a ratio above 1 lets the tie through:
+    assert loose["matches12"][0] == c["expect_order"][0]                                    # the first in reference order holds it
+
+
+def test_edges_early_returns_and_the_strict_window(family):
+    c, r = family["edges"]
+    ll = np.diff(r["list_start"])
+    assert (ll[:4] == 0).all() and (ll[9:] == 0).all()                                       # the four early returns; beyond int range
+    for q in range(4):
+        assert sm.cell_bounds(c["F2"], c["prev"][q, 0], c["prev"][q, 1], c["window"]) is None
+    e4 = set(r["entries"][r["list_start"][4]: r["list_start"][5]] & 0xFFFF)
+    assert 1 in e4 and 0 not in e4                                                           # |dx| == windowSize is outside
+    e6 = set(r["entries"][r["list_start"][6]: r["list_start"][7]] & 0xFFFF)
+    assert 3 in e6 and 2 not in e6
+    assert r["matches12"][4] == 1 and r["matches12"][6] == 3
+    assert r["prev"][4].tobytes() == c["F2"].pts[1].tobytes()                                # the match's point, not the query's
+    assert (c["F2"].cell_of < 0).any()                                                       # a feature outside the grid is in no list
+    assert c["F2"].bounds[0] < 0 and c["F2"].bounds[0] != int(c["F2"].bounds[0])
+
+
+@pytest.mark.parametrize("name", ["levels_f1", "levels_f2"])
+def test_no_octave_zero_feature_on_a_side_gives_nothing(family, name):
+    c, r = family[name]
+    assert r["nmatches"] == 0 and (r["matches12"] == -1).all() and r["prev"].tobytes() == c["prev"].tobytes()
+    assert r["n_candidates"] == 0
+
+
+def test_window10_big_and_no_orientation(family):
+    assert np.diff(family["window10"][1]["list_start"]).max() <= 4
+    c, r = family["big"]
+    assert c["F1"].n == c["F2"].n == 4100 and r["nmatches"] > 300
+    assert family["no_orientation"][1]["n_rot_rejected"] == 0 and family["small"][1]["n_rot_rejected"] > 0
+
+
+def test_replay_entry_gives_the_search_on_given_lists(family):
+    c, r = family["small"]
+    again = sm.search(c["F1"], c["F2"], c["prev"], c["window"], given_lists=(r["list_start"], r["entries"]))
+    assert np.array_equal(again["matches12"], r["matches12"]) and again["nmatches"] == r["nmatches"]
+
+
+def test_chain_carries_prev_matched(chain):
+    c, rs = chain
+    assert len(rs) == 5 and all(r["nmatches"] > 20 for r in rs)
+    assert rs[1]["prev"].tobytes() != rs[0]["prev"].tobytes()
+    fresh = sm.search(c["F1"], c["F2"][4], c["prev"], c["window"])                           # without the carried state: another answer
+    assert not np.array_equal(fresh["matches12"], rs[4]["matches12"])
+
+
+def _glue_ref(tmp_path, F1, F2, prev, window, nn_ratio, check):
+    if not os.path.isfile(GLUE):
+        pytest.fail("tests/cpp/search_init_glue is not built: run __graft_entry__.build()")
+    p = str(tmp_path / "scene.bin")
+    sm.write_scene(p, F1, F2, prev, window, nn_ratio, check)
+    out = subprocess.run([GLUE, "--ref", p], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    return sm.parse_program_output(out.stdout, "ref")
+
+
+def _same(got, want, where):
+    assert got["nmatches"] == want["nmatches"], where
+    assert np.array_equal(got["matches12"], want["matches12"]), where
+    assert got["prev"].tobytes() == np.ascontiguousarray(want["prev"], np.float32).tobytes(), where
+
+
+def test_serial_cpp_restatement_equals_the_model(family, chain, tmp_path):
+    for name, (c, r) in family.items():
+        g = _glue_ref(tmp_path, c["F1"], c["F2"], c["prev"], c["window"], c.get("nn_ratio", 0.9), c.get("check_orientation", True))
+        _same(g, r, name)
+        assert np.array_equal(g["list_start"], r["list_start"]) and np.array_equal(g.get("entries", np.zeros(0, np.uint32)), r["entries"]), name
+    c, rs = chain
+    prev = c["prev"]
+    for k, (F2, r) in enumerate(zip(c["F2"], rs)):
+        _same(_glue_ref(tmp_path, c["F1"], F2, prev, c["window"], 0.9, True), r, "chain %d" % k)
+        prev = r["prev"]
+
+
+def test_library_replay_under_sanitizers_equals_the_model(family, tmp_path):
+    exe = str(tmp_path / "init_replay_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "multi_orbslam3_amd", "csrc"), os.path.join(ROOT, "tests", "cpp", "init_replay_check.cpp"),
+                           "-o", exe])
+    for name, (c, r) in family.items():
+        p = str(tmp_path / "lists.bin")
+        sm.write_lists(p, r, c["F1"], c["F2"], c["prev"], c.get("nn_ratio", 0.9), c.get("check_orientation", True))
+        out = subprocess.run([exe, p], capture_output=True, text=True, timeout=120)
+        assert out.returncode == 0 and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, (name, out.stderr[-2000:])
+        g = sm.parse_program_output(out.stdout)
+        _same(g, r, name)
+        assert list(g["counters"]) == [r["n_queries"], r["n_candidates"], r["n_evictions"], r["n_rot_rejected"]], name
+
+
+def test_struct_layout_and_argument_checks_without_a_device():
+    assert C.sizeof(capi.InitSearchParams) == 20
+    assert "orbm_search_for_initialization" in capi.EXPORTED_SYMBOLS
+    lib = capi.load()
+    prm = capi.InitSearchParams(C.sizeof(capi.InitSearchParams), 100, 0.9, 1, 0)
+    prev = np.zeros((4, 2), np.float32); m12 = np.zeros(4, np.int32); n = C.c_int(0)
+    fake = C.c_void_p(1)                                            # never dereferenced: a NULL argument is found first
+    f = lib.orbm_search_for_initialization
+    assert f(None, None, prev.ctypes.data, 4, C.byref(prm), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(None, fake, prev.ctypes.data, 4, C.byref(prm), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(fake, None, prev.ctypes.data, 4, C.byref(prm), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(fake, fake, prev.ctypes.data, 4, None, m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(fake, fake, prev.ctypes.data, 4, C.byref(prm), m12.ctypes.data, None, None) == capi.ORBG_BAD_ARG
+    assert f(fake, fake, None, 4, C.byref(prm), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(fake, fake, prev.ctypes.data, 4, C.byref(prm), None, C.byref(n), None) == capi.ORBG_BAD_ARG
+    assert f(fake, fake, prev.ctypes.data, -1, C.byref(prm), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    for bad in (capi.InitSearchParams(C.sizeof(capi.InitSearchParams) - 4, 100, 0.9, 1, 0), capi.InitSearchParams(20, 0, 0.9, 1, 0),
+                capi.InitSearchParams(20, -5, 0.9, 1, 0), capi.InitSearchParams(20, 100, 0.9, 1, -1)):
+        assert f(fake, fake, prev.ctypes.data, 4, C.byref(bad), m12.ctypes.data, C.byref(n), None) == capi.ORBG_BAD_ARG
+    dbg = capi.InitSearchDebug(None, None, 0, 0, 0, 0, 0, 0)        # a debug struct without list_start
+    assert f(fake, fake, prev.ctypes.data, 4, C.byref(prm), m12.ctypes.data, C.byref(n), C.byref(dbg)) == capi.ORBG_BAD_ARG
