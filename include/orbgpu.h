@@ -229,6 +229,65 @@ int orbx_frame_mono_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_fra
                                const uint8_t* d_img, int width, int height, int stride);
 int orbx_frame_mono_wait(orbx_handle* h, int* n);
 int orbx_set_frame_outputs_un(orbx_handle* h, orbx_keypoint* kps_un /* cap_left of orbx_set_frame_outputs entries, or NULL */);
+/* ---- the RGB-D Frame constructor (TUM / Kinect style agents)
+ * Tracking::GrabImageRGBD (S/Tracking.cc:1086-1142) + Frame::Frame(imGray, imDepth, ...), S/Frame.cc:174-257, as ONE submission with ONE
+ * final synchronisation, like the two constructors above:
+ *   cvtColor to gray for a 3- or 4-channel image (S/Tracking.cc:1092-1105; rgb_order = mbRGB; 8-bit fixed point
+ *     (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14, a fourth channel is ignored; a 1-channel image is taken as it is),
+ *   ExtractORB(0, imGray, 0, 0) (S/Frame.cc:198: lapping area {0, 0}, i.e. the keypoint order of the STEREO constructor's left image),
+ *   UndistortKeyPoints (:212; dist and the view's bounds as for orbx_frame_mono),
+ *   ComputeStereoFromRGBD (:214, :966-988): d = imDepth.at<float>(v, u) at the DISTORTED keypoint, coordinates truncated to int;
+ *     d > 0: mvDepth = d, mvuRight = mvKeysUn.x - bf / d in float32; otherwise both -1 (NaN and d <= 0 fail, +inf passes),
+ *   AssignFeaturesToGrid (:256).
+ * imDepth.convertTo(CV_32F, mDepthMapFactor) (S/Tracking.cc:1107-1108) is applied to the values that are read: when
+ * fabs(depth_factor - 1.0f) > 1e-5 or the depth type is not float32, d = (float)raw * depth_factor (one float32 product, as OpenCV's
+ * convertTo computes it for 16-bit unsigned and float input); otherwise the float is taken as it is.  depth_factor is the float
+ * Tracking holds (S/Tracking.cc:166-172): 1 when fabs(DepthMapFactor) < 1e-5, else 1.0f / DepthMapFactor.
+ * A feature whose truncated coordinates lie outside the image reads no memory and gets -1 (undefined behaviour in the reference; the
+ * extractor's own keypoints are always inside).  `frame` afterwards views mvKeysUn, mDescriptors, mvuRight, mvDepth and the grid on the
+ * device exactly as after orbx_frame_stereo, so the uRight gates of the searches, the stereo edges of PoseOptimization / local BA,
+ * UnprojectStereo and Fuse work on it unchanged.  Limits: pinhole camera, one depth image per frame, features up to the handle's
+ * capacity.  struct_size = sizeof(the struct) as the caller was compiled. */
+#define ORBX_DEPTH_U16 0   /* CV_16U: raw sensor counts */
+#define ORBX_DEPTH_F32 1   /* CV_32F */
+typedef struct orbx_rgbd_image {
+  uint32_t struct_size;
+  int32_t channels;        /* of img: 1 (gray), 3 or 4 (packed 8-bit colour) */
+  const uint8_t* img;      /* imRGB: host memory, or device memory for the _dev entry points */
+  int32_t stride;          /* bytes per row of img */
+  int32_t rgb_order;       /* mbRGB: != 0 the first channel is R, 0 it is B */
+  const void* depth;       /* imD: same memory kind as img */
+  int32_t depth_type;      /* ORBX_DEPTH_U16 / ORBX_DEPTH_F32 */
+  int32_t depth_stride;    /* bytes per row of depth */
+  float depth_factor;      /* mDepthMapFactor (already inverted) */
+  int32_t reserved;
+} orbx_rgbd_image;
+/* Arguments as for orbx_frame_mono (ORBG_EMPTY without an image, a distorted camera needs `frame`, bounds rules with and without
+ * distortion, one submission per handle); in addition ORBG_BAD_ARG without a depth image, for a depth type or channel count other than
+ * the above, strides smaller than a row, and bf <= 0.  A depth image in device memory must be aligned to its element size.
+ * Host outputs (cap entries each, any may be NULL): kps = mvKeys, kps_un = mvKeysUn, desc = mDescriptors, uright = mvuRight,
+ * depth = mvDepth. */
+int orbx_frame_rgbd(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                    int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, float* uright, float* depth,
+                    int cap, int* n);
+int orbx_frame_rgbd_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                        int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, float* uright, float* depth,
+                        int cap, int* n);
+/* The two-halves form (see orbx_frame_stereo_submit).  Both host images go through pinned staging slots (the depth image through one of
+ * its own, allocated by the handle's first RGB-D frame) and may be reused as soon as _submit returns with flags == 0; with
+ * ORBX_SUBMIT_ASYNC they must stay valid until _wait (the descriptor itself is copied).  orbx_set_frame_outputs' arrays receive mvKeys /
+ * mDescriptors / mvuRight / mvDepth, orbx_set_frame_outputs_un's array mvKeysUn.  _wait redoes the whole frame, depth lookup included,
+ * with the host quad-trees if a device list overflowed. */
+int orbx_frame_rgbd_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                           int width, int height, float bf, int flags);
+int orbx_frame_rgbd_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                               const orbx_rgbd_image* im, int width, int height, float bf);
+int orbx_frame_rgbd_wait(orbx_handle* h, int* n);
+/* Frame::ComputeStereoFromRGBD on n caller-given points (host memory): xy = n x {x, y} of mvKeys, xy_un = the same of mvKeysUn (NULL:
+ * xy), depth_img = the raw depth image (depth_type, depth_stride bytes per row, width x height), the conversion rule above; uright /
+ * depth receive n floats each.  For callers that hold features already, as orbx_undistort_points is for the undistortion. */
+int orbx_depth_at_points(int device, const float* xy, const float* xy_un, int n, const void* depth_img, int depth_type, int depth_stride,
+                         int width, int height, float depth_factor, float bf, float* uright, float* depth);
 /* cv::undistortPoints(pts, pts, K, mDistCoef, Mat(), K) for n points (xy_in / xy_out: n x {x, y} float32, host memory; in place
  * allowed), on the device: what Frame::ComputeImageBounds (S/Frame.cc:756-783) runs on the four image corners. */
 int orbx_undistort_points(int device, const float* xy_in, int n, float fx, float fy, float cx, float cy, const orbx_distortion* dist,

@@ -203,6 +203,57 @@ class FrameOnDevice {
     n_ = nl;
     return nl;
   }
+  // Tracking::GrabImageRGBD + Frame::Frame(imGray, imDepth, ...) numerical part (S/Tracking.cc:1092-1108, S/Frame.cc:174-257): cvtColor,
+  // ExtractORB(0, imGray, 0, 0), UndistortKeyPoints, ComputeStereoFromRGBD (with imDepth.convertTo folded into the values it reads) and
+  // AssignFeaturesToGrid with ONE submission and ONE host sync.  im names imRGB / imD as GrabImageRGBD receives them (RgbdImage below
+  // fills it); dist = mDistCoef or nullptr; v.bf = mbf.  Host copies are optional.
+  static orbx_rgbd_image RgbdImage(const uint8_t* imRGB, int channels, int stride, bool mbRGB, const void* imD, int depth_type,
+                                   int depth_stride, float mDepthMapFactor) {
+    orbx_rgbd_image im{};
+    im.struct_size = (uint32_t)sizeof(orbx_rgbd_image);
+    im.img = imRGB; im.channels = channels; im.stride = stride; im.rgb_order = mbRGB ? 1 : 0;
+    im.depth = imD; im.depth_type = depth_type; im.depth_stride = depth_stride; im.depth_factor = mDepthMapFactor;
+    return im;
+  }
+  int RgbdCtor(ORBextractor& ex, orbm_frame_view v, const orbx_distortion* dist, const orbx_rgbd_image& im, int width, int height,
+               std::vector<orbx_keypoint>* mvKeys = nullptr, std::vector<orbx_keypoint>* mvKeysUn = nullptr,
+               std::vector<uint8_t>* mDescriptors = nullptr, std::vector<float>* mvuRight = nullptr, std::vector<float>* mvDepth = nullptr,
+               int cap = 4096) {
+    if (mvKeys) mvKeys->resize(cap);
+    if (mvKeysUn) mvKeysUn->resize(cap);
+    if (mDescriptors) mDescriptors->resize((size_t)cap * 32);
+    if (mvuRight) mvuRight->resize(cap);
+    if (mvDepth) mvDepth->resize(cap);
+    int n = 0;
+    const int rc = orbx_frame_rgbd(ex.handle(), f_, &v, dist, &im, width, height, v.bf, mvKeys ? mvKeys->data() : nullptr,
+                                   mvKeysUn ? mvKeysUn->data() : nullptr, mDescriptors ? mDescriptors->data() : nullptr,
+                                   mvuRight ? mvuRight->data() : nullptr, mvDepth ? mvDepth->data() : nullptr, cap, &n);
+    if (rc != ORBG_EMPTY) check(rc, "orbx_frame_rgbd");           // (no image: N = 0, as the reference's early return leaves it)
+    if (mvKeys) mvKeys->resize(n);
+    if (mvKeysUn) mvKeysUn->resize(n);
+    if (mDescriptors) mDescriptors->resize((size_t)n * 32);
+    if (mvuRight) mvuRight->resize(n);
+    if (mvDepth) mvDepth->resize(n);
+    n_ = n;
+    return n;
+  }
+  // The two-halves form with HOST images: the features reach ORBextractor::SetFrameOutputs' arrays (mvKeysUn: orbx_set_frame_outputs_un)
+  // by the time RgbdCtorWait returns.  flags == 0: the images are the caller's again when Submit returns; async_ingest: at the wait.
+  void RgbdCtorSubmitHost(ORBextractor& ex, orbm_frame_view v, const orbx_distortion* dist, const orbx_rgbd_image& im, int width, int height,
+                          bool async_ingest = false) {
+    check(orbx_frame_rgbd_submit(ex.handle(), f_, &v, dist, &im, width, height, v.bf, async_ingest ? ORBX_SUBMIT_ASYNC : 0),
+          "orbx_frame_rgbd_submit");
+  }
+  // ... and with both images resident in device memory
+  void RgbdCtorSubmit(ORBextractor& ex, orbm_frame_view v, const orbx_distortion* dist, const orbx_rgbd_image& im, int width, int height) {
+    check(orbx_frame_rgbd_dev_submit(ex.handle(), f_, &v, dist, &im, width, height, v.bf), "orbx_frame_rgbd_dev_submit");
+  }
+  int RgbdCtorWait(ORBextractor& ex) {
+    int n = 0;
+    check(orbx_frame_rgbd_wait(ex.handle(), &n), "orbx_frame_rgbd_wait");
+    n_ = n;
+    return n;
+  }
   int N() const { return n_; }
   orbm_frame* handle() const { return f_; }
 

@@ -262,6 +262,15 @@ class InitSearchDebug(C.Structure):
 
 INIT_SEARCH_MAX_LIST = 1 << 26
 
+ORBX_DEPTH_U16, ORBX_DEPTH_F32 = 0, 1
+
+
+class OrbxRgbdImage(C.Structure):
+    """orbx_rgbd_image: the colour / gray image and the depth image of one RGB-D frame (orbx_frame_rgbd*)."""
+    _fields_ = [("struct_size", C.c_uint32), ("channels", C.c_int32), ("img", C.c_void_p), ("stride", C.c_int32),
+                ("rgb_order", C.c_int32), ("depth", C.c_void_p), ("depth_type", C.c_int32), ("depth_stride", C.c_int32),
+                ("depth_factor", C.c_float), ("reserved", C.c_int32)]
+
 
 class PoseOptResult(C.Structure):
     _fields_ = [("Tcw", C.c_float * 16), ("outlier", C.c_void_p), ("n_inliers", C.c_int32), ("n_bad", C.c_int32),
@@ -297,6 +306,8 @@ EXPORTED_SYMBOLS = [
     "orbm_search_by_projection_frame_resident", "orbg_quiesce", "orbg_set_wait_policy", "orbg_get_wait_policy",
     "orbx_frame_mono", "orbx_frame_mono_dev", "orbx_frame_mono_submit", "orbx_frame_mono_dev_submit", "orbx_frame_mono_wait",
     "orbx_set_frame_outputs_un", "orbx_undistort_points",
+    "orbx_frame_rgbd", "orbx_frame_rgbd_dev", "orbx_frame_rgbd_submit", "orbx_frame_rgbd_dev_submit", "orbx_frame_rgbd_wait",
+    "orbx_depth_at_points",
     "orbm_sim3_create", "orbm_sim3_destroy", "orbm_sim3_set_stream", "orbm_sim3_set_problem", "orbm_sim3_set_ransac_parameters",
     "orbm_sim3_ransac_iterations", "orbm_sim3_resolve_draws", "orbm_sim3_iterate", "orbm_sim3_solve_batch",
     "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
@@ -353,6 +364,14 @@ def load():
     lib.orbm_search_for_triangulation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     lib.orbm_fuse.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orbm_search_for_initialization.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    rgbd_head = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
+    lib.orbx_frame_rgbd.argtypes = rgbd_head + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    lib.orbx_frame_rgbd_dev.argtypes = rgbd_head + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    lib.orbx_frame_rgbd_submit.argtypes = rgbd_head + [C.c_int]
+    lib.orbx_frame_rgbd_dev_submit.argtypes = rgbd_head
+    lib.orbx_frame_rgbd_wait.argtypes = [C.c_void_p, C.c_void_p]
+    lib.orbx_depth_at_points.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):

@@ -201,6 +201,82 @@ class ORBextractor:
     def frame_mono_wait(self):
         return self.frame_stereo_dev_wait()[0]
 
+    # ---- the RGB-D Frame constructor (S/Tracking.cc:1086-1142, S/Frame.cc:174-257)
+    @staticmethod
+    def _rgbd_image(image, depth, depth_factor, rgb_order, device_ptrs=None, size=None):
+        """-> (orbx_rgbd_image, width, height, keep-alive).  Host arrays: image H x W (gray) or H x W x 3 / 4 uint8, depth H x W uint16 or
+        float32; rows may be padded (any row stride, unit pixel stride).  device_ptrs = (image pointer, depth pointer) with
+        size = (w, h, channels, stride, depth dtype, depth stride in bytes) for images resident in HBM."""
+        im = capi.OrbxRgbdImage()
+        im.struct_size = C.sizeof(capi.OrbxRgbdImage)
+        im.rgb_order = int(bool(rgb_order))
+        im.depth_factor = float(np.float32(depth_factor))
+        if device_ptrs is not None:
+            w, h, ch, stride, ddtype, dstride = size
+            im.img, im.depth = device_ptrs
+            im.channels, im.stride, im.depth_stride = int(ch), int(stride), int(dstride)
+            im.depth_type = capi.ORBX_DEPTH_U16 if np.dtype(ddtype) == np.uint16 else capi.ORBX_DEPTH_F32
+            return im, int(w), int(h), None
+        if image is None or image.size == 0:
+            return im, 0, 0, None
+        assert image.dtype == np.uint8 and image.ndim in (2, 3) and image.strides[1] == (image.shape[2] if image.ndim == 3 else 1)
+        assert image.ndim == 2 or image.strides[2] == 1
+        im.img = image.ctypes.data
+        im.channels = image.shape[2] if image.ndim == 3 else 1
+        im.stride = image.strides[0]
+        if depth is not None:
+            assert depth.dtype in (np.uint16, np.float32) and depth.shape == image.shape[:2] and depth.strides[1] == depth.itemsize
+            im.depth = depth.ctypes.data
+            im.depth_type = capi.ORBX_DEPTH_U16 if depth.dtype == np.uint16 else capi.ORBX_DEPTH_F32
+            im.depth_stride = depth.strides[0]
+        return im, image.shape[1], image.shape[0], (image, depth)
+
+    def frame_rgbd(self, frame, fv, image, depth, bf, depth_factor=1.0, dist=None, rgb_order=False, download=True, device_ptrs=None,
+                   size=None):
+        """GrabImageRGBD + Frame::Frame(RGB-D) in ONE submission (orbx_frame_rgbd / _dev): colour -> gray, ExtractORB(0, im, 0, 0),
+        UndistortKeyPoints, ComputeStereoFromRGBD, grid; -> (n, mvKeys, mvKeysUn, mDescriptors, mvuRight, mvDepth) or n.
+        depth_factor is Tracking's mDepthMapFactor (api.depth_map_factor of the YAML value)."""
+        im, w, h, keep = self._rgbd_image(image, depth, depth_factor, rgb_order, device_ptrs, size)
+        n = C.c_int(0)
+        kps = kun = desc = ur = dp = None
+        if download:
+            kps = np.zeros(self.cap, capi.KEYPOINT_DTYPE); kun = np.zeros(self.cap, capi.KEYPOINT_DTYPE); desc = np.zeros((self.cap, 32), np.uint8)
+            ur = np.zeros(self.cap, np.float32); dp = np.zeros(self.cap, np.float32)
+        dk, darg = self._dist(dist)
+        fn = self.lib.orbx_frame_rgbd_dev if device_ptrs is not None else self.lib.orbx_frame_rgbd
+        rc = fn(self.h, frame.h if frame is not None else None, C.byref(fv) if fv is not None else None, darg, C.byref(im), w, h, float(bf),
+                capi.ptr(kps), capi.ptr(kun), capi.ptr(desc), capi.ptr(ur), capi.ptr(dp), self.cap, C.byref(n))
+        capi.check(rc, "orbx_frame_rgbd")
+        if frame is not None:
+            frame.n = n.value
+        if download:
+            m = n.value
+            return m, kps[:m].copy(), kun[:m].copy(), desc[:m].copy(), ur[:m].copy(), dp[:m].copy()
+        return n.value
+
+    def frame_rgbd_submit(self, frame, fv, image, depth, bf, depth_factor=1.0, dist=None, rgb_order=False, async_ingest=False,
+                          device_ptrs=None, size=None):
+        """First half of the RGB-D constructor (orbx_frame_rgbd_submit / _dev_submit); collect with frame_rgbd_wait().  The features
+        reach the arrays of set_frame_outputs()."""
+        im, w, h, keep = self._rgbd_image(image, depth, depth_factor, rgb_order, device_ptrs, size)
+        dk, darg = self._dist(dist)
+        self._pending = (frame, fv, dk, im, keep)
+        fr = frame.h if frame is not None else None
+        if device_ptrs is not None:
+            rc = self.lib.orbx_frame_rgbd_dev_submit(self.h, fr, C.byref(fv), darg, C.byref(im), w, h, float(bf))
+        else:
+            rc = self.lib.orbx_frame_rgbd_submit(self.h, fr, C.byref(fv), darg, C.byref(im), w, h, float(bf), 1 if async_ingest else 0)
+        capi.check(rc, "orbx_frame_rgbd_submit")
+
+    def frame_rgbd_wait(self):
+        n = C.c_int(0)
+        capi.check(self.lib.orbx_frame_rgbd_wait(self.h, C.byref(n)), "orbx_frame_rgbd_wait")
+        frame = self._pending[0] if getattr(self, "_pending", None) else None
+        if frame is not None:
+            frame.n = n.value
+        self._pending = None
+        return n.value
+
     def frame_stereo_dev_wait(self):
         nl, nr = C.c_int(0), C.c_int(0)
         capi.check(self.lib.orbx_frame_stereo_dev_wait(self.h, C.byref(nl), C.byref(nr)), "orbx_frame_stereo_dev_wait")
@@ -309,6 +385,29 @@ def undistort_points(xy, cam4, dist, device=0):
     capi.check(lib.orbx_undistort_points(int(device), _vp(xy), len(xy), C.c_float(cam4[0]), C.c_float(cam4[1]), C.c_float(cam4[2]),
                                          C.c_float(cam4[3]), darg, _vp(out)), "orbx_undistort_points")
     return out
+
+
+def depth_map_factor(yaml_value):
+    """The float Tracking holds as mDepthMapFactor (S/Tracking.cc:166-172) for the YAML's DepthMapFactor: 1 when
+    fabs(value) < 1e-5, else 1.0f / value."""
+    f = np.float32(yaml_value)
+    return np.float32(1.0) if abs(f) < 1e-5 else np.float32(1.0) / f
+
+
+def depth_at_points(xy, depth_img, bf, depth_factor=1.0, xy_un=None, device=0):
+    """Frame::ComputeStereoFromRGBD on given points (orbx_depth_at_points): xy = mvKeys' n x 2 float32, xy_un = mvKeysUn's (None: xy),
+    depth_img = the raw depth image (uint16 or float32, rows may be padded) -> (mvuRight, mvDepth)."""
+    lib = capi.load()
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    un = None if xy_un is None else np.ascontiguousarray(xy_un, np.float32).reshape(-1, 2)
+    assert un is None or len(un) == len(xy)
+    assert depth_img.dtype in (np.uint16, np.float32) and depth_img.ndim == 2 and depth_img.strides[1] == depth_img.itemsize
+    ur = np.zeros(len(xy), np.float32); dp = np.zeros(len(xy), np.float32)
+    capi.check(lib.orbx_depth_at_points(int(device), capi.ptr(xy), capi.ptr(un), len(xy), depth_img.ctypes.data,
+                                        capi.ORBX_DEPTH_U16 if depth_img.dtype == np.uint16 else capi.ORBX_DEPTH_F32,
+                                        depth_img.strides[0], depth_img.shape[1], depth_img.shape[0], float(np.float32(depth_factor)),
+                                        float(bf), capi.ptr(ur), capi.ptr(dp)), "orbx_depth_at_points")
+    return ur, dp
 
 
 def image_bounds(width, height, cam4, dist, device=0):

@@ -28,6 +28,7 @@
 #include "wave.hpp"
 #include "stereo_finalize.hpp"
 #include "grid_build.hpp"
+#include "rgbd.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1784,6 +1785,9 @@ struct orbx_handle {
   // host images (orbx_frame_stereo_submit / orbx_frame_stereo / orbx_extract*): one pinned staging slot per handle -- a handle
   // has one submission in flight, and the slot is free again when that submission has been waited for
   PinnedBuf<uint8_t> h_img;
+  // the depth image of an RGB-D frame (orbx_frame_rgbd*): a staging slot and a device copy of its own, allocated by the first such frame
+  PinnedBuf<uint8_t> h_depth_img;
+  DevBuf<uint8_t> d_depth_img;
   PinnedBuf<unsigned> up_ready;                // [0] "second image packed" word of img_upload_pair_kernel, [8] its error word
   unsigned up_seq = 0;
   // orbx_set_frame_outputs: host arrays the two-halves constructor delivers the left image's features into at _wait
@@ -2090,7 +2094,7 @@ extern "C" int orbx_destroy(orbx_handle* h) {
   (void)hipSetDevice(h->device);
   while (h->ingest_state.load(std::memory_order_acquire) == 1) std::this_thread::yield();   // an asynchronous submission is being enqueued
   (void)hipStreamSynchronize(h->stream);
-  h->d_pyr.release(); h->d_img.release(); h->h_img.release(); h->up_ready.release(); h->d_xtab.release(); h->d_ytab.release(); h->d_tower_x.release(); h->d_tower_y.release(); h->d_cells.release();
+  h->d_pyr.release(); h->d_img.release(); h->h_img.release(); h->h_depth_img.release(); h->d_depth_img.release(); h->up_ready.release(); h->d_xtab.release(); h->d_ytab.release(); h->d_tower_x.release(); h->d_tower_y.release(); h->d_cells.release();
   h->d_slots.release(); h->d_counts.release(); h->hdr.release(); h->cand.release(); h->sel.release();
   h->d_kps.release(); h->d_desc.release(); h->h_kps.release(); h->h_desc.release();
   h->d_uright.release(); h->d_depth.release(); h->d_sad.release(); h->h_stereo.release();
@@ -2129,6 +2133,10 @@ struct PostOps {
   bool mono = false, undist = false;
   orbx_distortion dist{};
   orbx_keypoint* kps_un_out = nullptr;       // host copy of mvKeysUn (cap[0] entries), may be NULL
+  // RGB-D constructor (S/Frame.cc:174-257): mvuRight / mvDepth from the depth image (rd.img .. rd.bf set by the caller; uright / depth above
+  // are its host outputs); undist as for the monocular constructor
+  bool rgbd = false;
+  orbg::RgbdDepthArgs rd{};
 };
 // Everything the second half of a GPU-path extraction needs (it runs either right away or in orbx_frame_stereo_dev_wait)
 struct ExtractPending {
@@ -2153,7 +2161,7 @@ struct ExtractPending {
 static void delete_pending(ExtractPending* p) { delete p; }
 int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, int n, hipStream_t stream, const int* d_n,
                          volatile unsigned* done_flag, unsigned done_seq, const StereoFinalizeArgs* fin, const orbg::UndistortArgs* un = nullptr,
-                         bool mono = false);
+                         bool mono = false, const orbg::RgbdDepthArgs* rgbd = nullptr);
 // arguments of the undistortion in front of the grid build (the handle's mvKeysUn buffers are sized here)
 static int make_undistort_args(orbx_handle* h, const PostOps* post, orbg::UndistortArgs* ua) {
   memset(ua, 0, sizeof(*ua));
@@ -2171,6 +2179,37 @@ void orbm_internal_set_n(orbm_frame* f, int n);
 int orbx_internal_kp_capacity(orbx_handle* h);
 static int launch_stereo(orbx_handle* h, float bf, float b, hipStream_t st, bool device_counts, float* host_mirror,
                          StereoFinalizeArgs* defer_finalize = nullptr);
+
+// ---- RGB-D (rgbd.hpp).  ComputeStereoFromRGBD as a kernel of its own: a constructor without a frame object (no grid to build) and
+// orbx_depth_at_points; with a frame it is part of the chain's last launch (rgbd_grid_kernel, matcher.hip).
+__global__ __launch_bounds__(256) void rgbd_depth_kernel(const orbx_keypoint* __restrict__ kps, orbg::RgbdDepthArgs rd, int n, const int* __restrict__ d_n) {
+  if (d_n) n = *d_n;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const orbx_keypoint k = kps[i];
+  float ur, dp;
+  orbg::rgbd_depth_one(rd, k.x, k.y, k.x, &ur, &dp);
+  rd.uright[i] = ur; rd.depth[i] = dp;
+  if (rd.host_out) { rd.host_out[i] = ur; rd.host_out[n + i] = dp; }
+}
+__global__ __launch_bounds__(256) void rgbd_points_kernel(const float2* __restrict__ xy, const float2* __restrict__ xy_un, orbg::RgbdDepthArgs rd, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float2 p = xy[i];
+  float ur, dp;
+  orbg::rgbd_depth_one(rd, p.x, p.y, xy_un[i].x, &ur, &dp);
+  rd.uright[i] = ur; rd.depth[i] = dp;
+}
+// cvtColor in front of the pyramid: 64 x 4 threads = 256 x 4 pixels per workgroup
+__global__ __launch_bounds__(256) void rgbd_gray_kernel(orbg::RgbdGrayArgs a) {
+  orbg::rgbd_gray4(a, 4 * (int)(blockIdx.x * 64 + (threadIdx.x & 63)), (int)(blockIdx.y * 4 + (threadIdx.x >> 6)));
+}
+// what the chain's tail needs of the handle for an RGB-D frame
+static orbg::RgbdDepthArgs rgbd_tail_args(orbx_handle* h, const PostOps* post, bool host_out) {
+  orbg::RgbdDepthArgs rd = post->rd;
+  rd.uright = h->d_uright.p; rd.depth = h->d_depth.p; rd.host_out = host_out ? h->h_stereo.d : nullptr;
+  return rd;
+}
 
 // Core: cams_mask selects which cameras of the rig are processed; d_img are device pointers.
 static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img0, const uint8_t* d_img1, int w, int hgt,
@@ -2209,7 +2248,8 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
   if (!use_gpu) h->pool->prepare();              // wake the host quad-tree workers only when they will be used
   const bool want_desc = desc_out[0] || desc_out[1];
   const bool do_stereo = use_gpu && post && post->stereo && ncams == 2;
-  const bool stereo_out = do_stereo && (post->uright || post->depth);
+  const bool do_rgbd = post && post->rgbd && ncams == 1;
+  const bool stereo_out = (do_stereo || (do_rgbd && use_gpu)) && (post->uright || post->depth);
   OctCfg oc = h->octcfg;
   oc.n_cams = ncams;                          // cameras processed by THIS call (a rig handle may extract one image)
   const uint8_t* const img1 = d_img1 ? d_img1 : d_img0;
@@ -2269,6 +2309,10 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
                                       post->frame ? &unused : nullptr);
         if (rcs) return rcs;
       }
+      // RGB-D without a frame object: no undistortion (refused), no grid -- the depth lookup is the chain's tail
+      if (do_rgbd && !post->frame && h->sel_bound > 0)
+        hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->sel_bound + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, post, stereo_out),
+                           0, h->d_nkp.p);
     }
     return ORBG_OK;
   };
@@ -2287,7 +2331,10 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
                                    reinterpret_cast<unsigned*>(h->d_overflow.p + 2)};
         orbg::UndistortArgs ua;
         if ((rc = make_undistort_args(h, post, &ua))) return rc;
-        if ((rc = orbm_internal_attach(post->frame, h, post->view, -1, st, h->d_nkp.p, flag, seq, with_fin ? &fin : nullptr, &ua, post->mono))) return rc;
+        orbg::RgbdDepthArgs rd;
+        if (do_rgbd) rd = rgbd_tail_args(h, post, stereo_out);
+        if ((rc = orbm_internal_attach(post->frame, h, post->view, -1, st, h->d_nkp.p, flag, seq, with_fin ? &fin : nullptr, &ua, post->mono,
+                                       do_rgbd ? &rd : nullptr))) return rc;
         posted = true;
       }
     }
@@ -2402,11 +2449,20 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
         stereo_out_host = true;
       }
     }
+    // RGB-D: the kernels mirror mvuRight / mvDepth into the mapped block themselves (complete at the synchronisation below)
+    const bool rgbd_out = do_rgbd && h->n_kp[0] > 0 && (post->uright || post->depth);
     if (post->frame) {
       orbg::UndistortArgs ua;
       if ((rc = make_undistort_args(h, post, &ua))) return rc;
-      if ((rc = orbm_internal_attach(post->frame, h, post->view, h->n_kp[0], st, nullptr, nullptr, 0u, nullptr, &ua, post->mono))) return rc;
+      orbg::RgbdDepthArgs rd;
+      if (do_rgbd) rd = rgbd_tail_args(h, post, rgbd_out);
+      if ((rc = orbm_internal_attach(post->frame, h, post->view, h->n_kp[0], st, nullptr, nullptr, 0u, nullptr, &ua, post->mono,
+                                     do_rgbd ? &rd : nullptr))) return rc;
+    } else if (do_rgbd && h->n_kp[0] > 0) {
+      hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->n_kp[0] + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, post, rgbd_out),
+                         h->n_kp[0], (const int*)nullptr);
     }
+    if (rgbd_out) stereo_out_host = true;
   }
   const bool want_out = kps_out[0] || desc_out[0] || kps_out[1] || desc_out[1];
   if (n_sel_total > 0) {
@@ -2424,6 +2480,7 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
       base += h->n_kp[cam];
     }
   }
+  if (stereo_out_host && do_rgbd && h->n_kp[0] > cap[0]) return ORBG_CAP_EXCEEDED;
   if (stereo_out_host) {
     if (post->uright) memcpy(post->uright, h->h_stereo.h, (size_t)h->n_kp[0] * 4);
     if (post->depth) memcpy(post->depth, h->h_stereo.h + h->n_kp[0], (size_t)h->n_kp[0] * 4);
@@ -2666,13 +2723,14 @@ extern "C" int orbx_frame_stereo_dev(orbx_handle* h, orbm_frame* frame, const or
 // mono: the monocular constructor (img_right unused; dist = mDistCoef or NULL)
 static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
                              const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono,
-                             const orbx_distortion* dist);
+                             const orbx_distortion* dist, const orbx_rgbd_image* rgbd);
+// rgbd: the RGB-D constructor (img_left / img_right / stride unused: the descriptor names the images; dist as for mono)
 static int frame_submit_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
                              const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono = false,
-                             const orbx_distortion* dist = nullptr) {
+                             const orbx_distortion* dist = nullptr, const orbx_rgbd_image* rgbd = nullptr) {
   const double t0 = host_now_us();
   h->tl_queue = t0 - h->tl_t_handover;
-  const int rc = frame_submit_core(h, frame, view, img_left, img_right, on_device, width, height, stride, bf, b, mono, dist);
+  const int rc = frame_submit_core(h, frame, view, img_left, img_right, on_device, width, height, stride, bf, b, mono, dist, rgbd);
   h->tl_enqueue = host_now_us() - t0 - h->tl_pack_acc;
   return rc;
 }
@@ -2684,9 +2742,18 @@ static void fill_mono_post(PostOps* post, orbm_frame* frame, const orbm_frame_vi
   post->undist = dist_active(dist) && frame != nullptr;
   if (post->undist) post->dist = *dist;
 }
+static int rgbd_prepare(orbx_handle* h, const orbx_rgbd_image* im, bool on_device, int w, int hgt, float bf, const uint8_t** d_gray,
+                        int* gray_stride, orbg::RgbdDepthArgs* rd);
+static void fill_rgbd_post(PostOps* post, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, orbx_keypoint* kps_un_out,
+                           float* uright, float* depth, const orbg::RgbdDepthArgs& rd) {
+  post->stereo = false; post->mono = false; post->rgbd = true; post->frame = frame; post->view = view; post->kps_un_out = kps_un_out;
+  post->uright = uright; post->depth = depth; post->bf = rd.bf; post->rd = rd;
+  post->undist = dist_active(dist) && frame != nullptr;
+  if (post->undist) post->dist = *dist;
+}
 static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
                              const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono,
-                             const orbx_distortion* dist) {
+                             const orbx_distortion* dist, const orbx_rgbd_image* rgbd) {
   int rc = select_device(h->device);
   if (rc) return rc;
   if (!h->pending) h->pending = new ExtractPending();
@@ -2694,7 +2761,11 @@ static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame
   if (P.active || P.finished) return ORBG_BAD_ARG;      // the previous submission has not been collected
   const uint8_t* d_img_left = img_left;
   const uint8_t* d_img_right = img_right;
-  if (!on_device) {
+  orbg::RgbdDepthArgs rd{};
+  if (rgbd) {
+    if ((rc = rgbd_prepare(h, rgbd, on_device, width, height, bf, &d_img_left, &stride, &rd))) return rc;
+    d_img_right = nullptr;
+  } else if (!on_device) {
     if ((rc = setup_geometry(h, width, height))) return rc;
     const uint8_t* const both[2] = {img_left, img_right};
     if ((rc = stage_images(h, both, mono ? 1 : 2, width, height, stride))) return rc;
@@ -2703,7 +2774,9 @@ static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame
     stride = width;
   }
   PostOps post;
-  if (mono) fill_mono_post(&post, frame, view, dist, h->out_kps_un);
+  const bool one_cam = mono || rgbd != nullptr;
+  if (rgbd) fill_rgbd_post(&post, frame, view, dist, h->out_kps_un, h->out_uright, h->out_depth, rd);
+  else if (mono) fill_mono_post(&post, frame, view, dist, h->out_kps_un);
   else {
     post.stereo = true; post.bf = bf; post.b = b; post.frame = frame; post.view = view;
     post.uright = h->out_uright; post.depth = h->out_depth;             // (orbx_set_frame_outputs: delivered by _wait)
@@ -2715,7 +2788,7 @@ static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame
   int* no[2] = {&P.n_res[0], &P.n_res[1]};
   int* nm[2] = {nullptr, nullptr};
   P.n_res[1] = 0;
-  rc = extract_core(h, mono ? 1u : 3u, d_img_left, d_img_right, width, height, stride, mono ? kMonoLap : lap_stereo, ko, dout, caps, no, nm, &post,
+  rc = extract_core(h, one_cam ? 1u : 3u, d_img_left, d_img_right, width, height, stride, mono ? kMonoLap : lap_stereo, ko, dout, caps, no, nm, &post,
                     false, true);
   if (rc) { P.active = false; return rc; }
   if (!P.active) P.finished = true;                      // host quad-tree path: it ran to completion inside the call
@@ -2752,6 +2825,7 @@ namespace {
 struct IngestJob {
   orbx_handle* h; orbm_frame* frame; orbm_frame_view view; bool has_view; const uint8_t* L; const uint8_t* R; int w, hgt, stride; float bf, b;
   bool mono = false, has_dist = false; orbx_distortion dist{};
+  bool rgbd = false; orbx_rgbd_image im{};
 };
 struct IngestWorker {
   std::mutex mu;
@@ -2787,7 +2861,7 @@ struct IngestWorker {
         queued.fetch_sub(1, std::memory_order_acq_rel);
       }
       job.h->ingest_rc = frame_submit_impl(job.h, job.frame, job.has_view ? &job.view : nullptr, job.L, job.R, false, job.w, job.hgt,
-                                           job.stride, job.bf, job.b, job.mono, job.has_dist ? &job.dist : nullptr);
+                                           job.stride, job.bf, job.b, job.mono, job.has_dist ? &job.dist : nullptr, job.rgbd ? &job.im : nullptr);
       job.h->ingest_state.store(2, std::memory_order_release);
     }
   }
@@ -2983,6 +3057,186 @@ extern "C" int orbx_set_frame_outputs_un(orbx_handle* h, orbx_keypoint* kps_un) 
   if (handle_busy(h)) return ORBG_BAD_ARG;
   h->out_kps_un = kps_un;
   return ORBG_OK;
+}
+
+
+// ---- the RGB-D Frame constructor (include/orbgpu.h): camera 0, lapping area {0, 0}; colour -> gray in front of the pyramid, the depth
+// lookup between the undistortion and the grid (rgbd.hpp)
+static inline int depth_elem(int type) { return type == ORBX_DEPTH_U16 ? 2 : type == ORBX_DEPTH_F32 ? 4 : 0; }
+static int rgbd_args_ok(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                        bool on_device, int width, int height, float bf) {
+  if (!h || !im || im->struct_size < sizeof(orbx_rgbd_image)) return ORBG_BAD_ARG;
+  int rc = mono_args_ok(h, frame, view, dist, im->img, width, height, im->channels == 1 ? im->stride : width);
+  if (rc) return rc;
+  const int es = depth_elem(im->depth_type);
+  if (!im->depth || !es || !(im->channels == 1 || im->channels == 3 || im->channels == 4) || !(bf > 0.0f)) return ORBG_BAD_ARG;
+  if ((long long)im->stride < (long long)width * im->channels || (long long)im->depth_stride < (long long)width * es) return ORBG_BAD_ARG;
+  // a depth image resident in HBM is read in place: its values must be aligned (a host image is repacked by the staging copy)
+  if (on_device && (((uintptr_t)im->depth | (uintptr_t)im->depth_stride) & (uintptr_t)(es - 1))) return ORBG_BAD_ARG;
+  return ORBG_OK;
+}
+
+// The images of an RGB-D frame on their way to the chain: gray as the other constructors stage it; colour through the same pinned slot
+// (or read in place when resident) and ONE conversion kernel that writes the gray image the pyramid reads; the depth image through a
+// slot and a device copy of its own (allocated by the first RGB-D frame of the handle), moved by one copy kernel.
+static int rgbd_prepare(orbx_handle* h, const orbx_rgbd_image* im, bool on_device, int w, int hgt, float bf, const uint8_t** d_gray,
+                        int* gray_stride, orbg::RgbdDepthArgs* rd) {
+  int rc;
+  if ((rc = setup_geometry(h, w, hgt))) return rc;
+  const int ch = im->channels;
+  if (ch == 1) {
+    if (on_device) { *d_gray = im->img; *gray_stride = im->stride; }
+    else {
+      const uint8_t* one = im->img;
+      if ((rc = stage_images(h, &one, 1, w, hgt, im->stride))) return rc;
+      *d_gray = h->d_img.p; *gray_stride = w;
+    }
+  } else {
+    orbg::RgbdGrayArgs ga;
+    ga.width = w; ga.height = hgt; ga.channels = ch; ga.rgb_order = im->rgb_order != 0;
+    if ((rc = h->d_img.reserve((size_t)w * hgt + 16))) return rc;
+    if (on_device) { ga.src = im->img; ga.src_stride = im->stride; }
+    else {
+      const size_t row = (size_t)w * ch;
+      if ((rc = h->h_img.reserve(row * hgt + 16))) return rc;
+      const double tp0 = host_now_us();
+      if ((size_t)im->stride == row) memcpy(h->h_img.h, im->img, row * hgt);
+      else for (int y = 0; y < hgt; y++) memcpy(h->h_img.h + (size_t)y * row, im->img + (size_t)y * im->stride, row);
+      h->tl_pack_acc += host_now_us() - tp0;
+      ga.src = h->h_img.d; ga.src_stride = (int)row;
+    }
+    ga.dst = h->d_img.p;
+    ga.dwords = (((uintptr_t)ga.src | (uintptr_t)ga.src_stride) & 3u) == 0;
+    hipLaunchKernelGGL(rgbd_gray_kernel, dim3((w + 255) / 256, (hgt + 3) / 4), dim3(256), 0, h->stream, ga);
+    ORBG_HIP(hipGetLastError());
+    *d_gray = h->d_img.p; *gray_stride = w;
+  }
+  const int es = depth_elem(im->depth_type);
+  memset(rd, 0, sizeof(*rd));
+  rd->type = im->depth_type; rd->width = w; rd->height = hgt; rd->factor = im->depth_factor; rd->bf = bf;
+  rd->convert = (fabsf(im->depth_factor - 1.0f) > 1e-5 || im->depth_type != ORBX_DEPTH_F32) ? 1 : 0;      // S/Tracking.cc:1107
+  if (on_device) { rd->img = static_cast<const uint8_t*>(im->depth); rd->stride = im->depth_stride; }
+  else {
+    const size_t row = (size_t)w * es, total = row * hgt;
+    if ((rc = h->h_depth_img.reserve(total + 16)) || (rc = h->d_depth_img.reserve(total + 16))) return rc;
+    const uint8_t* src = static_cast<const uint8_t*>(im->depth);
+    const double tp0 = host_now_us();
+    if ((size_t)im->depth_stride == row) memcpy(h->h_depth_img.h, src, total);
+    else for (int y = 0; y < hgt; y++) memcpy(h->h_depth_img.h + (size_t)y * row, src + (size_t)y * im->depth_stride, row);
+    h->tl_pack_acc += host_now_us() - tp0;
+    const int n16 = (int)((total + 15) / 16);
+    hipLaunchKernelGGL(img_upload_kernel, dim3((n16 + 255) / 256), dim3(256), 0, h->stream, reinterpret_cast<const uint4*>(h->h_depth_img.d),
+                       reinterpret_cast<uint4*>(h->d_depth_img.p), n16);
+    ORBG_HIP(hipGetLastError());
+    rd->img = h->d_depth_img.p; rd->stride = (int)row;
+  }
+  return ORBG_OK;
+}
+
+static int frame_rgbd_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                           bool on_device, int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc,
+                           float* uright, float* depth, int cap, int* n) {
+  if (!n) return ORBG_BAD_ARG;
+  int rc = rgbd_args_ok(h, frame, view, dist, im, on_device, width, height, bf);
+  if (rc) return rc;
+  if (handle_busy(h)) return ORBG_BAD_ARG;
+  if ((rc = select_device(h->device))) return rc;
+  const uint8_t* d_gray = nullptr;
+  int stride = 0;
+  orbg::RgbdDepthArgs rd;
+  if ((rc = rgbd_prepare(h, im, on_device, width, height, bf, &d_gray, &stride, &rd))) return rc;
+  PostOps post;
+  fill_rgbd_post(&post, frame, view, dist, kps_un, uright, depth, rd);
+  const int lap[2][2] = {{0, 0}, {0, 0}};          // ExtractORB(0, imGray, 0, 0), S/Frame.cc:198: the stereo constructor's order
+  orbx_keypoint* ko[2] = {kps, nullptr};
+  uint8_t* dout[2] = {desc, nullptr};
+  const int caps[2] = {cap, 0};
+  int* no[2] = {n, nullptr};
+  int* nm[2] = {nullptr, nullptr};
+  return extract_core(h, 1, d_gray, nullptr, width, height, stride, lap, ko, dout, caps, no, nm, &post);
+}
+
+extern "C" int orbx_frame_rgbd(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
+                               int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, float* uright,
+                               float* depth, int cap, int* n) {
+  if (h) h->tl_begin();
+  const int rc = frame_rgbd_impl(h, frame, view, dist, im, false, width, height, bf, kps, kps_un, desc, uright, depth, cap, n);
+  if (h && rc == ORBG_OK) h->tl_commit(0.0);
+  return rc;
+}
+extern "C" int orbx_frame_rgbd_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                                   const orbx_rgbd_image* im, int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un,
+                                   uint8_t* desc, float* uright, float* depth, int cap, int* n) {
+  return frame_rgbd_impl(h, frame, view, dist, im, true, width, height, bf, kps, kps_un, desc, uright, depth, cap, n);
+}
+
+extern "C" int orbx_frame_rgbd_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                                          const orbx_rgbd_image* im, int width, int height, float bf) {
+  int rc = rgbd_args_ok(h, frame, view, dist, im, true, width, height, bf);
+  if (rc) return rc;
+  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;
+  h->tl_begin();
+  return frame_submit_impl(h, frame, view, nullptr, nullptr, true, width, height, 0, bf, 0.f, false, dist, im);
+}
+
+extern "C" int orbx_frame_rgbd_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                                      const orbx_rgbd_image* im, int width, int height, float bf, int flags) {
+  int rc = rgbd_args_ok(h, frame, view, dist, im, false, width, height, bf);
+  if (rc) return rc;
+  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;       // one submission per handle at a time
+  if (h->pending && (h->pending->active || h->pending->finished)) return ORBG_BAD_ARG;
+  h->tl_begin();
+  if (!(flags & ORBX_SUBMIT_ASYNC)) return frame_submit_impl(h, frame, view, nullptr, nullptr, false, width, height, 0, bf, 0.f, false, dist, im);
+  if ((rc = select_device(h->device))) return rc;
+  IngestJob j;
+  j.h = h; j.frame = frame; j.has_view = view != nullptr; j.L = nullptr; j.R = nullptr; j.w = width; j.hgt = height; j.stride = 0; j.bf = bf; j.b = 0;
+  if (view) j.view = *view;
+  j.has_dist = dist != nullptr;
+  if (dist) j.dist = *dist;
+  j.rgbd = true; j.im = *im;                    // (the descriptor is copied; the images it names must stay valid until _wait)
+  h->ingest_state.store(1, std::memory_order_release);
+  ingest_worker().push(j);
+  return ORBG_OK;
+}
+
+extern "C" int orbx_frame_rgbd_wait(orbx_handle* h, int* n) { return orbx_frame_stereo_dev_wait(h, n, nullptr); }
+
+// Frame::ComputeStereoFromRGBD on caller-given points (host arrays), with GrabImageRGBD's convertTo rule applied to the values read
+extern "C" int orbx_depth_at_points(int device, const float* xy, const float* xy_un, int n, const void* depth_img, int depth_type, int depth_stride,
+                                    int width, int height, float depth_factor, float bf, float* uright, float* depth) {
+  const int es = depth_elem(depth_type);
+  if (n < 0 || (n > 0 && (!xy || !uright || !depth)) || !depth_img || !es || width <= 0 || height <= 0 || !(bf > 0.0f)) return ORBG_BAD_ARG;
+  if ((long long)depth_stride < (long long)width * es) return ORBG_BAD_ARG;
+  int rc = select_device(device);
+  if (rc) return rc;
+  if (n == 0) return ORBG_OK;
+  orbg::MiscStream ms;
+  if ((rc = ms.open())) return rc;
+  const size_t row = (size_t)width * es;
+  DevBuf<float2> d_xy, d_un;
+  DevBuf<float> d_out;
+  DevBuf<uint8_t> d_im;
+  auto done = [&](int code) { d_xy.release(); d_un.release(); d_out.release(); d_im.release(); return code; };
+  if ((rc = d_xy.reserve(n)) || (rc = d_un.reserve(n)) || (rc = d_out.reserve(2 * (size_t)n)) || (rc = d_im.reserve(row * height + 16)))
+    return done(rc);
+  orbg::RgbdDepthArgs rd;
+  memset(&rd, 0, sizeof(rd));
+  rd.img = d_im.p; rd.type = depth_type; rd.stride = (int)row; rd.width = width; rd.height = height; rd.factor = depth_factor; rd.bf = bf;
+  rd.convert = (fabsf(depth_factor - 1.0f) > 1e-5 || depth_type != ORBX_DEPTH_F32) ? 1 : 0;
+  rd.uright = d_out.p; rd.depth = d_out.p + n;
+  hipError_t e = hipMemcpyAsync(d_xy.p, xy, (size_t)n * 8, hipMemcpyHostToDevice, ms.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_un.p, xy_un ? xy_un : xy, (size_t)n * 8, hipMemcpyHostToDevice, ms.s);
+  // (the rows repacked: the device copy is aligned whatever the caller's pointer and stride are)
+  if (e == hipSuccess) e = hipMemcpy2DAsync(d_im.p, row, depth_img, (size_t)depth_stride, row, (size_t)height, hipMemcpyHostToDevice, ms.s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(rgbd_points_kernel, dim3((n + 255) / 256), dim3(256), 0, ms.s, d_xy.p, d_un.p, rd, n);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(uright, d_out.p, (size_t)n * 4, hipMemcpyDeviceToHost, ms.s);
+  if (e == hipSuccess) e = hipMemcpyAsync(depth, d_out.p + n, (size_t)n * 4, hipMemcpyDeviceToHost, ms.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(ms.s);
+  else (void)hipStreamSynchronize(ms.s);
+  return done(e == hipSuccess ? ORBG_OK : ORBG_HIP_ERROR);
 }
 
 // cv::undistortPoints on n host points, on the device (Frame::ComputeImageBounds runs it on the four corners, S/Frame.cc:756-783)

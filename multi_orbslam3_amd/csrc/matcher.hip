@@ -32,6 +32,7 @@ int orbx_internal_left_features(orbx_handle* h, const orbx_keypoint** d_kps, con
                                 const float** d_depth, const orbx_keypoint** h_kps, int* n, hipStream_t* stream);
 
 #include "grid_build.hpp"
+#include "rgbd.hpp"
 
 namespace {
 
@@ -117,6 +118,30 @@ __global__ __launch_bounds__(1024) void undistort_grid_kernel(orbg::UndistortArg
   if (done_flag) {
     if (ua.dst_host) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");           // mvKeysUn for the host: system scope, every wavefront
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // (see grid_build_kernel)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      *done_flag = done_seq;
+    }
+  }
+}
+
+// Last launch of the RGB-D Frame constructor (orbx_frame_rgbd*): Frame::UndistortKeyPoints (S/Frame.cc:212), ComputeStereoFromRGBD (:214,
+// :966-988) and AssignFeaturesToGrid (:256) in one workgroup (rgbd.hpp) -- the depth lookup needs mvKeysUn, the grid needs neither
+// mvuRight nor mvDepth, so the three run back to back without a launch between them.  mvuRight / mvDepth (and mvKeysUn of a distorted
+// camera) also go to mapped pinned memory when the caller asked for them: every wavefront then releases to system scope before the
+// completion word is posted.
+__global__ __launch_bounds__(1024) void rgbd_grid_kernel(const orbx_keypoint* __restrict__ kps, orbg::UndistortArgs ua, orbg::RgbdDepthArgs rd,
+                                                        FrameParams fp, int* __restrict__ cell_of, int* __restrict__ cell_start,
+                                                        int* __restrict__ cell_items, const int* __restrict__ d_n,
+                                                        volatile unsigned* done_flag, unsigned done_seq) {
+  const int n = d_n ? *d_n : fp.n;
+  orbg::rgbd_tail_body(kps, ua, rd, n, threadIdx.x, 1024);
+  // (grid_build_body's thread t reads the records t, t + 1024, ... -- the ones it has just written when ua.on)
+  grid_build_body<1024>(ua.on ? ua.dst : kps, fp, cell_of, cell_start, cell_items, d_n);
+  if (done_flag) {
+    if (rd.host_out || (ua.on && ua.dst_host)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");     // results for the host: system scope, every wavefront
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                        // (see grid_build_kernel)
     __syncthreads();
     if (threadIdx.x == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -1186,7 +1211,7 @@ extern "C" int orbm_frame_from_extractor(orbm_frame* f, orbx_handle* h, const or
 int orbx_internal_kp_capacity(orbx_handle* h);   // extractor.hip
 int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, int n, hipStream_t stream, const int* d_n,
                          volatile unsigned* done_flag, unsigned done_seq, const StereoFinalizeArgs* fin, const orbg::UndistortArgs* un,
-                         bool mono) {
+                         bool mono, const orbg::RgbdDepthArgs* rgbd) {
   if (!f || !h || !v) return ORBG_BAD_ARG;
   const orbx_keypoint* dk; const uint8_t* dd; const float* du; const float* dz; const orbx_keypoint* hk; int n0; hipStream_t xs;
   int rc = orbx_internal_left_features(h, &dk, &dd, &du, &dz, &hk, &n0, &xs);
@@ -1201,7 +1226,12 @@ int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v
   f->kps_p = (un && un->on) ? un->dst : dk;      // the grid and the searches read mvKeysUn
   f->desc_p = dd; f->uright_p = du; f->depth_p = dz; f->hk = hk; f->hk_cached_n = -1;      // (octave / angle of mvKeys == those of mvKeysUn)
   f->stream = stream;              // the extractor's stream: searches on this frame follow its constructor in order
-  if (un && un->on)
+  if (rgbd) {
+    orbg::UndistortArgs ua;
+    if (un) ua = *un; else memset(&ua, 0, sizeof(ua));
+    hipLaunchKernelGGL(rgbd_grid_kernel, dim3(1), dim3(1024), 0, stream, dk, ua, *rgbd, f->fp, f->d_cell_of.p, f->d_cell_start.p,
+                       f->d_cell_items.p, d_n, done_flag, done_seq);
+  } else if (un && un->on)
     hipLaunchKernelGGL(undistort_grid_kernel, dim3(1), dim3(1024), 0, stream, *un, f->fp, f->d_cell_of.p, f->d_cell_start.p, f->d_cell_items.p,
                        d_n, done_flag, done_seq);
   else if (fin)

@@ -118,6 +118,32 @@ class Scene:
         z = -Ow[2] / dw[:, 2]                       # Ow + z * dw hits world z = 0
         return np.where(np.isfinite(z) & (z > 0), z, -1.0).astype(np.float32)
 
+    def depth_image(self, Tcw, dtype=np.float32, factor=5000.0):
+        """Per-pixel camera-frame depth of the plane z = 0 as an RGB-D sensor delivers it: float32 metres, or (dtype uint16) counts of
+        1 / factor metres as TUM's 16-bit depth images hold them (DepthMapFactor = factor); 0 where the ray misses the plane."""
+        c = self.cam
+        u, v = np.meshgrid(np.arange(self.W, dtype=np.float64), np.arange(self.H, dtype=np.float64))
+        d = np.stack([(u - float(c["cx"])) / float(c["fx"]), (v - float(c["cy"])) / float(c["fy"]), np.ones_like(u)], axis=-1)
+        R, t = Tcw[:3, :3], Tcw[:3, 3]
+        Ow = -R.T @ t
+        dwz = d @ R[:, 2]                           # z of R^T d
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = -Ow[2] / dwz
+        z = np.where(np.isfinite(z) & (z > 0), z, 0.0)
+        if np.dtype(dtype) == np.uint16:
+            return np.clip(np.rint(z * factor), 0, 65535).astype(np.uint16)
+        return z.astype(np.float32)
+
+    def color_image(self, gray, channels=3, rgb_order=False):
+        """A colour rendering of a gray image with UNEQUAL channels (R = G = gray, B = gray // 2; alpha 255), packed in RGB(A) or
+        BGR(A) order: its gray value depends on which order the conversion assumes, and the contrast stays that of the gray image."""
+        g = np.asarray(gray, np.uint8)
+        r, gg, b = g, g, (g // 2).astype(np.uint8)
+        planes = [r, gg, b] if rgb_order else [b, gg, r]
+        if channels == 4:
+            planes.append(np.full_like(g, 255))
+        return np.ascontiguousarray(np.stack(planes, axis=-1))
+
     def frame_view_params(self):
         c = self.cam
         return dict(bounds=(0.0, float(self.W), 0.0, float(self.H)),
