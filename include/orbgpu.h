@@ -130,7 +130,8 @@ int orbx_get_level_bordered(orbx_handle* h, int cam, int level, uint8_t* host_ou
 
 /* Test/diagnostic view of ComputeKeyPointsOctTree's vToDistributeKeys (S/ORBextractor.cc:776-853)
  * for the last extraction: per level, FAST candidates in the reference's cell-major order,
- * coordinates relative to (minBorderX,minBorderY).  xys = cap x {x,y,score} int32. */
+ * coordinates relative to (minBorderX,minBorderY).  xys = cap x {x,y,score} int32.  cam must be a camera of that extraction
+ * (after one image on a two-camera handle: camera 0 only; ORBG_BAD_ARG otherwise, and before the first extraction). */
 int orbx_get_candidates(orbx_handle* h, int cam, int level, int32_t* xys, int cap, int* n);
 
 /* Frame::ComputeStereoMatches, S/Frame.cc:785-963, on the device-resident result of the last
@@ -1312,6 +1313,12 @@ int orbx_set_profile_kernel(orbx_handle* h, int which);
  * *n = entries written; reset != 0 forgets them.  For bench.py's per-step diagnosis of a shared host. */
 int orbx_get_ctor_timeline(orbx_handle* h, float* out, int cap, int* n, int reset);
 int orbx_get_fast_kernel_stats(orbx_handle* h, double* sum_ms, int64_t* n);
+/* Number of frames this handle ran the device quad-trees on and then redid with the host quad-trees because a device list
+ * overflowed (more than 4096 candidates at a level of one camera, or more nodes than a level's list holds).  Such a frame costs a
+ * device pass and a host pass; its results are the same.  Frames that go to the host trees at once -- a partial lapping area,
+ * ORBG_HOST_OCTREE=1, a per-level target too large for the node list (4 N + 8 > 2048) -- are no redos and do not count.  Read-only;
+ * counts from the handle's creation, for synchronous calls and for the two-halves constructors alike. */
+int orbx_get_host_redo_count(orbx_handle* h, int64_t* n);
 
 #ifdef __cplusplus
 }

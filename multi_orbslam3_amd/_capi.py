@@ -313,6 +313,7 @@ EXPORTED_SYMBOLS = [
     "orbm_sim3_optimize", "orbm_sim3_optimize_batch",
     "orbm_create_new_points", "orbm_search_for_triangulation", "orbm_fuse", "orbm_search_for_initialization",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
+    "orbx_get_host_redo_count",
 ]
 
 # The initialisers (prefix orbi_): a list of its own, because tests/test_capi_cpu.py holds EXPORTED_SYMBOLS against the header's

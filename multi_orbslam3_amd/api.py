@@ -364,6 +364,12 @@ class ORBextractor:
         capi.check(self.lib.orbx_get_fast_kernel_stats(self.h, C.byref(s), C.byref(n)), "orbx_get_fast_kernel_stats")
         return s.value, n.value
 
+    def host_redo_count(self):
+        """Frames this handle redid with the host quad-trees because a device list overflowed (orbx_get_host_redo_count)."""
+        n = C.c_int64(0)
+        capi.check(self.lib.orbx_get_host_redo_count(self.h, C.byref(n)), "orbx_get_host_redo_count")
+        return n.value
+
     def event_overhead_ms(self, reps=50):
         ms = C.c_float(0.0)
         capi.check(self.lib.orbx_event_overhead(self.h, int(reps), C.byref(ms)), "orbx_event_overhead")

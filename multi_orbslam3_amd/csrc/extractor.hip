@@ -1392,7 +1392,9 @@ __device__ __forceinline__ void stereo_match_wave(const int iL, const uint8_t* _
   if (!(maxU < 0) && row >= 0 && row < nRows) {
     const uint4 a0 = *reinterpret_cast<const uint4*>(dl + (size_t)iL * 32);
     const uint4 a1 = *reinterpret_cast<const uint4*>(dl + (size_t)iL * 32 + 16);
-    // the right keypoint of the NEXT round is requested before this round's gates and descriptor (each a dependent trip to the L2)
+    // the right keypoint of the NEXT round is requested before this round's gates and descriptor (each a dependent trip to the L2).
+    // With nr == 0 this reads kr[-1]: on every path kr is kl + nl of ONE allocation (launch_stereo passes d_kps + nl, the device
+    // counts set kr = kl + nl above) and iL < nl makes nl >= 1 here, so it is the last left keypoint, read and never used.
     orbx_keypoint kpN = kr[min(lane, nr - 1)];
     for (int iR = lane; iR < nr; iR += 64) {
       const orbx_keypoint kpR = kpN;
@@ -1774,6 +1776,8 @@ struct orbx_handle {
   int sel_bound = 0;             // upper bound of selected keypoints (sum of region capacities)
   bool gpu_octree = true;
   bool last_was_gpu = false;
+  int last_ncams = 0;            // cameras the last extraction launched (a rig handle may extract one image)
+  long long host_redos = 0;      // frames redone with the host quad-trees after a device list overflowed (orbx_get_host_redo_count)
   struct ExtractPending* pending = nullptr;    // orbx_frame_stereo_dev_submit .. _wait
   float timings[8] = {0};
   int profile = 1;   // 0: no events, 1: only the FAST kernel is bracketed (bench roofline), 2: every stage
@@ -2245,6 +2249,7 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
     else use_gpu = false;
   }
   h->last_was_gpu = use_gpu;
+  h->last_ncams = ncams;
   if (!use_gpu) h->pool->prepare();              // wake the host quad-tree workers only when they will be used
   const bool want_desc = desc_out[0] || desc_out[1];
   const bool do_stereo = use_gpu && post && post->stereo && ncams == 2;
@@ -3302,6 +3307,7 @@ extern "C" int orbx_get_level_bordered(orbx_handle* h, int cam, int level, uint8
 
 extern "C" int orbx_get_candidates(orbx_handle* h, int cam, int level, int32_t* xys, int cap, int* n) {
   if (!h || cam < 0 || cam >= h->cfg.n_cams || level < 0 || level >= h->cfg.n_levels || !n) return ORBG_BAD_ARG;
+  if (cam >= h->last_ncams) return ORBG_BAD_ARG;       // not a camera of the last extraction (device or host trees alike)
   if (h->last_was_gpu) {
     // device-resident candidate list of the last extraction: fetch and decode on demand
     int rc = select_device(h->device);
@@ -3309,7 +3315,9 @@ extern "C" int orbx_get_candidates(orbx_handle* h, int cam, int level, int32_t* 
     if (!h->cells.empty()) {
       // the constructor chain no longer builds the compacted list (the quad-trees read the per-cell slots): build it now from the
       // slots of the last extraction, which stay valid until the next one
-      const int ncams = h->cfg.n_cams, n_cells = (int)h->cells.size();
+      // Only the cameras of that extraction: after one image on a rig handle the other camera's cell counts are whatever the
+      // allocation held (nothing wrote them), and gathering them would read the slots as far as such a count says.
+      const int ncams = h->last_ncams, n_cells = (int)h->cells.size();
       hipLaunchKernelGGL(gather_cells_kernel, dim3(n_cells, ncams), dim3(256), 0, h->stream, h->d_slots.p, h->d_counts.p, h->geom,
                          h->d_cells.p, n_cells, ncams, h->d_hdr.p, h->d_cand.p, h->cand_cap);
       ORBG_HIP(hipGetLastError());
@@ -3348,6 +3356,8 @@ static int extract_finish_gpu(orbx_handle* h, ExtractPending& c) {
   const PostOps* post = c.has_post ? &c.post : nullptr;
   if (h->h_nkp.h[2]) {
     // a level had more candidates / nodes than the LDS-resident quad-tree holds: redo this frame with the host trees
+    // (the only place that acts on the flag: the synchronous calls and orbx_frame_stereo_dev_wait both finish here)
+    h->host_redos++;
     ORBG_HIP(hipMemsetAsync(h->d_overflow.p, 0, sizeof(int), st));
     return extract_core(h, c.cams_mask, c.d_img0, c.d_img1, c.w, c.hgt, c.stride, c.lap, c.kps_out, c.desc_out, c.cap, c.n_out, c.n_mono_out,
                         post, true, false);
@@ -3431,6 +3441,12 @@ extern "C" int orbx_set_profile_interval(orbx_handle* h, int interval, int reset
   if (!h || interval < 1) return ORBG_BAD_ARG;
   h->profile_interval = interval;
   if (reset) { h->fast_ms_sum = 0; h->fast_ms_n = 0; h->extract_calls = 0; }
+  return ORBG_OK;
+}
+
+extern "C" int orbx_get_host_redo_count(orbx_handle* h, int64_t* n) {
+  if (!h || !n) return ORBG_BAD_ARG;
+  *n = (int64_t)h->host_redos;
   return ORBG_OK;
 }
 
