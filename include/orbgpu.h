@@ -1202,6 +1202,75 @@ int lba_event_overhead(lba_handle* h, int reps, float* ms);
  * one-workgroup kernels, which the handle then keeps using, and the event is counted here.  0 on a healthy box. */
 int lba_get_watchdog_count(lba_handle* h, int64_t* n_timeouts);
 
+/* ---------------------------------------------------------------- full bundle adjustment (Optimizer::BundleAdjustment) */
+
+/* What the edges of ONE keyframe read (S/Optimizer.cc:202,237-241: e->pCamera = pKF->mpCamera; e->fx .. e->bf = pKF->fx .. pKF->mbf).
+ * After a map merge the keyframes of a map belong to different agents: every pose of a ba_problem names its own camera.
+ * Monocular edges (EdgeSE3ProjectXYZ) project through `model` (ORBG_CAM_PINHOLE or ORBG_CAM_KANNALA_BRANDT8); stereo edges
+ * (g2o::EdgeStereoSE3ProjectXYZ) use the five scalars, as in lba_problem. */
+typedef struct ba_camera {
+  float fx, fy, cx, cy, bf;
+  orbg_camera model;
+} ba_camera;
+
+/* Everything S/Optimizer.cc:73-305 reads.  Vertex order follows the rule of lba_problem: poses in ascending vertex id, points
+ * likewise; edges in creation order -- per point, its observations in the order the reference walks them, so the edges of a
+ * point are consecutive and edge.point never decreases along the list (anything else: ORBG_BAD_ARG).
+ * Limits: at most BA_MAX_FREE_POSES free poses (the reduced camera system goes to the widest LDL^T of the library, 8192
+ * unknowns); poses, points and edges are counted and addressed in 32 bits everywhere on this path (no 16-bit packed counts).
+ * n_edges <= BA_MAX_EDGES: an edge index is an int32 and an edge keeps 27 doubles of Jacobian products on the device (216 B: 17 GB
+ * at the cap, addressed in 64 bits); the list of shared-landmark items has 32-bit offsets too, a problem with more than 2^31 - 1 of
+ * them is refused once they have been counted (on the device).  A problem beyond the other limits returns ORBG_CAP_EXCEEDED before
+ * anything is launched.  An edge with ur == LBA_UR_RIGHT_CAMERA (the mpCamera2 edges of a two-camera keyframe,
+ * EdgeSE3ProjectXYZToBody) returns ORBG_BAD_ARG, also before any launch: those edges are not part of this entry point. */
+#define BA_MAX_FREE_POSES 1365
+#define BA_MAX_EDGES 79000000
+typedef struct ba_problem {
+  int32_t n_poses, n_points, n_edges, n_cameras;
+  const float*   poses;        /* n_poses x 16, Tcw row-major float32 (KeyFrame::GetPose) */
+  const uint8_t* pose_fixed;   /* n_poses: pKF->mnId == pMap->GetInitKFid(), or the bUseUniqueId rule of S/Optimizer.cc:110-117 */
+  const int32_t* pose_camera;  /* n_poses: index into cameras[] */
+  const float*   points;       /* n_points x 3 */
+  const lba_edge* edges;
+  const ba_camera* cameras;    /* n_cameras */
+  int32_t iterations;          /* nIterations: ONE optimize(nIterations), no outlier round */
+  int32_t robust;              /* bRobust: Huber kernels on every edge (sqrt 5.99 / sqrt 7.815, S/Optimizer.cc:131-132: not the local BA's 5.991), or none */
+  int32_t device;
+} ba_problem;
+
+typedef struct ba_result {
+  float*   poses;           /* n_poses x 16, caller-allocated */
+  float*   points;          /* n_points x 3; a point with point_included == 0 comes back as it went in */
+  double*  edge_chi2;       /* n_edges (may be NULL): e->chi2() as S/Optimizer.cc:373,400 reads it */
+  uint8_t* edge_depth_pos;  /* n_edges (may be NULL): e->isDepthPositive() */
+  uint8_t* point_included;  /* n_points (may be NULL): 0 = the vertex without an edge that S/Optimizer.cc:289-293 removes */
+  int32_t  status;          /* LBA_APPLIED, or LBA_ABORTED_BEFORE_OPT when the flag was up before the call did anything */
+  int32_t  iters;           /* LM iterations actually run */
+  double   chi2_initial, chi2_final;   /* as in lba_result (robust == 0: the plain chi2) */
+  double*  trace;           /* optional, as in lba_result: per LM iteration {lambda, chi2, trials} */
+  int32_t  trace_cap, trace_len;
+} ba_result;
+
+/* void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, bUseUniqueId, nLoopKF, bRobust), numerical core
+ * (S/Optimizer.cc:73-305) and the state read back at :307-446, reached through GlobalBundleAdjustemnt from
+ * Tracking::CreateInitialMapMonocular (S/Tracking.cc:2316) and LoopClosing::RunGlobalBundleAdjustment (S/LoopClosing.cc:2627).
+ * stop_flag has the poll points and the deterministic negative test form that lba_solve documents; ba_solve_b takes the
+ * reference's own flag (&mbStopGBA) unchanged.  Two calls on the same input return the same bits. */
+int ba_solve(const ba_problem* p, const volatile int32_t* stop_flag, ba_result* r);
+int ba_solve_b(const ba_problem* p, const volatile uint8_t* stop_bool, ba_result* r);
+/* Persistent workspace.  The three capacities are accepted for symmetry with lba_create and are not used: the buffers grow on first
+ * use and are kept. */
+typedef struct ba_handle ba_handle;
+int ba_create(int device, int cap_poses, int cap_points, int cap_edges, ba_handle** out);
+int ba_destroy(ba_handle* h);
+int ba_solve_h(ba_handle* h, const ba_problem* p, const volatile int32_t* stop_flag, ba_result* r);
+int ba_solve_hb(ba_handle* h, const ba_problem* p, const volatile uint8_t* stop_bool, ba_result* r);
+/* MEASUREMENT ONLY, not part of the stable interface (tools/full_ba_time.py; may change or go with the kernels): device time of the handle's LAST solve by phase, from HIP events around every
+ * launch group when `on` was set before that solve -- ms[5] = structure build, linearisation, Schur complement, LDL^T, update and
+ * evaluation.  Off by default (the events cost a few microseconds per launch group). */
+int ba_set_profiling(ba_handle* h, int on);
+int ba_get_phase_ms(ba_handle* h, double* ms /* 5 */);
+
 /* ---------------------------------------------------------------- pose-only optimisation */
 
 /* Everything Optimizer::PoseOptimization(Frame*) reads (S/Optimizer.cc:964-1278): one entry per

@@ -205,6 +205,14 @@ struct GpuOps {
     s.ba->Run(p, stop, r);
     return ORBG_OK;
   }
+  // the full BA: one persistent workspace per calling thread (LoopClosing's GBA thread, or Tracking at initialisation); &mbStopGBA
+  // goes through as it is (ba_solve_hb)
+  static int ba(const ba_problem& p, const volatile bool* stop, ba_result& r) {
+    struct Holder { ba_handle* h = nullptr; ~Holder() { if (h) ba_destroy(h); } };
+    static thread_local Holder s;
+    if (!s.h) { const int rc = ba_create(p.device, 0, 0, 0, &s.h); if (rc) return rc; }
+    return ba_solve_hb(s.h, &p, Optimizer::stop_byte(stop), &r);
+  }
   static int pose_opt(const pose_opt_problem& p, pose_opt_result& r) { return pose_optimize(&p, &r); }
   static int search_init(const FrameKey& k1, const orbm_frame_view& v1, const FrameKey& k2, const orbm_frame_view& v2, float* prev, int n_prev,
                          const orbm_init_search_params& prm, int32_t* matches12, int* n) {
@@ -1211,6 +1219,134 @@ int LocalBundleAdjustment(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, int& num
   pMap->IncreaseChangeIndex();                                                               // :2397 (Tracking reads it: mbMapUpdated)
   ORBGPU_GLUE_T("write-back");
   return R.status;
+}
+
+// void Optimizer::BundleAdjustment(const vector<KeyFrame*>& vpKFs, const vector<MapPoint*>& vpMP, int nIterations, bool* pbStopFlag,
+// bool bUseUniqueId, const unsigned long nLoopKF, const bool bRobust), S/Optimizer.cc:50-447.  Graph collection (:102-298) and the
+// write-back (:307-446) act on the caller's objects as the reference does; the g2o block in between is one ba_solve with a camera per
+// keyframe (e->pCamera = pKF->mpCamera, e->fx .. e->bf = pKF->fx .. pKF->mbf, :202,237-241).  Not covered: the mpCamera2 edges of
+// two-camera keyframes (:250-284; such an observation throws) and the debug counters behind dist > 1 (:353-413, output only).
+// Returns the number of LM iterations (the reference returns void).
+template <class Ops = GpuOps, class KeyFrameT, class MapPointT>
+int BundleAdjustment(const std::vector<KeyFrameT*>& vpKFs, const std::vector<MapPointT*>& vpMP, int nIterations, bool* pbStopFlag = nullptr,
+                     bool bUseUniqueId = false, const unsigned long nLoopKF = 0, const bool bRobust = true) {
+  if (vpKFs.empty()) return 0;
+  auto* pMap = vpKFs[0]->GetMap();                                                           // :56
+  auto kf_id = [&](KeyFrameT* kf) -> unsigned long { return bUseUniqueId ? kf->mnUniqueId : kf->mnId; };
+  // ---- keyframe vertices (:102-129): the keyframes that are not bad, in ascending vertex id
+  struct KfV { unsigned long id; KeyFrameT* kf; };
+  std::vector<KfV> kfs;
+  unsigned long maxKFid = 0;
+  for (KeyFrameT* kf : vpKFs) {
+    if (kf->isBad()) continue;
+    kfs.push_back(KfV{kf_id(kf), kf});
+    if (kf_id(kf) > maxKFid) maxKFid = kf_id(kf);
+  }
+  std::stable_sort(kfs.begin(), kfs.end(), [](const KfV& a, const KfV& b) { return a.id < b.id; });
+  std::unordered_map<const KeyFrameT*, int32_t> col;
+  std::vector<float> poses(16 * kfs.size()); std::vector<uint8_t> fixed(kfs.size()); std::vector<int32_t> pose_camera(kfs.size());
+  // the camera table: the distinct (camera object, fx, fy, cx, cy, bf) of the keyframes -- after a merge, one per agent
+  std::vector<ba_camera> cameras;
+  struct CamKey { const void* cam; float s[5]; };
+  std::vector<CamKey> camKeys;
+  for (size_t i = 0; i < kfs.size(); i++) {
+    KeyFrameT* kf = kfs[i].kf;
+    col[kf] = (int32_t)i;
+    const auto Tm = kf->GetPose();
+    std::memcpy(&poses[16 * i], mat_f32(Tm), 64);
+    fixed[i] = bUseUniqueId ? (kf->mnId == pMap->GetInitKFid() && kf->mnClientId == pMap->mnClientId)       // :110-117
+                            : (kf->mnId == pMap->GetInitKFid());
+    const CamKey key{kf->mpCamera, {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf}};
+    size_t c = 0;
+    for (; c < camKeys.size(); c++)
+      if (camKeys[c].cam == key.cam && !std::memcmp(camKeys[c].s, key.s, sizeof(key.s))) break;
+    if (c == camKeys.size()) {
+      camKeys.push_back(key);
+      ba_camera bc{};
+      bc.fx = kf->fx; bc.fy = kf->fy; bc.cx = kf->cx; bc.cy = kf->cy; bc.bf = kf->mbf;
+      if (kf->mpCamera) fill_camera(bc.model, kf->mpCamera);
+      else { bc.model.model = ORBG_CAM_PINHOLE; bc.model.fx = kf->fx; bc.model.fy = kf->fy; bc.model.cx = kf->cx; bc.model.cy = kf->cy; }
+      cameras.push_back(bc);
+    }
+    pose_camera[i] = (int32_t)c;
+  }
+  // ---- point vertices and their edges (:136-298): the points that are not bad, in ascending vertex id; a point's observations by
+  // keyframe vertex id (the reference walks a std::map keyed by address: only the order of sums differs)
+  struct PtV { unsigned long id; size_t idx; };
+  std::vector<PtV> pts_v;
+  for (size_t i = 0; i < vpMP.size(); i++)
+    if (!vpMP[i]->isBad()) pts_v.push_back(PtV{bUseUniqueId ? vpMP[i]->mnUniqueId : vpMP[i]->mnId + maxKFid + 1, i});
+  std::stable_sort(pts_v.begin(), pts_v.end(), [](const PtV& a, const PtV& b) { return a.id < b.id; });
+  std::vector<float> pts(3 * pts_v.size());
+  std::vector<lba_edge> edges;
+  struct ObsRef { unsigned long vid; KeyFrameT* kf; int li; int32_t col; };
+  std::vector<ObsRef> obs;
+  for (size_t j = 0; j < pts_v.size(); j++) {
+    MapPointT* mp = vpMP[pts_v[j].idx];
+    const auto Xm = mp->GetWorldPos();
+    std::memcpy(&pts[3 * j], mat_f32(Xm), 12);
+    obs.clear();
+    for (const auto& ob : mp->GetObservations()) {
+      KeyFrameT* kf = ob.first;
+      if (kf->isBad() || kf_id(kf) > maxKFid) continue;                                       // :161,167
+      const auto it = col.find(kf);
+      if (it == col.end()) continue;                                                          // optimizer.vertex(id) == NULL (:163,169)
+      if (kf->mpCamera2 && std::get<1>(ob.second) != -1) throw std::runtime_error("orbgpu BundleAdjustment: mpCamera2 observations are not supported");
+      const int li = std::get<0>(ob.second);
+      obs.push_back(ObsRef{kf_id(kf), kf, li, it->second});                                   // nEdges++ (:173), also when no edge follows
+    }
+    std::sort(obs.begin(), obs.end(), [](const ObsRef& a, const ObsRef& b) { return a.vid < b.vid; });
+    for (const ObsRef& o : obs) {
+      if (o.li < 0) continue;                                                                 // leftIndex == -1: counted, no edge
+      const auto& kp = o.kf->mvKeysUn[o.li];
+      edges.push_back(lba_edge{o.col, (int32_t)j, kp.pt.x, kp.pt.y, o.kf->mvuRight[o.li] /* < 0: monocular (:177) */, o.kf->mvInvLevelSigma2[kp.octave]});
+    }
+  }
+  ba_problem P{};
+  P.n_poses = (int32_t)kfs.size(); P.n_points = (int32_t)pts_v.size(); P.n_edges = (int32_t)edges.size(); P.n_cameras = (int32_t)cameras.size();
+  P.poses = poses.data(); P.pose_fixed = fixed.data(); P.pose_camera = pose_camera.data(); P.points = pts.data(); P.edges = edges.data();
+  P.cameras = cameras.data(); P.iterations = nIterations; P.robust = bRobust ? 1 : 0;
+  P.device = 0;                          // as LocalBundleAdjustment above: an agent's (or the server's) process sees its GPU as device 0
+  std::vector<float> oposes(poses.size()), opts(pts.size());
+  std::vector<uint8_t> included(pts_v.size() + 1);
+  ba_result R{};
+  R.poses = oposes.data(); R.points = opts.data(); R.point_included = included.data();
+  check(Ops::ba(P, pbStopFlag, R), "BundleAdjustment");
+  // ---- recover (:307-446)
+  const bool bDirect = nLoopKF == pMap->GetOriginKF()->mnId;                                  // :322,435
+  for (size_t i = 0; i < kfs.size(); i++) {
+    KeyFrameT* kf = kfs[i].kf;
+    if (bDirect) {
+      decltype(kf->GetPose()) T; make_mat(T, 4, 4, &oposes[16 * i]);
+      kf->SetPose(T, true);                                                                   // :324
+    } else {
+      make_mat(kf->mTcwGBA, 4, 4, &oposes[16 * i]);                                           // :345-347
+      kf->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  for (size_t j = 0; j < pts_v.size(); j++) {
+    if (!included[j]) continue;                                                               // vbNotIncludedMP (:289-293,421)
+    MapPointT* mp = vpMP[pts_v[j].idx];
+    if (bDirect) {
+      decltype(mp->GetWorldPos()) X; make_mat(X, 3, 1, &opts[3 * j]);
+      mp->SetWorldPos(X, true);                                                               // :437-438
+      mp->UpdateNormalAndDepth();
+    } else {
+      make_mat(mp->mPosGBA, 3, 1, &opts[3 * j]);                                              // :442-444
+      mp->mnBAGlobalForKF = nLoopKF;
+    }
+  }
+  return R.iters;
+}
+
+// void Optimizer::GlobalBundleAdjustemnt(Map* pMap, int nIterations, bool* pbStopFlag, bool bUseUniqueId, const unsigned long nLoopKF,
+// const bool bRobust), S/Optimizer.cc:42-47 (the reference's spelling)
+template <class Ops = GpuOps, class MapT>
+int GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = nullptr, bool bUseUniqueId = false, const unsigned long nLoopKF = 0,
+                           const bool bRobust = true) {
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  const auto vpMP = pMap->GetAllMapPoints();
+  return BundleAdjustment<Ops>(vpKFs, vpMP, nIterations, pbStopFlag, bUseUniqueId, nLoopKF, bRobust);
 }
 
 // int Optimizer::PoseOptimization(Frame *pFrame), S/Optimizer.cc:964-1278: the rectified-stereo / mono frames of every BASELINE

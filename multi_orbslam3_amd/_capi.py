@@ -135,6 +135,27 @@ class LbaResult(C.Structure):
                 ("trace_cap", C.c_int32), ("trace_len", C.c_int32)]
 
 
+class BaCamera(C.Structure):
+    """ba_camera: what one keyframe's edges read -- fx fy cx cy bf of the stereo edges, the camera model of the monocular ones."""
+    _fields_ = [("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float), ("model", Camera)]
+
+
+class BaProblem(C.Structure):
+    _fields_ = [("n_poses", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32), ("n_cameras", C.c_int32),
+                ("poses", C.c_void_p), ("pose_fixed", C.c_void_p), ("pose_camera", C.c_void_p), ("points", C.c_void_p),
+                ("edges", C.c_void_p), ("cameras", C.c_void_p), ("iterations", C.c_int32), ("robust", C.c_int32),
+                ("device", C.c_int32)]
+
+
+class BaResult(C.Structure):
+    _fields_ = [("poses", C.c_void_p), ("points", C.c_void_p), ("edge_chi2", C.c_void_p), ("edge_depth_pos", C.c_void_p),
+                ("point_included", C.c_void_p), ("status", C.c_int32), ("iters", C.c_int32), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double), ("trace", C.c_void_p), ("trace_cap", C.c_int32), ("trace_len", C.c_int32)]
+
+
+BA_MAX_FREE_POSES = 1365
+
+
 class PoseOptProblem(C.Structure):
     _fields_ = [("n", C.c_int32), ("Xw", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("ur", C.c_void_p),
                 ("inv_sigma2", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
@@ -319,6 +340,8 @@ EXPORTED_SYMBOLS = [
 # The initialisers (prefix orbi_): a list of its own, because tests/test_capi_cpu.py holds EXPORTED_SYMBOLS against the header's
 # declarations under the prefixes above only.  build() and load() treat both lists alike; tests/test_two_view_cpu.py holds this one.
 INITIALISER_SYMBOLS = ["orbi_two_view_resolve_draws", "orbi_two_view_reconstruct"]
+# The full bundle adjustment (prefix ba_), likewise a list of its own; tests/test_full_ba_cpu.py holds it against the header.
+FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solve_h", "ba_solve_hb", "ba_set_profiling", "ba_get_phase_ms"]
 
 _lib = None
 
@@ -373,7 +396,7 @@ def load():
     lib.orbx_frame_rgbd_wait.argtypes = [C.c_void_p, C.c_void_p]
     lib.orbx_depth_at_points.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

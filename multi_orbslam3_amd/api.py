@@ -887,6 +887,9 @@ class Optimizer:
         self.device = device
 
     def close(self):
+        if getattr(self, "_ba", None) is not None:
+            self._ba.close()
+            self._ba = None
         if getattr(self, "h", None):
             self.lib.lba_destroy(self.h)
             self.h = None
@@ -965,6 +968,58 @@ class Optimizer:
         fn = self.lib.lba_solve_hb if self._is_bool_flag(pbStopFlag) else self.lib.lba_solve_h
         capi.check(fn(self.h, C.byref(problem), sp, C.byref(out.c)), "lba_solve_h")
         return out
+
+    def BundleAdjustment(self, p, nIterations=None, pbStopFlag=None, bRobust=None, out=None):
+        """void Optimizer::BundleAdjustment(vpKFs, vpMP, nIterations, pbStopFlag, ..., bRobust) (S/Optimizer.cc:73-446), numerical
+        core.  p: views.ba_problem(...)[0]; nIterations / bRobust override the problem's fields when given (None: the problem's
+        own iterations / robust, which views.ba_problem sets to 10 / True by default, stay); pbStopFlag as in
+        LocalBundleAdjustment (np.bool_[1] = &mbStopGBA).  The workspace is created on first use and kept."""
+        if getattr(self, "_ba", None) is None:
+            self._ba = FullBA(self.device)
+        if nIterations is not None:
+            p.iterations = int(nIterations)
+        if bRobust is not None:
+            p.robust = int(bool(bRobust))
+        return self._ba.solve(p, pbStopFlag, out=out)
+
+
+class FullBA:
+    """Persistent workspace of Optimizer::BundleAdjustment (include/orbgpu.h: ba_create ... ba_solve_hb)."""
+
+    def __init__(self, device=0, cap_poses=0, cap_points=0, cap_edges=0):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        capi.check(self.lib.ba_create(device, int(cap_poses), int(cap_points), int(cap_edges), C.byref(self.h)), "ba_create")
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ba_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, problem, pbStopFlag=None, trace_cap=64, out=None):
+        if out is None:
+            out = views.BaOutput(problem.n_poses, problem.n_points, problem.n_edges, trace_cap)
+        else:
+            out.c.trace_len = 0
+        sp = None if pbStopFlag is None else C.c_void_p(pbStopFlag.ctypes.data)
+        fn = self.lib.ba_solve_hb if Optimizer._is_bool_flag(pbStopFlag) else self.lib.ba_solve_h
+        capi.check(fn(self.h, C.byref(problem), sp, C.byref(out.c)), "ba_solve_h")
+        return out
+
+    def set_profiling(self, on=True):
+        capi.check(self.lib.ba_set_profiling(self.h, int(bool(on))), "ba_set_profiling")
+
+    def phase_ms(self):
+        """Device time of the last solve: (structure build, linearisation, Schur complement, LDL^T, update + evaluation) in ms."""
+        ms = (C.c_double * 5)()
+        capi.check(self.lib.ba_get_phase_ms(self.h, ms), "ba_get_phase_ms")
+        return tuple(ms)
 
 
 class KeyFrameDatabase:

@@ -45,8 +45,10 @@ using namespace orbg;
 #include "ldlt_mfma.hpp"
 #include "ldlt_xcd.hpp"
 #include "se3.hpp"
+#include "lm_driver.hpp"
 
 using namespace orbg_se3;
+using namespace orbg_lm;
 
 namespace {
 
@@ -66,69 +68,7 @@ __device__ long long g_lba_prof[3][8 + 2 * 1020];
 #define LBA_PROF_PHASE(block, slot) do { } while (0)
 #endif
 
-__device__ inline void edge_error(const PoseQ& T, const double* X, const Cam& c, const lba_edge& e, double* err, double* Xc) {
-  double r[3];
-  quat_rotate(T.q, X, r);
-  Xc[0] = r[0] + T.t[0]; Xc[1] = r[1] + T.t[1]; Xc[2] = r[2] + T.t[2];
-  if (e.ur < 0) {
-    const double iz = 1.0 / Xc[2];
-    err[0] = (double)e.u - (c.fx * Xc[0] * iz + c.cx);
-    err[1] = (double)e.v - (c.fy * Xc[1] * iz + c.cy);
-    err[2] = 0;
-  } else {
-    const float invz = (float)(1.0 / Xc[2]);                 // cam_project: float invz (types_six_dof_expmap.cpp:191)
-    const double r0 = Xc[0] * invz * c.fx + c.cx;
-    const double r1 = Xc[1] * invz * c.fy + c.cy;
-    const double r2 = r0 - (double)(c.bf_f * invz);
-    err[0] = (double)e.u - r0; err[1] = (double)e.v - r1; err[2] = (double)e.ur - r2;
-  }
-}
-
-// The same for a problem that carries an orbg_camera_rig: stereo edges as above; monocular edges through mpCamera->project
-// (EdgeSE3ProjectXYZ::computeError, I/OptimizableTypes.h:99-104); the right camera's through mpCamera2 after (mTrl * T)
-// (EdgeSE3ProjectXYZToBody::computeError, :127-132).  Xc: the point in the frame of the camera that made the observation.
-__device__ inline void edge_error(const PoseQ& T, const double* X, const CamRig& g, const lba_edge& e, double* err, double* Xc) {
-  if (e.ur >= 0) { edge_error(T, X, g.c, e, err, Xc); return; }
-  double r[3], uv[2];
-  if (g.has_right && ur_is_right(e.ur)) {
-    PoseQ Trw;
-    se3_mul(g.Trl, T, &Trw);
-    quat_rotate(Trw.q, X, r);
-    Xc[0] = r[0] + Trw.t[0]; Xc[1] = r[1] + Trw.t[1]; Xc[2] = r[2] + Trw.t[2];
-    cam_project(g.right, Xc, uv);
-  } else {
-    quat_rotate(T.q, X, r);
-    Xc[0] = r[0] + T.t[0]; Xc[1] = r[1] + T.t[1]; Xc[2] = r[2] + T.t[2];
-    cam_project(g.left, Xc, uv);
-  }
-  err[0] = (double)e.u - uv[0]; err[1] = (double)e.v - uv[1]; err[2] = 0;
-}
-
-// isDepthPositive() of an edge: z of the point in the observing camera's frame (G/types/types_six_dof_expmap.h:163-167,
-// I/OptimizableTypes.h:106-110,134-138)
-__device__ inline bool edge_depth_positive(const PoseQ& T, const double* X, const Cam&, const lba_edge&) {
-  double rr[3];
-  quat_rotate(T.q, X, rr);
-  return rr[2] + T.t[2] > 0.0;
-}
-__device__ inline bool edge_depth_positive(const PoseQ& T, const double* X, const CamRig& g, const lba_edge& e) {
-  double rr[3];
-  if (g.has_right && ur_is_right(e.ur)) {
-    PoseQ Trw;
-    se3_mul(g.Trl, T, &Trw);
-    quat_rotate(Trw.q, X, rr);
-    return rr[2] + Trw.t[2] > 0.0;
-  }
-  quat_rotate(T.q, X, rr);
-  return rr[2] + T.t[2] > 0.0;
-}
-
-__device__ inline void huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
-  if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-  else { const double s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
-}
-
-struct Huber { double delta_mono, dsqr_mono, delta_stereo, dsqr_stereo; };
+#include "ba_edge.hpp"     // edge_error, edge_depth_positive, huber, edge_jacobians: shared with full_ba.hip
 
 // ---------------------------------------------------------------------------------------------- kernels
 
@@ -360,84 +300,6 @@ __global__ __launch_bounds__(256) void k_errors_export(int n_edge_blocks, int n_
 
 // per-edge blocks: EB[k*27 + ...] = Hpl (6x3, 18) | pointH upper (6) | pointB (3)
 constexpr int kEB = 27;
-
-// Jacobians of one edge (stereo: G/types/types_six_dof_expmap.cpp:228-274; mono: S/OptimizableTypes.cpp:139-160)
-__device__ inline void edge_jacobians(const PoseQ& T, double x, double y, double z, const Cam& c, float ur, double* A, double* B) {
-  const bool mono = ur < 0;
-  double R[9];
-  quat_to_R(T.q, R);
-  const double iz = 1.0 / z, iz2 = iz * iz;     // one division per edge; the reference divides term by term (<= 2 ulp apart)
-  if (mono) {
-    const double J[6] = {-(c.fx * iz), -0.0, c.fx * x * iz2, -0.0, -(c.fy * iz), c.fy * y * iz2};
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) A[3 * i + j] = J[3 * i] * R[j] + J[3 * i + 1] * R[3 + j] + J[3 * i + 2] * R[6 + j];
-    const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 6; j++) B[6 * i + j] = J[3 * i] * S[j] + J[3 * i + 1] * S[6 + j] + J[3 * i + 2] * S[12 + j];
-#pragma unroll
-    for (int j = 0; j < 3; j++) A[6 + j] = 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++) B[12 + j] = 0;
-  } else {
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-      A[j] = -c.fx * R[j] * iz + c.fx * x * R[6 + j] * iz2;
-      A[3 + j] = -c.fy * R[3 + j] * iz + c.fy * y * R[6 + j] * iz2;
-      A[6 + j] = A[j] - c.bf * R[6 + j] * iz2;
-    }
-    B[0] = x * y * iz2 * c.fx; B[1] = -(1 + (x * x * iz2)) * c.fx; B[2] = y * iz * c.fx; B[3] = -iz * c.fx; B[4] = 0; B[5] = x * iz2 * c.fx;
-    B[6] = (1 + y * y * iz2) * c.fy; B[7] = -x * y * iz2 * c.fy; B[8] = -x * iz * c.fy; B[9] = 0; B[10] = -iz * c.fy; B[11] = y * iz2 * c.fy;
-    B[12] = B[0] - c.bf * y * iz2; B[13] = B[1] + c.bf * x * iz2; B[14] = B[2]; B[15] = B[3]; B[16] = 0; B[17] = B[5] - c.bf * iz2;
-  }
-}
-
-// With a camera rig: (x, y, z) = T.map(X) is the point in the LEFT camera's (body) frame for every kind of edge.
-//   monocular  S/OptimizableTypes.cpp:139-160   Xi = -projectJac(X_l) * R(T),                  Xj = -projectJac(X_l) * SE3deriv(X_l)
-//   right cam  S/OptimizableTypes.cpp:192-214   Xi = -projectJac(X_r) * R(mTrl * T),  Xj = -projectJac(X_r) * R(mTrl) * SE3deriv(X_l),
-//              X_r = mTrl.map(X_l)
-__device__ inline void edge_jacobians(const PoseQ& T, double x, double y, double z, const CamRig& g, float ur, double* A, double* B) {
-  if (ur >= 0) { edge_jacobians(T, x, y, z, g.c, ur, A, B); return; }
-  const double Xl[3] = {x, y, z};
-  double R[9], J[6], M[6];
-  if (g.has_right && ur_is_right(ur)) {
-    double rr[3], Xr[3], Rrl[9];
-    quat_rotate(g.Trl.q, Xl, rr);
-    Xr[0] = rr[0] + g.Trl.t[0]; Xr[1] = rr[1] + g.Trl.t[1]; Xr[2] = rr[2] + g.Trl.t[2];
-    cam_project_jac(g.right, Xr, J);
-#pragma unroll
-    for (int i = 0; i < 6; i++) J[i] = -J[i];
-    PoseQ Trw;
-    se3_mul(g.Trl, T, &Trw);
-    quat_to_R(Trw.q, R);
-    quat_to_R(g.Trl.q, Rrl);
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++) M[3 * i + j] = J[3 * i] * Rrl[j] + J[3 * i + 1] * Rrl[3 + j] + J[3 * i + 2] * Rrl[6 + j];
-  } else {
-    cam_project_jac(g.left, Xl, J);
-#pragma unroll
-    for (int i = 0; i < 6; i++) { J[i] = -J[i]; M[i] = J[i]; }
-    quat_to_R(T.q, R);
-  }
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) A[3 * i + j] = J[3 * i] * R[j] + J[3 * i + 1] * R[3 + j] + J[3 * i + 2] * R[6 + j];
-  const double S[18] = {0, z, -y, 1, 0, 0, -z, 0, x, 0, 1, 0, y, -x, 0, 0, 0, 1};
-#pragma unroll
-  for (int i = 0; i < 2; i++)
-#pragma unroll
-    for (int j = 0; j < 6; j++) B[6 * i + j] = M[3 * i] * S[j] + M[3 * i + 1] * S[6 + j] + M[3 * i + 2] * S[12 + j];
-#pragma unroll
-  for (int j = 0; j < 3; j++) A[6 + j] = 0;
-#pragma unroll
-  for (int j = 0; j < 6; j++) B[12 + j] = 0;
-}
 
 // thread per edge; the 256 x 27 block of results is staged in LDS and written as ONE contiguous, coalesced chunk
 // FUSED: the residuals are computed here (and stored, with their chi2 and the workgroup's robust partial sum) instead of being
@@ -1269,150 +1131,7 @@ __global__ __launch_bounds__(kSchurThreads) void k_schur(int nP, const int* __re
   LBA_PROF_END();
 }
 
-// ---- Blocked LDL^T + solve over MANY workgroups, for windows beyond the matrix-core kernels (more than 50 free poses:
-// the matrix-core kernels hold <= 19 tile rows in one CU's registers, the row-pair kernel <= 1344 blocks).  Right-looking,
-// 16-column blocks, dense row-major S in global memory (L2-resident), two launches per block column:
-//   k_wide_panel(kb):  every workgroup factors the 16 x 16 diagonal block itself (no hand-over between workgroups).  The
-//                      block is READ from its diagonal and upper triangle only and workgroup 0 WRITES the strictly lower
-//                      triangle only (L_kk for the back-substitution), so a workgroup that is dispatched after workgroup 0
-//                      has finished still factors the unfactored block: no location is input and output of one launch;
-//                      workgroup 0 also forward-substitutes the right-hand side's block, workgroup g >= 1 turns
-//                      row block kb + g into L = A L_kk^-T D^-1 (in place) and W = L D (kept in the mirrored upper block);
-//   k_wide_update(kb): A_ij -= W_ik L_jk^T for every trailing block, and the right-hand side as one more row;
-// then k_wide_back: x = L^-T z in one workgroup.  Same failure rule as k_ldlt: a zero / non-finite pivot clears the flag.
-__global__ __launch_bounds__(256) void k_wide_panel(int n, int kb, double* S, const double* __restrict__ b, double* yw, double* z,
-                                                    int* __restrict__ ok_flag) {
-  __shared__ double Lk[16][17];
-  __shared__ double Aw[16][17];
-  const int tid = threadIdx.x, r = tid >> 4, c = tid & 15;
-  const int k0 = 16 * kb;
-  {
-    const int gr = k0 + r, gc = k0 + c;
-    const int lo = gr < gc ? gr : gc, hi = gr < gc ? gc : gr;
-    Lk[r][c] = (gr < n && gc < n) ? S[(size_t)lo * n + hi] : (r == c ? 1.0 : 0.0);
-  }
-  if (blockIdx.x == 0 && kb == 0 && tid == 0) *ok_flag = 1;
-  __syncthreads();
-  bool bad = false;
-  for (int j = 0; j < 16; j++) {
-    const double d = Lk[j][j];
-    if (d == 0.0 || !(d == d) || fabs(d) == INFINITY) bad = true;
-    const bool below = r > j, upd = below && c > j && c <= r;
-    double v = 0.0, wc = 0.0;
-    if (below) v = Lk[r][j];
-    if (upd) wc = Lk[c][j];
-    __syncthreads();
-    const double l = v / d;
-    if (upd) Lk[r][c] -= l * wc;
-    if (below && c == j) Lk[r][j] = l;
-    __syncthreads();
-  }
-  if (blockIdx.x == 0) {
-    if (bad && tid == 0) *ok_flag = 0;
-    const int gr = k0 + r, gc = k0 + c;
-    if (gr < n && gc < n && c < r) S[(size_t)gr * n + gc] = Lk[r][c];
-    // the right-hand side as a one-row block: w = b_k^T L_kk^-T (kept for the trailing update), z = w / D
-    const double* src = kb == 0 ? b : yw;
-    Aw[r][c] = (r == 0 && k0 + c < n) ? src[k0 + c] : 0.0;
-    __syncthreads();
-    for (int m = 0; m < 15; m++) {
-      if (r == 0 && c > m) Aw[0][c] -= Aw[0][m] * Lk[c][m];
-      __syncthreads();
-    }
-    if (r == 0 && k0 + c < n) { const double w = Aw[0][c]; yw[k0 + c] = w; z[k0 + c] = w / Lk[c][c]; }
-    return;
-  }
-  const int i0 = 16 * (kb + (int)blockIdx.x);
-  Aw[r][c] = i0 + r < n ? S[(size_t)(i0 + r) * n + k0 + c] : 0.0;
-  __syncthreads();
-  for (int m = 0; m < 15; m++) {
-    if (c > m) Aw[r][c] -= Aw[r][m] * Lk[c][m];
-    __syncthreads();
-  }
-  if (i0 + r < n) {
-    const double w = Aw[r][c];
-    S[(size_t)(i0 + r) * n + k0 + c] = w / Lk[c][c];
-    S[(size_t)(k0 + c) * n + i0 + r] = w;
-  }
-}
-
-// grid (m, m + 1), m = trailing row blocks: block (jj, ii) updates tile (kb+1+ii, kb+1+jj), ii >= jj; row ii == m is the right-hand side
-__global__ __launch_bounds__(256) void k_wide_update(int n, int kb, double* S, const double* __restrict__ b, double* yw) {
-  const int m_blocks = gridDim.x, jj = blockIdx.x, ii = blockIdx.y;
-  if (ii < m_blocks && ii < jj) return;
-  __shared__ double Wt[16][17];
-  __shared__ double Lj[16][17];
-  const int tid = threadIdx.x, r = tid >> 4, c = tid & 15;
-  const int k0 = 16 * kb, j0 = 16 * (kb + 1 + jj);
-  Lj[r][c] = j0 + r < n ? S[(size_t)(j0 + r) * n + k0 + c] : 0.0;               // L_jk[r][c]
-  if (ii == m_blocks) {
-    if (r == 0) Wt[0][c] = yw[k0 + c];
-    __syncthreads();
-    if (r == 0 && j0 + c < n) {
-      double acc = 0.0;
-      for (int m = 0; m < 16; m++) acc += Wt[0][m] * Lj[c][m];
-      yw[j0 + c] = (kb == 0 ? b[j0 + c] : yw[j0 + c]) - acc;
-    }
-    return;
-  }
-  const int i0 = 16 * (kb + 1 + ii);
-  Wt[c][r] = i0 + c < n ? S[(size_t)(k0 + r) * n + i0 + c] : 0.0;               // W_ik[c][r], read along the mirrored block's rows
-  __syncthreads();
-  if (i0 + r < n && j0 + c < n) {
-    double acc = 0.0;
-    for (int m = 0; m < 16; m++) acc += Wt[r][m] * Lj[c][m];
-    S[(size_t)(i0 + r) * n + j0 + c] -= acc;
-  }
-}
-
-__global__ __launch_bounds__(1024) void k_wide_back(int n, const double* __restrict__ S, const double* __restrict__ z, double* __restrict__ x,
-                                                    const int* __restrict__ ok_flag) {
-  extern __shared__ double xs[];
-  if (*ok_flag == 0) return;
-  const int tid = threadIdx.x, T = (n + 15) / 16;
-  for (int i = tid; i < n; i += 1024) xs[i] = z[i];
-  __syncthreads();
-  for (int kb = T - 1; kb >= 0; kb--) {
-    const int k0 = 16 * kb, w = min(16, n - k0);
-    if (tid < 64) {
-      // the diagonal block: lane i < 16 holds x_i and column i of L_kk; x_j goes round by a lane read, 15 steps in registers
-      const int i = tid & 15;
-      double lcol[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) lcol[j] = (j > i && j < w) ? S[(size_t)(k0 + j) * n + k0 + i] : 0.0;
-      double xv = i < w ? xs[k0 + i] : 0.0;
-#pragma unroll
-      for (int j = 15; j > 0; j--) {
-        const double xj = __shfl(xv, j, 16);
-        xv -= lcol[j] * xj;
-      }
-      if (tid < w) xs[k0 + tid] = xv;
-    }
-    __syncthreads();
-    for (int i = tid; i < k0; i += 1024) {
-      double acc = 0.0;
-      for (int cc = 0; cc < w; cc++) acc += S[(size_t)(k0 + cc) * n + i] * xs[k0 + cc];
-      xs[i] -= acc;
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < n; i += 1024) x[i] = xs[i];
-}
-
-constexpr int kWideMaxUnknowns = 8192;   // k_wide_back keeps x in LDS: n * 8 bytes <= 64 KB (1365 free poses)
-static hipError_t launch_ldlt_wide(int n, double* S, const double* b, double* x, int* ok, double* scratch, hipStream_t st) {
-  if (n > kWideMaxUnknowns) return hipErrorInvalidValue;
-  const int T = (n + 15) / 16;
-  double* yw = scratch;
-  double* z = scratch + n;
-  for (int kb = 0; kb < T; kb++) {
-    hipLaunchKernelGGL(k_wide_panel, dim3(T - kb), dim3(256), 0, st, n, kb, S, b, yw, z, ok);
-    const int m = T - kb - 1;
-    if (m > 0) hipLaunchKernelGGL(k_wide_update, dim3(m, m + 1), dim3(256), 0, st, n, kb, S, b, yw);
-  }
-  hipLaunchKernelGGL(k_wide_back, dim3(1), dim3(1024), (size_t)n * sizeof(double), st, n, S, z, x, ok);
-  return hipGetLastError();
-}
+#include "ldlt_wide.hpp"   // k_wide_panel / k_wide_update / k_wide_back, launch_ldlt_wide: shared with full_ba.hip
 
 // trial state = oplus(current, x): poses exp(x_p) * T; points X + x_l with the landmark back-substitution
 // x_l = Dinv_l (bl_l - sum_i Hpl_il^T x_i) folded in (x_l is also stored for computeScale)
@@ -1591,12 +1310,6 @@ __global__ __launch_bounds__(256) void k_finish_items(int n_partial, const doubl
 
 // ---------------------------------------------------------------------------------------------- handle
 
-// The abort flag as the caller owns it: the C-ABI's int32 (with its deterministic test forms) or the reference's own
-// one-byte bool (LocalMapping::mbAbortBA behind Optimizer::LocalBundleAdjustment's bool* pbStopFlag, S/LocalMapping.cc:381-386)
-struct StopRef {
-  const volatile int32_t* i32 = nullptr;
-  const volatile uint8_t* u8 = nullptr;
-};
 // The one switch of the solve (read ONCE, when the handle is created -- the solve path itself never calls getenv):
 // ORBG_LDLT_WIDE=1 sends every window to the many-workgroup blocked LDL^T (k_wide_*: the solver of windows beyond 50 free poses) so
 // that tests can run it on small problems.  Round 5 removed the measured-slower variants of rounds 1-4 (vector-ALU LDL^T kernels,
@@ -1777,20 +1490,6 @@ static int lba_solve_impl(lba_handle* h, const lba_problem* p, StopRef stop_ref,
 
 // ---------------------------------------------------------------------------------------------- one solve
 
-// g2o's termination test: > 0 stops (the reference's bool); < 0 stops once that many LM trials have been evaluated (deterministic
-// test hook, orbgpu.h); INT32_MIN is raised right after the check that precedes optimize() (the -k form with k = 0)
-struct StopCheck {
-  StopRef ref;
-  int trials_done = 0;
-  bool past_precheck = false;
-  bool operator()() const {
-    if (ref.u8) return *ref.u8 != 0;
-    if (!ref.i32) return false;
-    const int v = *ref.i32;
-    if (v == INT32_MIN) return past_precheck;
-    return v > 0 || (v < 0 && trials_done >= -v);
-  }
-};
 
 // The arrays of the upload arena, at host or at device addresses
 struct Arena {
@@ -1841,15 +1540,13 @@ struct LbaStructure {
 //                       first trial of the next iteration if that trial is the very next one and its iteration took that set
 //   exp_version/exp_buf k_export of state buffer exp_buf ran (completion word posted) behind trial exp_version: the final export
 //                       if no later trial ran and exp_buf became the current estimate
-struct LmState {
+struct LmState : LmScalars {       // lambda, ni, currentChi, nBad: lm_driver.hpp
   int version = 0;
   int cur = 0;                     // state buffer of the current estimate: a trial goes to (cur + 1) % 3, an accepted one becomes current
   int ls = 0;                      // linearisation set of the current iteration
   bool err_valid = false;          // d_err / d_chi2 hold the residuals of the current estimate
   bool spec_ready = false;
   int fin_version = -1, solve_version = -1, exp_version = -1, exp_buf = -1;
-  double lambda = -1, ni = 2, currentChi = 0;
-  int nBad = 0;
   bool first_chi = true;           // r->chi2_initial not yet set
   bool last_round = false;
 };
@@ -2459,7 +2156,7 @@ struct LbaRun : LbaStructure {
         } else {
           if ((rc = finish_record(m.ls, 0.0, 0, 1, false))) return rc;
           m.currentChi = h->rec.h->chi2;
-          m.lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
+          m.lambda = lm_lambda_init(p->lambda_init, h->rec.h->maxdiag);
         }
         m.ni = 2; m.nBad = 0;
       }
@@ -2477,47 +2174,31 @@ struct LbaRun : LbaStructure {
         if (lambda_on_device) {
           // the round's initial chi2 / lambda, as the device computed them before this first trial
           m.currentChi = h->rec.h->chi2_init;
-          m.lambda = p->lambda_init > 0 ? p->lambda_init : 1e-5 * h->rec.h->maxdiag;
+          m.lambda = lm_lambda_init(p->lambda_init, h->rec.h->maxdiag);
           lambda_on_device = false;
           if (m.first_chi) { r->chi2_initial = m.currentChi; m.first_chi = false; }
           iniChi = m.currentChi;
         }
-        const bool ok2 = h->rec.h->ok != 0;
-        double tempChi = h->rec.h->chi2;
-        if (!ok2) tempChi = std::numeric_limits<double>::max();
-        rho = m.currentChi - tempChi;
-        double scale = h->rec.h->scale;
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          const double c3 = 2 * rho - 1;               // (2 rho - 1)^3 as two multiplications: publish_trial_record does the same
-          double alpha = 1. - c3 * c3 * c3;            // arithmetic on the device for the speculative next solve
-          alpha = std::min(alpha, 2. / 3.);
-          const double scaleFactor = std::max(1. / 3., alpha);
-          m.lambda *= scaleFactor;
-          m.ni = 2;
-          m.currentChi = tempChi;
+        bool accepted;
+        rho = lm_trial_verdict(m, h->rec.h->ok != 0, h->rec.h->chi2, h->rec.h->scale, &accepted);
+        if (accepted) {
           m.cur = trial;                              // discardTop(): keep the trial state
           m.err_valid = true;
           m.spec_ready = speculated;
         } else {
-          m.lambda *= m.ni;
-          m.ni *= 2;                                  // pop(): current buffer untouched
-          m.err_valid = false;                        // d_err now belongs to the rejected trial
+          m.err_valid = false;                        // pop(): current buffer untouched; d_err now belongs to the rejected trial
           m.spec_ready = false;
         }
         qmax++;
         stop.trials_done++;
-      } while (rho < 0 && qmax < 10 && !stop());
+      } while (lm_try_again(rho, qmax < 10, stop()));
       done++;
       r->chi2_final = m.currentChi;
       if (r->trace && r->trace_len < r->trace_cap) {
         r->trace[3 * r->trace_len] = m.lambda; r->trace[3 * r->trace_len + 1] = m.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
         r->trace_len++;
       }
-      if (qmax == 10 || rho == 0) { ok = false; continue; }
-      if ((iniChi - m.currentChi) * 1e3 < iniChi) m.nBad++; else m.nBad = 0;
-      if (m.nBad >= 3) ok = false;
+      ok = lm_iteration_continues(m, qmax == 10, rho, iniChi);
     }
     *done_out = done;
     return ORBG_OK;

@@ -265,6 +265,96 @@ def make_lba_problem(n_free=20, n_fixed=10, n_points=2000, seed=SEED_LBA, width=
                 poses_true=poses_true, points_true=points_true)
 
 
+# ---------------------------------------------------------------- full BA problems
+SEED_BA = 0xBA11
+
+
+def make_ba_problem(n_free=5, n_fixed=1, n_points=90, n_cameras=2, mono_frac=0.3, outlier_frac=0.0, seed=SEED_BA, width=640, height=480,
+                    min_obs=2, max_obs=4, kb8_camera=None, pixel_sigma=1.0, sigma_rot_deg=0.3, sigma_t=0.01, sigma_point=0.02):
+    """Synthetic Optimizer::BundleAdjustment problem: make_lba_problem's trajectory and observation pattern, with the keyframes
+    spread round-robin over n_cameras intrinsics.  Camera c scales camera 0's focal lengths and bf by 1.15 ** c (two cameras differ
+    by at least 10 % in focal length and in bf) and moves its principal point by 7 c pixels.  kb8_camera: index of a camera that is a
+    KannalaBrandt8 model (its keyframes then make monocular observations only).  pixel_sigma scales the pixel noise, sigma_rot_deg /
+    sigma_t / sigma_point the error of the initial estimates.  Pose order: fixed poses first."""
+    rng = np.random.RandomState(seed & 0x7FFFFFFF)
+    cam0 = camera_for(width, height)
+    cams = []
+    for c in range(n_cameras):
+        f = 1.15 ** c
+        five = (float(cam0["fx"]) * f, float(cam0["fy"]) * f, float(cam0["cx"]) + 7.0 * c, float(cam0["cy"]) - 7.0 * c, float(cam0["bf"]) * f)
+        five = tuple(float(np.float32(x)) for x in five)
+        if kb8_camera is not None and c == kb8_camera:
+            model = (capi.CAM_KANNALA_BRANDT8, five[0] * 0.6, five[1] * 0.6, five[2], five[3], -0.013, 0.021, -0.009, 0.0015)
+            cams.append(five + (tuple(float(np.float32(x)) for x in model),))
+        else:
+            cams.append(five + (None,))
+    P = n_free + n_fixed
+    pose_camera = (np.arange(P) % n_cameras).astype(np.int32)
+    poses_true = np.zeros((P, 4, 4))
+    for k in range(P):
+        R = _rot(0.02 * np.sin(0.3 * k), 0.03 * np.sin(0.2 * k + 1.0), 0.01 * np.sin(0.5 * k))
+        Cc = np.array([0.12 * k, 0.02 * np.sin(0.4 * k), 0.03 * np.cos(0.3 * k)])
+        poses_true[k] = np.eye(4)
+        poses_true[k, :3, :3] = R
+        poses_true[k, :3, 3] = -R @ Cc
+    sc = np.ones(8, np.float32)
+    for i in range(1, 8):
+        sc[i] = np.float32(sc[i - 1] * np.float32(1.2))
+    inv_s2 = (np.float32(1.0) / (sc * sc)).astype(np.float32)
+    level_p = np.array([217, 181, 151, 126, 105, 87, 73, 60], np.float64)
+    level_p /= level_p.sum()
+
+    def project(c, Xc):
+        five, model = cams[c][:5], cams[c][5]
+        if model is not None:
+            return kb8_project(model, Xc)
+        return np.array([five[0] * Xc[0] / Xc[2] + five[2], five[1] * Xc[1] / Xc[2] + five[3]])
+
+    points_true = np.zeros((n_points, 3))
+    edges = []
+    for j in range(n_points):
+        nobs = rng.randint(min_obs, max_obs + 1)
+        k0 = rng.randint(0, max(P - nobs, 0) + 1)
+        kc = min(k0 + nobs // 2, P - 1)
+        z = rng.uniform(2.0, 9.0)
+        u = rng.uniform(120, width - 120); v = rng.uniform(100, height - 100)
+        f0 = cams[0]
+        Pc = np.array([(u - f0[2]) * z / f0[0], (v - f0[3]) * z / f0[1], z])
+        Rc, tc = poses_true[kc, :3, :3], poses_true[kc, :3, 3]
+        Xw = Rc.T @ (Pc - tc)
+        points_true[j] = Xw
+        for k in range(k0, min(k0 + nobs, P)):
+            c = int(pose_camera[k])
+            Xc = poses_true[k, :3, :3] @ Xw + poses_true[k, :3, 3]
+            if Xc[2] < 0.3:
+                continue
+            uv = project(c, Xc)
+            if not (0 <= uv[0] < width and 0 <= uv[1] < height):
+                continue
+            octave = rng.choice(8, p=level_p)
+            s = float(sc[octave]) * pixel_sigma
+            nu, nv, nr = rng.randn(3) * s
+            ur = uv[0] - cams[c][4] / Xc[2] + nr
+            if rng.rand() < outlier_frac:
+                nu += rng.choice([-20, 20]); nv += rng.choice([-20, 20])
+            is_mono = rng.rand() < mono_frac or cams[c][5] is not None or ur < 0      # (no right-image match left of the image: mvuRight = -1)
+            edges.append((k, j, uv[0] + nu, uv[1] + nv, -1.0 if is_mono else ur, inv_s2[octave]))
+    E = np.zeros(len(edges), dtype=capi.EDGE_DTYPE)
+    for i, e in enumerate(edges):
+        E[i] = (e[0], e[1], np.float32(e[2]), np.float32(e[3]), np.float32(e[4]), e[5])
+    poses0 = np.zeros((P, 16), np.float32)
+    fixed = np.zeros(P, np.uint8)
+    fixed[:n_fixed] = 1
+    for k in range(P):
+        T = poses_true[k].copy()
+        if not fixed[k]:
+            T = perturb_pose(T, rng, sigma_rot_deg=sigma_rot_deg, sigma_t=sigma_t)
+        poses0[k] = T.astype(np.float32).reshape(16)
+    points0 = (points_true + rng.randn(n_points, 3) * sigma_point).astype(np.float32)
+    return dict(poses=poses0, pose_fixed=fixed, pose_camera=pose_camera, points=points0, edges=E, cameras=cams,
+                poses_true=poses_true, points_true=points_true)
+
+
 def make_pose_opt_problem(n=500, seed=0xF00D, width=640, height=480, outlier_frac=0.1, mono_frac=0.2, sigma_rot_deg=0.5,
                           sigma_t=0.02):
     """Correspondences of one frame for Optimizer::PoseOptimization: points in front of a camera, observations with

@@ -184,6 +184,67 @@ class LbaOutput:
         return self.trace[: self.c.trace_len].copy()
 
 
+def ba_cameras(cameras):
+    """ba_camera array from a list of dicts / tuples: (fx, fy, cx, cy, bf) for a pinhole keyframe, or
+    (fx, fy, cx, cy, bf, model) with model = (model id, fx, fy, cx, cy[, k1..k4]) as camera_rig takes it."""
+    arr = (capi.BaCamera * max(len(cameras), 1))()
+    for i, cam in enumerate(cameras):
+        five = [float(np.float32(c)) for c in cam[:5]]
+        arr[i].fx, arr[i].fy, arr[i].cx, arr[i].cy, arr[i].bf = five
+        model = cam[5] if len(cam) > 5 and cam[5] is not None else (capi.CAM_PINHOLE,) + tuple(five[:4])
+        arr[i].model = camera_rig(model).left
+    return arr
+
+
+def ba_problem(poses, pose_fixed, pose_camera, points, edges, cameras, iterations=10, robust=True, device=0):
+    """Optimizer::BundleAdjustment's inputs (include/orbgpu.h: ba_problem).  poses: (P,16) or (P,4,4) float32; pose_camera: (P,)
+    indices into cameras; edges: structured EDGE_DTYPE, per point its observations; cameras: see ba_cameras."""
+    poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float32).reshape(-1, 16))
+    pose_fixed = np.ascontiguousarray(pose_fixed, dtype=np.uint8)
+    pose_camera = np.ascontiguousarray(pose_camera, dtype=np.int32)
+    points = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
+    edges = np.ascontiguousarray(edges, dtype=capi.EDGE_DTYPE)
+    cams = cameras if isinstance(cameras, C.Array) else ba_cameras(cameras)
+    p = capi.BaProblem()
+    p.n_poses, p.n_points, p.n_edges, p.n_cameras = len(poses), len(points), len(edges), len(cameras)
+    p.poses, p.pose_fixed, p.pose_camera, p.points, p.edges = [capi.ptr(a) for a in (poses, pose_fixed, pose_camera, points, edges)]
+    p.cameras = C.cast(cams, C.c_void_p)
+    p.iterations, p.robust, p.device = int(iterations), int(bool(robust)), int(device)
+    return p, [poses, pose_fixed, pose_camera, points, edges, cams]
+
+
+class BaOutput:
+    """Owns the result arrays of one full-BA call."""
+
+    def __init__(self, n_poses, n_points, n_edges, trace_cap=64):
+        self.poses = np.zeros((n_poses, 16), dtype=np.float32)
+        self.points = np.zeros((n_points, 3), dtype=np.float32)
+        self.edge_chi2 = np.zeros(n_edges, dtype=np.float64)
+        self.edge_depth_pos = np.zeros(n_edges, dtype=np.uint8)
+        self.point_included = np.zeros(n_points, dtype=np.uint8)
+        self.trace = np.zeros((trace_cap, 3), dtype=np.float64)
+        r = capi.BaResult()
+        r.poses, r.points = capi.ptr(self.poses), capi.ptr(self.points)
+        r.edge_chi2, r.edge_depth_pos, r.point_included = capi.ptr(self.edge_chi2), capi.ptr(self.edge_depth_pos), capi.ptr(self.point_included)
+        r.trace, r.trace_cap, r.trace_len = capi.ptr(self.trace), trace_cap, 0
+        self.c = r
+
+    @property
+    def status(self):
+        return self.c.status
+
+    @property
+    def iters(self):
+        return self.c.iters
+
+    @property
+    def chi2(self):
+        return (self.c.chi2_initial, self.c.chi2_final)
+
+    def trace_rows(self):
+        return self.trace[: self.c.trace_len].copy()
+
+
 def pose_opt_problem(Xw, u, v, ur, inv_sigma2, cam, Tcw, device=0, rig=None):
     """cam = (fx, fy, cx, cy, bf); Tcw = pFrame->mTcw (4x4); rig: camera_rig(...) or None."""
     arrs = [_c(np.asarray(Xw, np.float32).reshape(-1, 3), np.float32), _c(u, np.float32), _c(v, np.float32), _c(ur, np.float32),

@@ -1,0 +1,148 @@
+"""tests/full_ba_model.py, the float64 restatement of Optimizer::BundleAdjustment that the GPU tests hold the product against, pinned
+on the CPU: against the oracle's local BA, robust against non-robust, the conditioning of every problem the GPU tests use, the
+effect of per-keyframe cameras.  Also what ba_solve answers without a device: its refusals and the solves that run no iteration."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import full_ba_cases as fc
+import full_ba_model as fm
+from multi_orbslam3_amd import _capi as capi
+from multi_orbslam3_amd import synth, views
+from oracle import binding as ob
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# chi2 and lambda of the trace, model against oracle and product against model: the project's GPU-versus-oracle bound.  The model
+# meets it against the oracle (largest relative difference measured over the one-camera problems below: 2.6e-14, printed by the test).
+TRACE_RTOL = 1e-9
+
+
+def _ba_view(pr, iterations, robust, pose_camera=None):
+    return views.ba_problem(pr["poses"], pr["pose_fixed"], pr["pose_camera"] if pose_camera is None else pose_camera, pr["points"],
+                            pr["edges"], pr["cameras"], iterations=iterations, robust=robust)
+
+
+def test_header_declares_the_full_ba_symbols():
+    hdr = open(os.path.join(ROOT, "include", "orbgpu.h")).read()
+    declared = set(re.findall(r"^int\s+(ba_\w+)\s*\(", hdr, flags=re.M))
+    assert declared == set(capi.FULL_BA_SYMBOLS), declared ^ set(capi.FULL_BA_SYMBOLS)
+    lib = capi.load()
+    for s in declared:
+        assert hasattr(lib, s), s
+    assert C.sizeof(capi.BaCamera) == 20 + C.sizeof(capi.Camera)
+
+
+@pytest.mark.parametrize("seed", [0xBA04, 0xBA14])
+def test_trace_equals_the_oracles_first_round(seed):
+    args = dict(fc.CASES["one_camera"][0], seed=seed)
+    pr = synth.make_ba_problem(**args)
+    m = fm.solve(pr, 5, True)
+    p, keep = views.lba_problem(pr["poses"], pr["pose_fixed"], pr["points"], pr["edges"], pr["cameras"][0][:5], its=(5, 10))
+    o = ob.lba_solve(p)
+    rows = o.trace_rows()[: o.iters[0]]
+    assert m.iters == o.iters[0] == len(m.trace)
+    assert np.array_equal(m.trace[:, 2], rows[:, 2])
+    rel = np.abs(m.trace[:, :2] - rows[:, :2]) / np.abs(rows[:, :2])
+    print("model against oracle, largest relative difference of lambda / chi2: %.3g" % rel.max())
+    assert rel.max() <= TRACE_RTOL
+    assert abs(m.chi2_initial - o.chi2[0]) <= TRACE_RTOL * o.chi2[0]
+
+
+def test_robust_equals_non_robust_below_the_huber_threshold_and_differs_above():
+    args = dict(fc.CASES["one_camera"][0], mono_frac=0.3, outlier_frac=0.0, pixel_sigma=0.3, sigma_rot_deg=0.01, sigma_t=0.0005, sigma_point=0.002)
+    pr = synth.make_ba_problem(**args)
+    a, b = fm.solve(pr, 4, True), fm.solve(pr, 4, False)
+    # noise only, and little of it: no edge's chi2 reaches the lower (monocular) Huber threshold in any evaluation of either solve
+    assert 0 < a.max_edge_chi2 < 5.99 and 0 < b.max_edge_chi2 < 5.99
+    assert np.array_equal(a.trace, b.trace) and np.array_equal(a.poses, b.poses) and np.array_equal(a.points, b.points)
+    pr = synth.make_ba_problem(**dict(fc.CASES["one_camera"][0], mono_frac=0.3, outlier_frac=0.1))
+    a, b = fm.solve(pr, 4, True), fm.solve(pr, 4, False)
+    assert not np.array_equal(a.trace, b.trace)
+    assert np.abs(a.poses - b.poses).max() > 1e-4
+
+
+@pytest.mark.parametrize("name", sorted(fc.CASES))
+def test_every_problem_of_the_gpu_tests_is_well_conditioned(name):
+    a, b = fc.model(name), fc.model(name, True)
+    assert a.iters == b.iters and np.array_equal(a.trace[:, 2], b.trace[:, 2])
+    assert np.abs(a.poses64 - b.poses64).max() <= 1e-6
+    assert np.abs(a.points.astype(np.float64) - b.points).max() <= 1e-6
+    assert min(a.min_abs_rho, b.min_abs_rho) > 1e-6, (a.min_abs_rho, b.min_abs_rho)
+
+
+def test_float_angles_of_the_fisheye_projection_bound_the_kb8_case():
+    """Where the bounds of the KannalaBrandt8 case come from (tests/full_ba_cases.py): the model solved with theta and psi of
+    KannalaBrandt8::project taken as the double atan2 rounded to float -- what the device computes -- and moved by one float32 ulp,
+    against the model over the oracle's atan2f.  The GPU test's bounds are ten times the largest change measured here; this test
+    prints the figures and fails if a change outgrows a tenth of its bound."""
+    base = fc.model("kb8_pinhole")
+    worst_chi2 = worst_edge = worst_lambda = 0.0
+    for form in fc.KB8_ANGLE_FORMS:
+        m = fc.model("kb8_pinhole", False, None, form)
+        assert m.iters == base.iters and np.array_equal(m.trace[:, 2], base.trace[:, 2])
+        assert 0 < m.max_kb8_residual_shift < 1e-4                                   # px: the angles did move, by last bits
+        rel = np.abs(m.trace[:, :2] - base.trace[:, :2]) / np.abs(base.trace[:, :2])
+        chi2 = max(rel[:, 1].max(), abs(m.chi2_initial - base.chi2_initial) / base.chi2_initial)
+        edge = np.abs(m.edge_chi2 - base.edge_chi2).max()
+        print("%s: chi2 %.3g lambda %.3g edge chi2 %.3g poses %.3g points %.3g" % (form, chi2, rel[:, 0].max(), edge,
+              np.abs(m.poses64 - base.poses64).max(), np.abs(m.points.astype(np.float64) - base.points).max()))
+        worst_chi2, worst_edge, worst_lambda = max(worst_chi2, chi2), max(worst_edge, edge), max(worst_lambda, rel[:, 0].max())
+        assert np.abs(m.poses64 - base.poses64).max() <= 1e-5 and np.abs(m.points.astype(np.float64) - base.points).max() <= 1e-5
+    assert worst_lambda <= TRACE_RTOL / 10
+    assert worst_chi2 <= fc.KB8_CHI2_RTOL / 10 * 1.0001 and worst_edge <= fc.KB8_EDGE_CHI2_ATOL / 10 * 1.0001
+
+
+def test_per_keyframe_cameras_matter():
+    pr = fc.problem("loop_closing")
+    a = fc.model("loop_closing")
+    b = fm.solve(pr, 10, False, pose_camera=np.zeros(len(pr["poses"]), np.int32))
+    assert np.abs(a.poses64 - b.poses64).max() > 1e-2
+
+
+# ---------------------------------------------------------------- the C ABI without a device
+
+def _solve(p, stop=None, boolean=False):
+    out = views.BaOutput(p.n_poses, p.n_points, p.n_edges)
+    lib = capi.load()
+    fn = lib.ba_solve_b if boolean else lib.ba_solve
+    rc = fn(C.byref(p), None if stop is None else C.c_void_p(stop.ctypes.data), C.byref(out.c))
+    return rc, out
+
+
+def test_refusals_come_before_any_device_work():
+    pr = fc.problem("loop_closing")
+    e = pr["edges"].copy()
+    e["ur"][3] = capi.UR_RIGHT_CAMERA
+    p, keep = _ba_view(dict(pr, edges=e), 10, True)
+    assert _solve(p)[0] == capi.ORBG_BAD_ARG
+    n = capi.BA_MAX_FREE_POSES + 1
+    poses = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (n, 1))
+    p, keep = views.ba_problem(poses, np.zeros(n, np.uint8), np.zeros(n, np.int32), pr["points"], pr["edges"][:0], pr["cameras"])
+    assert _solve(p)[0] == capi.ORBG_CAP_EXCEEDED
+    e = pr["edges"].copy()
+    e[[0, len(e) - 1]] = e[[len(e) - 1, 0]]                      # a point's observations are no longer consecutive
+    p, keep = _ba_view(dict(pr, edges=e), 10, True)
+    assert _solve(p)[0] == capi.ORBG_BAD_ARG
+    p, keep = _ba_view(pr, 10, True, pose_camera=np.full(len(pr["poses"]), 2, np.int32))
+    assert _solve(p)[0] == capi.ORBG_BAD_ARG
+
+
+@pytest.mark.parametrize("form", ["iterations0", "raised", "no_points"])
+def test_a_solve_without_an_iteration_returns_the_estimate_it_was_given(form):
+    pr = fc.problem("loop_closing")
+    stop = None
+    if form == "no_points":
+        pr = dict(pr, points=pr["points"][:0], edges=pr["edges"][:0])
+    p, keep = _ba_view(pr, 0 if form == "iterations0" else 10, True)
+    if form == "raised":
+        stop = np.array([np.iinfo(np.int32).min], np.int32)
+    rc, out = _solve(p, stop)
+    assert rc == capi.ORBG_OK and out.iters == 0 and out.c.trace_len == 0
+    m = fm.solve(pr, 0, True)
+    assert np.abs(out.poses - m.poses).max() <= 1e-6 and np.array_equal(out.points, pr["points"])
+    assert np.array_equal(out.edge_depth_pos, m.edge_depth_pos) and not out.edge_chi2.any()
+    assert np.array_equal(out.point_included, m.point_included)

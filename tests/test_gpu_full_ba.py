@@ -1,0 +1,170 @@
+"""Optimizer::BundleAdjustment on the GPU (ba_solve, csrc/full_ba.hip) against tests/full_ba_model.py on the problems of
+tests/full_ba_cases.py, whose conditioning tests/test_full_ba_cpu.py checks.  Tolerances: poses and points 1e-4 after the float32
+write-back (the project's figure for BA results); trial counts, iterations, point_included, edge_depth_pos equal; lambda and chi2 of
+the trace to rtol 1e-9 (the bound the model meets against the oracle with a margin of four orders, tests/test_full_ba_cpu.py)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import full_ba_cases as fc
+import full_ba_model as fm
+from multi_orbslam3_amd import _capi as capi
+from multi_orbslam3_amd import api, views
+from oracle import binding as ob
+
+pytestmark = pytest.mark.gpu
+
+TRACE_RTOL = 1e-9
+STATE_TOL = 1e-4
+# The one case with a KannalaBrandt8 keyframe has bounds of its own on chi2, measured on the CPU: tests/full_ba_cases.py.
+
+@pytest.fixture(scope="module")
+def opt():
+    o = api.Optimizer()
+    yield o
+    o.close()
+
+
+def _view(pr, iterations, robust, pose_camera=None):
+    return views.ba_problem(pr["poses"], pr["pose_fixed"], pr["pose_camera"] if pose_camera is None else pose_camera, pr["points"],
+                            pr["edges"], pr["cameras"], iterations=iterations, robust=robust)
+
+
+def _solve(opt, pr, iterations, robust, stop=None, pose_camera=None):
+    p, keep = _view(pr, iterations, robust, pose_camera)
+    return opt.BundleAdjustment(p, iterations, pbStopFlag=stop, bRobust=robust)
+
+
+def _assert_equals_model(out, m, chi2_rtol=TRACE_RTOL, edge_chi2_atol=1e-6):
+    rows = out.trace_rows()
+    print("iters %d / %d, trials %s / %s" % (out.iters, m.iters, rows[:, 2].tolist(), m.trace[:, 2].tolist()))
+    assert out.status == 0                           # LBA_APPLIED
+    assert out.iters == m.iters and len(rows) == len(m.trace)
+    assert np.array_equal(rows[:, 2], m.trace[:, 2])
+    if len(rows):
+        rel = np.abs(rows[:, :2] - m.trace[:, :2]) / np.abs(m.trace[:, :2])
+        print("largest relative difference of lambda %.3g, of chi2 %.3g" % (rel[:, 0].max(), rel[:, 1].max()))
+        assert rel[:, 0].max() <= TRACE_RTOL and rel[:, 1].max() <= chi2_rtol
+        assert abs(out.chi2[0] - m.chi2_initial) <= chi2_rtol * m.chi2_initial
+        assert abs(out.chi2[1] - m.chi2_final) <= chi2_rtol * m.chi2_final
+    dp, dx = np.abs(out.poses - m.poses).max(), np.abs(out.points - m.points).max() if len(m.points) else 0.0
+    print("poses %.3g points %.3g" % (dp, dx))
+    assert dp <= STATE_TOL and dx <= STATE_TOL
+    assert np.isfinite(out.poses).all() and np.isfinite(out.points).all()
+    assert np.array_equal(out.point_included, m.point_included)
+    assert np.array_equal(out.edge_depth_pos, m.edge_depth_pos)
+    # e->chi2(): of the last evaluation.  A residual moves by at most (its Jacobian, < 1e3 px per unit) x (the state's difference
+    # between two float64 implementations, < 1e-9): 1e-6 px on residuals of a few px
+    print("edge chi2 %.3g" % np.abs(out.edge_chi2 - m.edge_chi2).max())
+    assert np.allclose(out.edge_chi2, m.edge_chi2, rtol=1e-6, atol=edge_chi2_atol)
+
+
+@pytest.mark.parametrize("name", ["initial_map", "loop_closing", "kb8_pinhole", "chain40"] + ["boundary_%d" % n for n in fc.BOUNDARY_POSES])
+def test_equals_the_model(opt, name):
+    _, its, robust = fc.CASES[name]
+    out = _solve(opt, fc.problem(name), its, robust)
+    if name == "kb8_pinhole":
+        _assert_equals_model(out, fc.model(name), fc.KB8_CHI2_RTOL, fc.KB8_EDGE_CHI2_ATOL)
+        # ... and against the model whose fisheye angles are the double atan2 rounded to float, as the device's are: every bound
+        # of the other cases holds again
+        _assert_equals_model(out, fc.model(name, False, None, "rounded_double"))
+    else:
+        _assert_equals_model(out, fc.model(name))
+
+
+def test_per_keyframe_cameras_reach_the_kernels(opt):
+    pr = fc.problem("loop_closing")
+    a = _solve(opt, pr, 10, False)
+    b = _solve(opt, pr, 10, False, pose_camera=np.zeros(len(pr["poses"]), np.int32))
+    assert np.abs(a.poses - b.poses).max() > 1e-3
+
+
+def test_api_leaves_the_problems_own_fields_when_none_are_given(opt):
+    pr = fc.problem("loop_closing")
+    p, keep = _view(pr, 10, False)
+    _assert_equals_model(opt.BundleAdjustment(p), fc.model("loop_closing"))           # bRobust = false stays false
+    assert p.robust == 0 and p.iterations == 10
+
+
+def test_degenerate_vertices(opt):
+    pr = fc.with_degenerate_vertices(fc.problem("loop_closing"))
+    out = _solve(opt, pr, 10, False)
+    m = fm.solve(pr, 10, False)
+    _assert_equals_model(out, m)
+    assert out.point_included[-1] == 0 and out.point_included[:-1].all()
+    assert np.array_equal(out.points[-1], pr["points"][-1])
+
+
+@pytest.mark.parametrize("form", ["iterations0", "no_points"])
+def test_nothing_to_iterate(opt, form):
+    pr = fc.problem("loop_closing")
+    if form == "no_points":
+        pr = dict(pr, points=pr["points"][:0], edges=pr["edges"][:0])
+    out = _solve(opt, pr, 0 if form == "iterations0" else 10, True)
+    assert out.iters == 0 and out.c.trace_len == 0
+    assert np.abs(out.poses - pr["poses"]).max() <= 1e-6 and np.array_equal(out.points, pr["points"])
+
+
+def test_stop_flag_forms(opt):
+    pr = fc.problem("loop_closing")
+    out = _solve(opt, pr, 10, False, stop=np.array([np.iinfo(np.int32).min], np.int32))
+    assert out.iters == 0 and np.abs(out.poses - pr["poses"]).max() <= 1e-6 and np.array_equal(out.points, pr["points"])
+    full = fc.model("loop_closing")
+    k = int(full.trace[:, 2].sum()) // 2
+    assert 0 < k < full.trace[:, 2].sum()
+    out = _solve(opt, pr, 10, False, stop=np.array([-k], np.int32))
+    _assert_equals_model(out, fc.model("loop_closing", False, k))
+    plain = _solve(opt, pr, 10, False)
+    byte = _solve(opt, pr, 10, False, stop=np.zeros(1, np.uint8))
+    for f in ("poses", "points", "edge_chi2", "edge_depth_pos", "trace"):
+        assert np.array_equal(getattr(plain, f), getattr(byte, f)), f
+
+
+def test_trace_equals_the_oracles_first_round(opt):
+    pr = fc.problem("one_camera")
+    out = _solve(opt, pr, 5, True)
+    p, keep = views.lba_problem(pr["poses"], pr["pose_fixed"], pr["points"], pr["edges"], pr["cameras"][0][:5], its=(5, 10))
+    o = ob.lba_solve(p)
+    want = o.trace_rows()[: o.iters[0]]
+    rows = out.trace_rows()
+    assert out.iters == o.iters[0] and np.array_equal(rows[:, 2], want[:, 2])
+    rel = np.abs(rows[:, :2] - want[:, :2]) / np.abs(want[:, :2])
+    print("largest relative difference of lambda / chi2 against the oracle: %.3g" % rel.max())
+    assert rel.max() <= TRACE_RTOL
+
+
+def test_two_solves_return_the_same_bits():
+    pr = fc.problem("boundary_65")
+    p, keep = _view(pr, 3, True)
+    h = api.FullBA()
+    a, b = h.solve(p), h.solve(p)
+    h.close()
+    h2 = api.FullBA()
+    c = h2.solve(p)
+    h2.close()
+    for other in (b, c):
+        for f in ("poses", "points", "edge_chi2", "edge_depth_pos", "point_included", "trace"):
+            assert np.array_equal(getattr(a, f), getattr(other, f)), f
+        assert a.chi2 == other.chi2 and a.iters == other.iters
+
+
+def test_handle_grows_and_refuses():
+    h = api.FullBA(cap_poses=0, cap_points=0, cap_edges=0)
+    pr = fc.problem("loop_closing")
+    out = h.solve(_view(pr, 10, False)[0])
+    _assert_equals_model(out, fc.model("loop_closing"))
+    out = h.solve(_view(fc.problem("boundary_21"), 3, True)[0])          # a larger problem on the same handle
+    _assert_equals_model(out, fc.model("boundary_21"))
+    n = capi.BA_MAX_FREE_POSES + 1
+    poses = np.tile(np.eye(4, dtype=np.float32).reshape(1, 16), (n, 1))
+    p, keep = views.ba_problem(poses, np.zeros(n, np.uint8), np.zeros(n, np.int32), pr["points"], pr["edges"][:0], pr["cameras"])
+    with pytest.raises(capi.OrbGpuError) as ei:
+        h.solve(p)
+    assert ei.value.code == capi.ORBG_CAP_EXCEEDED
+    e = pr["edges"].copy()
+    e["ur"][0] = capi.UR_RIGHT_CAMERA
+    with pytest.raises(capi.OrbGpuError) as ei:
+        h.solve(_view(dict(pr, edges=e), 10, False)[0])
+    assert ei.value.code == capi.ORBG_BAD_ARG
+    h.close()
