@@ -74,6 +74,157 @@ def test_every_problem_of_the_gpu_tests_is_well_conditioned(name):
     assert min(a.min_abs_rho, b.min_abs_rho) > 1e-6, (a.min_abs_rho, b.min_abs_rho)
 
 
+# ---------------------------------------------------------------- the cases past the first lap of the kernels' loops
+
+def _shape(pr):
+    """Free pose columns, degree per pose, observations per point, the set of non-empty pairs of free columns (diagonal included),
+    the largest number of points an off-diagonal pair shares."""
+    e = pr["edges"]
+    fixed = np.asarray(pr["pose_fixed"]).astype(bool)
+    col = np.where(fixed, -1, np.cumsum(~fixed) - 1)
+    nP = int((~fixed).sum())
+    deg = np.bincount(e["pose"], minlength=len(fixed))
+    obs = np.bincount(e["point"], minlength=len(pr["points"]))
+    seen = np.zeros((len(pr["points"]), nP), np.int64)
+    c = col[e["pose"]]
+    seen[e["point"][c >= 0], c[c >= 0]] = 1
+    shared = seen.T @ seen
+    pairs = int((np.triu(shared, 1) > 0).sum()) + nP
+    return nP, deg, obs, pairs, int(np.triu(shared, 1).max()) if nP > 1 else 0
+
+
+def _validates(pr, robust):
+    p, keep = _ba_view(pr, 0, robust)
+    rc, out = _solve(p)
+    return rc == capi.ORBG_OK and out.iters == 0
+
+
+def _has_descending_run(pr):
+    e = pr["edges"]
+    same = e["point"][1:] == e["point"][:-1]
+    return bool((same & (e["pose"][1:] < e["pose"][:-1])).any())
+
+
+def test_laps_has_degrees_around_one_and_two_laps():
+    pr = fc.problem("laps")
+    nP, deg, obs, pairs, shared = _shape(pr)
+    free = np.flatnonzero(pr["pose_fixed"] == 0)
+    assert tuple(deg[free]) == fc.LAPS_DEGREES == (255, 256, 257, 512, 513)
+    assert deg[pr["pose_fixed"] != 0].tolist() == [600] and len(pr["edges"]) == 600 + sum(fc.LAPS_DEGREES)
+    assert shared > 256                                        # an off-diagonal pair past one lap of k_ba_schur / k_ba_items_fill
+    assert obs.min() >= 2
+    assert _validates(pr, True)
+
+
+@pytest.mark.parametrize("name", ["dense46", "dense52"])
+def test_dense_cases_fill_every_pair(name):
+    pr = fc.problem(name)
+    nP, deg, obs, pairs, shared = _shape(pr)
+    assert pairs == nP * (nP + 1) // 2 and pairs > 1024        # k_ba_scan: two elements per thread
+    assert (nP <= 50) if name == "dense46" else (nP > 50)      # the eight-workgroup LDL^T / k_wide_*
+    assert nP == (46 if name == "dense46" else 52)
+    assert obs.max() >= 47
+    assert _validates(pr, True)
+
+
+def test_chain257_is_past_256_free_poses():
+    pr = fc.problem("chain257")
+    nP, deg, obs, pairs, shared = _shape(pr)
+    assert nP == 257 and (nP + 31) // 32 == 9
+    assert deg[pr["pose_fixed"] == 0].min() >= 1 and obs.min() >= 2
+    assert _validates(pr, True)
+
+
+@pytest.mark.parametrize("name", ["scrambled", "scrambled_gaps"])
+def test_scrambled_cases_have_no_pose_order(name):
+    pr = fc.problem(name)
+    fixed = np.flatnonzero(pr["pose_fixed"])
+    assert len(fixed) == 1 and 0 < fixed[0] < len(pr["poses"]) - 1
+    assert _has_descending_run(pr) and not _has_descending_run(fc.problem("loop_closing"))
+    assert _validates(pr, False)
+    nP, deg, obs, pairs, shared = _shape(pr)
+    if name == "scrambled":
+        assert fixed[0] == 3 and obs.min() >= 2 and deg.min() >= 1
+        return
+    assert np.flatnonzero(obs == 0).tolist() == list(fc.GAP_POINTS) and 0 < fc.GAP_POINTS[1] < len(obs) - 1
+    assert np.flatnonzero(deg == 0).tolist() == [fc.GAP_POSE] and not pr["pose_fixed"][fc.GAP_POSE]
+    # nothing else moved: without its gaps the problem is `scrambled`
+    s = fc.problem("scrambled")
+    kp, kx = deg > 0, obs > 0
+    assert np.array_equal(pr["poses"][kp], s["poses"]) and np.array_equal(pr["points"][kx], s["points"])
+    assert np.array_equal(pr["pose_fixed"][kp], s["pose_fixed"]) and np.array_equal(pr["pose_camera"][kp], s["pose_camera"])
+    assert np.array_equal((np.cumsum(kp) - 1)[pr["edges"]["pose"]], s["edges"]["pose"])
+    assert np.array_equal((np.cumsum(kx) - 1)[pr["edges"]["point"]], s["edges"]["point"])
+
+
+def test_the_model_does_not_depend_on_the_labelling():
+    """The model on `scrambled` is the model on loop_closing mapped through the permutation: pinned here before the device is held
+    to it."""
+    a, b = fc.model("loop_closing"), fc.model("scrambled")
+    pa, pb = fc.problem("loop_closing"), fc.problem("scrambled")
+    perm = np.asarray(fc.SCRAMBLE)
+    assert sorted(perm.tolist()) == list(range(len(pa["poses"])))
+    assert np.array_equal(pb["poses"][perm], pa["poses"]) and np.array_equal(pb["pose_fixed"][perm], pa["pose_fixed"])
+    assert np.array_equal(pb["pose_camera"][perm], pa["pose_camera"])
+    src = pb["edge_source"]
+    assert np.array_equal(np.sort(src), np.arange(len(src))) and not np.array_equal(src, np.arange(len(src)))
+    for f in ("point", "u", "v", "ur", "inv_sigma2"):
+        assert np.array_equal(pb["edges"][f], pa["edges"][f][src]), f
+    assert np.array_equal(pb["edges"]["pose"], perm[pa["edges"]["pose"][src]])
+    assert a.iters == b.iters and np.array_equal(a.trace[:, 2], b.trace[:, 2])
+    rel = np.abs(a.trace[:, :2] - b.trace[:, :2]) / np.abs(a.trace[:, :2])
+    dp, dx = np.abs(b.poses64[perm] - a.poses64).max(), np.abs(a.points.astype(np.float64) - b.points).max()
+    print("relabelled against original: lambda %.3g chi2 %.3g poses %.3g points %.3g edge chi2 %.3g" %
+          (rel[:, 0].max(), rel[:, 1].max(), dp, dx, np.abs(b.edge_chi2 - a.edge_chi2[src]).max()))
+    assert rel.max() <= TRACE_RTOL
+    assert abs(a.chi2_initial - b.chi2_initial) <= TRACE_RTOL * a.chi2_initial
+    assert dp <= 1e-6 and dx <= 1e-6
+    assert np.allclose(b.edge_chi2, a.edge_chi2[src], rtol=1e-6, atol=1e-6)
+    assert np.array_equal(b.edge_depth_pos, a.edge_depth_pos[src]) and np.array_equal(a.point_included, b.point_included)
+
+
+def test_a_stop_right_after_a_rejected_trial_returns_the_accepted_state():
+    """optimization_algorithm_levenberg.cpp:143-147: a rejected trial multiplies lambda by ni and pop()s the vertices, but no
+    computeActiveErrors follows: e->chi2() stays the rejected trial's."""
+    full = fc.model("rejected")
+    trials = full.trace[:, 2].astype(int).tolist()
+    assert max(trials) > 1
+    it = next(i for i, q in enumerate(trials) if q > 1)        # the first iteration with a rejection
+    k = sum(trials[:it]) + 1                                   # its first trial, counted over the solve
+    assert (it, k) == (4, 5)
+    before, after = fc.model("rejected", False, k - 1), fc.model("rejected", False, k)
+    assert before.iters == it and after.iters == it + 1 and after.trace[it, 2] == 1
+    assert np.array_equal(after.trace[:it], before.trace) and np.array_equal(after.trace[:it], full.trace[:it])
+    # the state: of the k - 1 accepted trials, to the bit
+    assert np.array_equal(after.poses64, before.poses64) and np.array_equal(after.points, before.points)
+    assert np.array_equal(after.edge_depth_pos, before.edge_depth_pos)
+    assert after.chi2_final == before.chi2_final == after.trace[it, 1]
+    # lambda: the raised one (ni = 2 after an accepted step), and the one the second trial of the full solve started from
+    assert after.trace[it, 0] == 2.0 * before.trace[it - 1, 0]
+    assert full.trace[it, 0] < after.trace[it, 0] and full.trace[it, 1] < after.trace[it, 1]
+    # e->chi2(): of the rejected trial's state.  Without Huber kernels the chi2 of an evaluation is the sum over its edges: the
+    # accepted state's is the trace's, the rejected trial's is larger (that is why it was rejected)
+    assert abs(before.edge_chi2.sum() - before.chi2_final) <= 1e-12 * before.chi2_final
+    assert after.edge_chi2.sum() > after.chi2_final * (1 + 1e-6)
+    assert not np.allclose(after.edge_chi2, before.edge_chi2, rtol=1e-3, atol=1e-3)
+
+
+@pytest.mark.parametrize("name", fc.NEW_CASES)
+def test_reordered_sums_bound_the_trace(name):
+    """Where the GPU bound on lambda and chi2 of the cases above comes from (tests/full_ba_cases.py): forward against reversed sums,
+    times ten, and never below the project's 1e-9.  Prints the figures; fails if one outgrows a tenth of its bound."""
+    a, b = fc.model(name), fc.model(name, True)
+    assert np.array_equal(a.trace[:, 2], b.trace[:, 2])
+    rel = np.abs(a.trace[:, :2] - b.trace[:, :2]) / np.abs(a.trace[:, :2])
+    chi2 = max(rel[:, 1].max(), abs(a.chi2_initial - b.chi2_initial) / a.chi2_initial)
+    print("%s: forward against reversed sums: lambda %.3g chi2 %.3g poses %.3g points %.3g; bound %.3g" %
+          (name, rel[:, 0].max(), chi2, np.abs(a.poses64 - b.poses64).max(), np.abs(a.points.astype(np.float64) - b.points).max(),
+           fc.trace_rtol(name)))
+    assert set(fc.REORDER_MEASURED) == set(fc.NEW_CASES)
+    assert fc.trace_rtol(name) == max(1e-9, 10 * max(fc.REORDER_MEASURED[name]))
+    assert max(rel[:, 0].max(), chi2) <= fc.trace_rtol(name) / 10 * 1.0001
+
+
 def test_float_angles_of_the_fisheye_projection_bound_the_kb8_case():
     """Where the bounds of the KannalaBrandt8 case come from (tests/full_ba_cases.py): the model solved with theta and psi of
     KannalaBrandt8::project taken as the double atan2 rounded to float -- what the device computes -- and moved by one float32 ulp,

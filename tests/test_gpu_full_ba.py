@@ -1,7 +1,9 @@
 """Optimizer::BundleAdjustment on the GPU (ba_solve, csrc/full_ba.hip) against tests/full_ba_model.py on the problems of
 tests/full_ba_cases.py, whose conditioning tests/test_full_ba_cpu.py checks.  Tolerances: poses and points 1e-4 after the float32
 write-back (the project's figure for BA results); trial counts, iterations, point_included, edge_depth_pos equal; lambda and chi2 of
-the trace to rtol 1e-9 (the bound the model meets against the oracle with a margin of four orders, tests/test_full_ba_cpu.py)."""
+the trace to rtol 1e-9 (the bound the model meets against the oracle with a margin of four orders, tests/test_full_ba_cpu.py).
+The cases past the first lap of the kernels' loops (fc.NEW_CASES) bound chi2 of the trace by fc.trace_rtol: ten times what reversing
+every sum of the model moves it by, measured on the CPU, and never below 1e-9."""
 import ctypes as C
 
 import numpy as np
@@ -60,11 +62,19 @@ def _assert_equals_model(out, m, chi2_rtol=TRACE_RTOL, edge_chi2_atol=1e-6):
     assert np.allclose(out.edge_chi2, m.edge_chi2, rtol=1e-6, atol=edge_chi2_atol)
 
 
-@pytest.mark.parametrize("name", ["initial_map", "loop_closing", "kb8_pinhole", "chain40"] + ["boundary_%d" % n for n in fc.BOUNDARY_POSES])
+@pytest.mark.parametrize("name", ["initial_map", "loop_closing", "kb8_pinhole", "chain40"] + ["boundary_%d" % n for n in fc.BOUNDARY_POSES] +
+                         list(fc.NEW_CASES))
 def test_equals_the_model(opt, name):
     _, its, robust = fc.CASES[name]
     out = _solve(opt, fc.problem(name), its, robust)
-    if name == "kb8_pinhole":
+    if name in fc.NEW_CASES:
+        _assert_equals_model(out, fc.model(name), fc.trace_rtol(name))
+        if name == "scrambled_gaps":
+            pr = fc.problem(name)
+            gaps = list(fc.GAP_POINTS)
+            assert not out.point_included[gaps].any() and out.point_included.sum() == len(pr["points"]) - len(gaps)
+            assert np.array_equal(out.points[gaps], pr["points"][gaps])
+    elif name == "kb8_pinhole":
         _assert_equals_model(out, fc.model(name), fc.KB8_CHI2_RTOL, fc.KB8_EDGE_CHI2_ATOL)
         # ... and against the model whose fisheye angles are the double atan2 rounded to float, as the device's are: every bound
         # of the other cases holds again
@@ -121,6 +131,25 @@ def test_stop_flag_forms(opt):
         assert np.array_equal(getattr(plain, f), getattr(byte, f)), f
 
 
+def test_stop_right_after_a_rejected_trial(opt):
+    """The flag goes up once the fifth trial -- the rejected one -- has been evaluated: the state is the fourth trial's, lambda the
+    raised one, e->chi2() the rejected trial's."""
+    m = fc.model("rejected", False, 5)
+    assert m.iters == 5 and m.trace[:, 2].tolist() == [1, 1, 1, 1, 1] and m.edge_chi2.sum() > m.chi2_final * (1 + 1e-6)
+    _, its, robust = fc.CASES["rejected"]
+    out = _solve(opt, fc.problem("rejected"), its, robust, stop=np.array([-5], np.int32))
+    _assert_equals_model(out, m, fc.trace_rtol("rejected"))
+    assert out.edge_chi2.sum() > out.chi2[1] * (1 + 1e-6)
+
+
+def test_rejected_trial_leaves_the_accepted_state(opt):
+    _, its, robust = fc.CASES["rejected"]
+    out = _solve(opt, fc.problem("rejected"), its, robust)
+    rows = out.trace_rows()
+    assert rows[:, 2].max() == 2                                  # (not a trace without a rejection)
+    _assert_equals_model(out, fc.model("rejected"), fc.trace_rtol("rejected"))
+
+
 def test_trace_equals_the_oracles_first_round(opt):
     pr = fc.problem("one_camera")
     out = _solve(opt, pr, 5, True)
@@ -134,19 +163,41 @@ def test_trace_equals_the_oracles_first_round(opt):
     assert rel.max() <= TRACE_RTOL
 
 
+def _assert_same_bits(a, other):
+    for f in ("poses", "points", "edge_chi2", "edge_depth_pos", "point_included", "trace"):
+        assert np.array_equal(getattr(a, f), getattr(other, f)), f
+    assert a.chi2 == other.chi2 and a.iters == other.iters
+
+
+# laps: sums of two and three laps per thread; dense46: runs of 47 observations, 1081 pairs
 def test_two_solves_return_the_same_bits():
-    pr = fc.problem("boundary_65")
-    p, keep = _view(pr, 3, True)
+    for name in ("boundary_65", "laps", "dense46"):
+        _, its, robust = fc.CASES[name]
+        p, keep = _view(fc.problem(name), its, robust)
+        h = api.FullBA()
+        a, b = h.solve(p), h.solve(p)
+        h.close()
+        h2 = api.FullBA()
+        c = h2.solve(p)
+        h2.close()
+        assert a.iters > 0, name
+        for other in (b, c):
+            _assert_same_bits(a, other)
+
+
+def test_one_handle_across_shrinking_and_growing_problems():
+    """A handle keeps its tables, bitmaps and item lists; none of them may leak from a larger earlier problem into a smaller later
+    one, or the other way round."""
     h = api.FullBA()
-    a, b = h.solve(p), h.solve(p)
+    outs = []
+    for name in ("laps", "loop_closing", "dense46", "laps"):
+        _, its, robust = fc.CASES[name]
+        p, keep = _view(fc.problem(name), its, robust)
+        out = h.solve(p)
+        _assert_equals_model(out, fc.model(name), fc.trace_rtol(name) if name in fc.NEW_CASES else TRACE_RTOL)
+        outs.append(out)
     h.close()
-    h2 = api.FullBA()
-    c = h2.solve(p)
-    h2.close()
-    for other in (b, c):
-        for f in ("poses", "points", "edge_chi2", "edge_depth_pos", "point_included", "trace"):
-            assert np.array_equal(getattr(a, f), getattr(other, f)), f
-        assert a.chi2 == other.chi2 and a.iters == other.iters
+    _assert_same_bits(outs[0], outs[3])
 
 
 def test_handle_grows_and_refuses():
