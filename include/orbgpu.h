@@ -1271,6 +1271,69 @@ int ba_solve_hb(ba_handle* h, const ba_problem* p, const volatile uint8_t* stop_
 int ba_set_profiling(ba_handle* h, int on);
 int ba_get_phase_ms(ba_handle* h, double* ms /* 5 */);
 
+/* ---------------------------------------------------------------- essential graph (Optimizer::OptimizeEssentialGraph) */
+
+/* The Sim3 pose graph that LoopClosing::CorrectLoop optimises between the fuse and the full BA (S/LoopClosing.cc:1272, body
+ * S/Optimizer.cc:2413-2747).  The forms at S/Optimizer.cc:3196 (LoopClosing::MergeLocal, S/LoopClosing.cc:1922) and :3596 set up the
+ * same numerical problem -- g2o::VertexSim3Expmap vertices, some fixed, each with its _fix_scale; g2o::EdgeSim3 edges with identity
+ * information and no robust kernel; setUserLambdaInit(1e-16); one optimize(20) -- so this one flat problem serves all three
+ * ("OptimizeEssentialGraph", says how each maps onto it).
+ * A Sim3 is rotation().coeffs() (x, y, z, w), translation(), scale(), all doubles, taken as it is (no renormalisation).
+ * FIXING THE GAUGE IS THE CALLER'S JOB, as in the reference: every connected component of the graph needs at least one fixed vertex
+ * (the reference fixes the keyframe with mnId == pMap->GetInitKFid()).  Without one the normal equations are singular up to
+ * lambda_init and the result is whatever the factorisation makes of that; nothing is checked here. */
+#define EG_MAX_FREE_KEYFRAMES 1170       /* 7 x 1170 = 8190 unknowns: the widest LDL^T of the library takes 8192 */
+typedef struct eg_vertex {
+  double  q[4], t[3], s;   /* the estimate: CorrectedSim3 of the keyframe, or its pose with scale 1 (S/Optimizer.cc:2456-2470) */
+  int32_t fixed;           /* VSim3->setFixed(true) */
+  int32_t fix_scale;       /* VSim3->_fix_scale: oplusImpl zeroes update[6] */
+} eg_vertex;
+typedef struct eg_edge {
+  int32_t vi, vj;          /* setVertex(0, .), setVertex(1, .): error = log(measurement * Siw * Sjw^-1) */
+  double  q[4], t[3], s;   /* setMeasurement(Sji) */
+} eg_edge;
+typedef struct eg_point {
+  float   pos[3];          /* pMP->GetWorldPos() */
+  int32_t ref;             /* vertex of mnCorrectedReference / GetReferenceKeyFrame(); < 0: the point keeps its bits (the reference maps
+                              a point without a vertex through two default-constructed identities, S/Optimizer.cc:2435-2436) */
+} eg_point;
+typedef struct eg_problem {
+  uint32_t struct_size;    /* sizeof(eg_problem) */
+  int32_t  n_vertices;
+  const eg_vertex* vertices;
+  int32_t  n_edges;
+  const eg_edge* edges;    /* in creation order: sums over edges run in this order */
+  int32_t  iterations;     /* optimize(20) */
+  double   lambda_init;    /* setUserLambdaInit(1e-16); <= 0: g2o's own 1e-5 x the largest diagonal entry */
+  int32_t  n_points;       /* may be 0 */
+  const eg_point* points;
+  int32_t  device;
+} eg_problem;
+typedef struct eg_result {
+  uint32_t struct_size;    /* sizeof(eg_result) */
+  double*  estimates;      /* n_vertices x 8 (q, t, s), caller-allocated: VSim3->estimate() after optimize() */
+  float*   points;         /* n_points x 3: correctedSwr.map(Srw.map(P)), Srw the vertex's estimate on entry (S/Optimizer.cc:2732-2740) */
+  double   err0, errEnd;   /* activeRobustChi2() before and after (doubles here; the reference keeps floats for a message) */
+  int32_t  iters;          /* LM iterations actually run */
+  double*  trace;          /* optional: per LM iteration {trials, last trial accepted, chi2, lambda} */
+  int32_t  trace_cap, trace_len;
+  double*  edge_error0;    /* optional, for checkers: n_edges x 7, EdgeSim3::computeError at the estimate on entry */
+} eg_result;
+
+/* The numerical core of Optimizer::OptimizeEssentialGraph on the calling thread's work area and stream: numeric Jacobians as g2o
+ * takes them for EdgeSim3 (central differences, delta = 1e-9, through oplusImpl), dense normal equations over the free vertices in
+ * ascending order, g2o's Levenberg-Marquardt without a stop flag (the reference passes none), then the map points.  Two calls on the
+ * same input return the same bits.  ORBG_BAD_ARG (indices out of range, an edge from a vertex to itself, a non-finite value, a scale
+ * <= 0, a short struct_size) and ORBG_CAP_EXCEEDED (more than EG_MAX_FREE_KEYFRAMES free vertices) are returned before a device is
+ * looked for; a problem without a free vertex, without an edge or with iterations <= 0 launches nothing (the estimates come back as
+ * they went in, the points go through them, err0 == errEnd is evaluated on the host); otherwise ORBG_NO_DEVICE where there is none. */
+int eg_solve(const eg_problem* p, eg_result* r);
+/* MEASUREMENT ONLY, not part of the stable interface (tools/essential_graph_time.py): while `on` is set (process-wide), every
+ * eg_solve brackets its launch groups with HIP events; eg_get_phase_ms returns the device time of the calling thread's last solve,
+ * ms[4] = linearisation, assembly of the blocks and of the dense system, LDL^T, update and evaluation. */
+int eg_set_profiling(int on);
+int eg_get_phase_ms(double* ms /* 4 */);
+
 /* ---------------------------------------------------------------- pose-only optimisation */
 
 /* Everything Optimizer::PoseOptimization(Frame*) reads (S/Optimizer.cc:964-1278): one entry per

@@ -155,6 +155,25 @@ class BaResult(C.Structure):
 
 BA_MAX_FREE_POSES = 1365
 
+# Optimizer::OptimizeEssentialGraph (include/orbgpu.h: eg_vertex, eg_edge, eg_point)
+EG_VERTEX_DTYPE = np.dtype([("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8"), ("fixed", "<i4"), ("fix_scale", "<i4")])
+EG_EDGE_DTYPE = np.dtype([("vi", "<i4"), ("vj", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8")])
+EG_POINT_DTYPE = np.dtype([("pos", "<f4", (3,)), ("ref", "<i4")])
+assert EG_VERTEX_DTYPE.itemsize == 72 and EG_EDGE_DTYPE.itemsize == 72 and EG_POINT_DTYPE.itemsize == 16
+EG_MAX_FREE_KEYFRAMES = 1170
+
+
+class EgProblem(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_vertices", C.c_int32), ("vertices", C.c_void_p), ("n_edges", C.c_int32),
+                ("edges", C.c_void_p), ("iterations", C.c_int32), ("lambda_init", C.c_double), ("n_points", C.c_int32),
+                ("points", C.c_void_p), ("device", C.c_int32)]
+
+
+class EgResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("estimates", C.c_void_p), ("points", C.c_void_p), ("err0", C.c_double),
+                ("errEnd", C.c_double), ("iters", C.c_int32), ("trace", C.c_void_p), ("trace_cap", C.c_int32),
+                ("trace_len", C.c_int32), ("edge_error0", C.c_void_p)]
+
 
 class PoseOptProblem(C.Structure):
     _fields_ = [("n", C.c_int32), ("Xw", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("ur", C.c_void_p),
@@ -342,6 +361,8 @@ EXPORTED_SYMBOLS = [
 INITIALISER_SYMBOLS = ["orbi_two_view_resolve_draws", "orbi_two_view_reconstruct"]
 # The full bundle adjustment (prefix ba_), likewise a list of its own; tests/test_full_ba_cpu.py holds it against the header.
 FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solve_h", "ba_solve_hb", "ba_set_profiling", "ba_get_phase_ms"]
+# The essential graph (prefix eg_), likewise; tests/test_essential_graph_cpu.py holds it against the header.
+ESSENTIAL_GRAPH_SYMBOLS = ["eg_solve", "eg_set_profiling", "eg_get_phase_ms"]
 
 _lib = None
 
@@ -396,7 +417,10 @@ def load():
     lib.orbx_frame_rgbd_wait.argtypes = [C.c_void_p, C.c_void_p]
     lib.orbx_depth_at_points.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS:
+    lib.eg_solve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.eg_set_profiling.argtypes = [C.c_int]
+    lib.eg_get_phase_ms.argtypes = [C.c_void_p]
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

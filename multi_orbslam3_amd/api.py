@@ -1022,6 +1022,40 @@ class FullBA:
         return tuple(ms)
 
 
+class EssentialGraphResult:
+    """What eg_solve returns: estimates (V, 8) float64 = q (x y z w), t, s per vertex; points (P, 3) float32; err0 / errEnd; iters;
+    trace (iters, 4) = {trials, last trial accepted, chi2, lambda} per LM iteration; edge_error0 (E, 7)."""
+
+    def __init__(self, estimates, points, err0, errEnd, iters, trace, edge_error0):
+        self.estimates, self.points, self.err0, self.errEnd, self.iters, self.trace, self.edge_error0 = (
+            estimates, points, err0, errEnd, iters, trace, edge_error0)
+
+
+def OptimizeEssentialGraph(vertices, edges, points=None, iterations=20, lambda_init=1e-16, device=0, raw=False):
+    """The numerical core of Optimizer::OptimizeEssentialGraph (S/Optimizer.cc:2413-2747; include/orbgpu.h: eg_solve).  vertices /
+    edges / points: arrays of capi.EG_VERTEX_DTYPE / EG_EDGE_DTYPE / EG_POINT_DTYPE.  At least one vertex of
+    every connected component must be fixed: that is the caller's job, as in the reference.  raw=True returns the status code with the
+    result instead of raising."""
+    lib = capi.load()
+    V = np.ascontiguousarray(vertices, capi.EG_VERTEX_DTYPE)
+    E = np.ascontiguousarray(edges, capi.EG_EDGE_DTYPE)
+    P = np.zeros(0, capi.EG_POINT_DTYPE) if points is None else np.ascontiguousarray(points, capi.EG_POINT_DTYPE)
+    est = np.zeros((len(V), 8), np.float64)
+    pts = np.zeros((len(P), 3), np.float32)
+    trace = np.zeros((max(int(iterations), 1), 4), np.float64)
+    err = np.zeros((len(E), 7), np.float64)
+    p = capi.EgProblem(C.sizeof(capi.EgProblem), len(V), _vp(V) if len(V) else None, len(E), _vp(E) if len(E) else None, int(iterations),
+                       float(lambda_init), len(P), _vp(P) if len(P) else None, int(device))
+    r = capi.EgResult(C.sizeof(capi.EgResult), _vp(est) if len(V) else None, _vp(pts) if len(P) else None, 0.0, 0.0, 0, _vp(trace), len(trace), 0,
+                      _vp(err) if len(E) else None)
+    rc = lib.eg_solve(C.byref(p), C.byref(r))
+    out = EssentialGraphResult(est, pts, r.err0, r.errEnd, r.iters, trace[: r.trace_len].copy(), err)
+    if raw:
+        return rc, out
+    capi.check(rc, "eg_solve")
+    return out
+
+
 class KeyFrameDatabase:
     """Device-resident place-recognition database (inverted file, BowVectors, covisibility lists): the compute side of
     KeyFrameDatabase::DetectNBestCandidates (S/KeyFrameDatabase.cc:594-761).  view: views.database_view(...)."""

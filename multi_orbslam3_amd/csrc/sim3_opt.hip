@@ -50,6 +50,7 @@
 #include "wave.hpp"
 #include "lm_block.hpp"
 #include "se3.hpp"
+#include "sim3_math.hpp"
 
 using orbg::block_sum;
 using orbg::lane_ldlt_solve;
@@ -57,6 +58,10 @@ using orbg::select_device;
 using orbg::wave_sum_f64;
 using orbg_se3::quat_from_R;
 using orbg_se3::quat_rotate;
+using orbg_s3::S3;            // Sim3(Vector7d), operator*, inverse(): sim3_math.hpp
+using orbg_s3::s3_exp;
+using orbg_s3::s3_inverse;
+using orbg_s3::s3_mul;
 
 namespace {
 
@@ -64,8 +69,6 @@ constexpr int kS3oThreads = 256;
 constexpr int kS3oTile = 1024;     // pairs staged in LDS: 12 floats each, 48 KiB
 constexpr int kS3oNV = 36;         // 28 of H, 7 of b, chi2
 constexpr int kS3oTrace = 15;      // 5 + 10 LM iterations at most
-
-struct S3 { double q[4], t[3], s; };   // g2o::Sim3: rotation().coeffs() (x, y, z, w), translation(), scale()
 
 struct S3oDesc {                   // one problem of a launch
   int n, fix_scale, n_corr, pad;
@@ -83,90 +86,6 @@ struct S3oRec {                    // what the host reads back per problem
   S3 S;
   double trace[kS3oTrace][4];      // per LM iteration: round, lambda, chi2, trials
 };
-
-// Sim3(const Vector7d& update), G/types/sim3.h:70-142, all four branches (E-1, E-4)
-__device__ inline void s3_exp(const double* u, S3* o) {
-  const double om0 = u[0], om1 = u[1], om2 = u[2], sigma = u[6];
-  const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-  const double O[9] = {0, -om2, om1, om2, 0, -om0, -om1, om0, 0};
-  const double s = exp(sigma);
-  double O2[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-  const double eps = 0.00001;
-  double A, B, C, ra = 1.0, rb = 1.0;      // R = I + ra Omega + rb Omega2; the small-angle branches add Omega and Omega2 as they are
-  const bool small = theta < eps;
-  if (fabs(sigma) < eps) {
-    C = 1;
-    if (small) {
-      A = 1. / 2.;
-      B = 1. / 6.;
-    } else {
-      const double theta2 = theta * theta;
-      A = (1 - cos(theta)) / (theta2);
-      B = (theta - sin(theta)) / (theta2 * theta);
-    }
-  } else {
-    C = (s - 1) / sigma;
-    if (small) {
-      const double sigma2 = sigma * sigma;
-      A = ((sigma - 1) * s + 1) / sigma2;
-      B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-    } else {
-      const double a = s * sin(theta);
-      const double b = s * cos(theta);
-      const double theta2 = theta * theta;
-      const double sigma2 = sigma * sigma;
-      const double c = theta2 + sigma2;
-      A = (a * sigma + (1 - b) * theta) / (theta * c);
-      B = (C - ((b - 1) * sigma + a * theta) / (c)) * 1. / (theta2);
-    }
-  }
-  double R[9];
-  if (small) {
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + O[i] + O2[i];
-  } else {
-    ra = sin(theta) / theta;
-    rb = (1 - cos(theta)) / (theta * theta);
-#pragma unroll
-    for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + ra * O[i] + rb * O2[i];
-  }
-  quat_from_R(R, o->q);
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    const double W0 = A * O[3 * i] + B * O2[3 * i] + C * (i == 0 ? 1.0 : 0.0);
-    const double W1 = A * O[3 * i + 1] + B * O2[3 * i + 1] + C * (i == 1 ? 1.0 : 0.0);
-    const double W2 = A * O[3 * i + 2] + B * O2[3 * i + 2] + C * (i == 2 ? 1.0 : 0.0);
-    o->t[i] = W0 * u[3] + W1 * u[4] + W2 * u[5];
-  }
-  o->s = s;
-}
-
-// Sim3::operator*, sim3.h:266-272 (E-3, E-7)
-__device__ inline void s3_mul(const S3& a, const S3& b, S3* o) {
-  const double* x = a.q; const double* y = b.q;
-  o->q[0] = x[3] * y[0] + x[0] * y[3] + x[1] * y[2] - x[2] * y[1];
-  o->q[1] = x[3] * y[1] + x[1] * y[3] + x[2] * y[0] - x[0] * y[2];
-  o->q[2] = x[3] * y[2] + x[2] * y[3] + x[0] * y[1] - x[1] * y[0];
-  o->q[3] = x[3] * y[3] - x[0] * y[0] - x[1] * y[1] - x[2] * y[2];
-  double rt[3];
-  quat_rotate(a.q, b.t, rt);
-#pragma unroll
-  for (int i = 0; i < 3; i++) o->t[i] = a.s * rt[i] + a.t[i];
-  o->s = a.s * b.s;
-}
-
-// Sim3::inverse, sim3.h:233-236 (E-6)
-__device__ inline void s3_inverse(const S3& a, S3* o) {
-  o->q[0] = -a.q[0]; o->q[1] = -a.q[1]; o->q[2] = -a.q[2]; o->q[3] = a.q[3];
-  const double k = -1. / a.s;
-  const double v[3] = {k * a.t[0], k * a.t[1], k * a.t[2]};
-  quat_rotate(o->q, v, o->t);
-  o->s = 1. / a.s;
-}
 
 // VertexSim3Expmap::oplusImpl, I/OptimizableTypes.h:158-167, followed by the inverse every EdgeInverseSim3ProjectXYZ takes:
 // E[0..8) = Sim3(update) * est, E[8..16) = its inverse, each as q[4] t[3] s
