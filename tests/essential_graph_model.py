@@ -518,3 +518,62 @@ def measure_family():
             band_pts[key] = max(band_pts.get(key, 0.0), d_pts)
         scenes.append(dict(entry=(n, fs, seed), problem=p, f64=a, ld=b, same_trace=same, d_est=d_est, d_pts=d_pts, band=key))
     return dict(scenes=scenes, band_est=band_est, band_pts=band_pts)
+
+
+# ------------------------------------------------------------------ the cap, against a model that stays cheap
+# K disjoint copies of one component: chi2 is K times the component's and lambda starts at the user's 1e-16 whatever the size.  The
+# gain ratio of a trial is K dchi2 / (K (scale) + 1e-3) against dchi2 / (scale + 1e-3): the same sign, so the same verdicts; its size
+# only sets the factor on a lambda that stays far below the rounding of the diagonal it is added to (and is alone only on a
+# fixed-scale diagonal, whose right-hand side is exactly 0).  The trajectory of every copy is the component's.
+
+RING_FREE = 13
+# name -> copies: 90 x 13 = 1170 = EG_MAX_FREE_KEYFRAMES (8190 unknowns); 80 x 13 = 1040 (past 1024, below the cap)
+RING_COPIES = {"cap1170": 90, "kilo1040": 80}
+
+
+def ring_problem(fix_scale, n_free=RING_FREE, seed=3, noise=0.02, drift=0.05):
+    """A loop of n_free + 1 keyframes one metre apart, vertex 0 fixed: odometry edges (i + 1, i), a chord (i + 3, i) from every
+    third vertex, the loop edge (n_free, 0).  The estimates are disturbed; the measurements are those of the undisturbed ring,
+    disturbed again, so they contradict each other (drift) and the minimum keeps a residual.  One map point per keyframe and one
+    without a reference."""
+    rng = np.random.default_rng(seed + (100 if fix_scale else 0))
+    n = n_free + 1
+
+    def sim3(rot, trans, sig):
+        S = sim3_exp([float(v) for v in rot] + [float(v) for v in trans] + [float(sig)], np.float64)
+        return [float(v) for v in S[0]], [float(v) for v in S[1]], float(S[2])
+
+    q, t, s = zip(*[sim3(np.zeros(3), np.zeros(3), 0.0) if i == 0 else
+                    sim3(rng.normal(size=3) * noise, np.array([-float(i), 0, 0]) + rng.normal(size=3) * noise, 0.0 if fix_scale else rng.normal() * noise)
+                    for i in range(n)])
+    edges = [(i + 1, i) for i in range(n - 1)] + [(i + 3, i) for i in range(0, n - 3, 3)] + [(n - 1, 0)]
+    mq, mt, ms = zip(*[sim3(rng.normal(size=3) * drift, np.array([float(i - j), 0, 0]) + rng.normal(size=3) * drift, 0.0 if fix_scale else rng.normal() * drift)
+                       for i, j in edges])
+    pos = rng.normal(size=(n + 1, 3)).astype(np.float32) * 2
+    return Problem(q, t, s, [True] + [False] * n_free, [fix_scale] * n, [e[0] for e in edges], [e[1] for e in edges], mq, mt, ms, pos, list(range(n)) + [-1])
+
+
+def replicate(p, K, seed=13):
+    """K disjoint copies of p, interleaved: vertex (point) v of copy c is vertex (point) v * K + c, every copy with its own fixed
+    keyframe; the edges in the order of a seeded permutation.  The result carries edge_source / edge_copy and copies."""
+    rep = lambda a: np.repeat(a, K, axis=0)
+    copy_v = np.tile(np.arange(K), len(p.s))
+    E = len(p.vi)
+    o = np.random.RandomState(seed).permutation(E * K)
+    src, copy_e = np.repeat(np.arange(E), K)[o], np.tile(np.arange(K), E)[o]
+    ref = np.repeat(p.ref, K)
+    ref = np.where(ref >= 0, ref * K + np.tile(np.arange(K), len(p.ref)), -1)
+    r = Problem(rep(p.q), rep(p.t), rep(p.s), rep(p.fixed), rep(p.fix_scale), p.vi[src] * K + copy_e, p.vj[src] * K + copy_e, p.mq[src], p.mt[src], p.ms[src],
+                rep(p.pos), ref)
+    r.edge_source, r.edge_copy, r.copies, r.vertex_copy = src, copy_e, K, copy_v
+    return r
+
+
+def reorder_figure(terms):
+    """|forward sum - reversed sum| / sum of the float64 terms, added one by one"""
+    fwd = rev = 0.0
+    for v in np.asarray(terms, np.float64).tolist():
+        fwd += v
+    for v in np.asarray(terms, np.float64)[::-1].tolist():
+        rev += v
+    return abs(fwd - rev) / abs(fwd)

@@ -171,6 +171,81 @@ def problem(name):
     return DERIVED[name](pr) if name in DERIVED else pr
 
 
+# ---------------------------------------------------------------- the caps, against a model that stays cheap
+# K disjoint copies of one component: chi2 is K times the component's, the largest diagonal entry (lambda's first value) is the
+# component's, and the gain ratio of a trial is K dchi2 / (K scale + 1e-3) where the component's is dchi2 / (scale + 1e-3): the same
+# sign, and the same factor on lambda as long as both sit above the 0.937 from which the factor is the clamped 1/3.  The LM
+# trajectory of every copy is then the component's, which the model solves in half a second.  The component: 13 free poses and a
+# fixed one, robust with 3 % outliers, four iterations (gain ratios 1.07 .. 1.4, computeScale 50 and more; tests/test_full_ba_cpu.py
+# checks both for K = REPLICATED_MAX_K).  It is a case like the others (CASES), the replicated problems are not: nobody runs the model on them.
+CASES["component13"] = (dict(n_free=13, n_fixed=1, n_points=195, n_cameras=2, mono_frac=0.3, outlier_frac=0.03, seed=0xBE01, min_obs=2, max_obs=4), 4, True)
+# name -> (component, copies).  105 x 13 = 1365 = BA_MAX_FREE_POSES (8190 unknowns); 80 x 13 = 1040: past the 1024 threads of
+# one workgroup of the thread-per-pose kernels and below the cap, so that a failure at the cap can be told from one at the second workgroup
+REPLICATED = {"cap1365": ("component13", 105), "kilo1040": ("component13", 80)}
+REPLICATED_MAX_K = 105
+
+
+def replicate(pr, K, seed=11):
+    """K disjoint copies of pr, interleaved: pose (point) k of copy c is pose (point) k * K + c of the result, every copy with its own
+    fixed keyframes and points.  The edges keep the order rule (edge.point never decreases) and nothing else: inside a point's run
+    they are shuffled by a seeded permutation.  out['edge_source'][e] / out['edge_copy'][e]: the component's edge and the copy."""
+    out = {f: np.repeat(pr[f], K, axis=0) for f in ("poses", "pose_fixed", "pose_camera", "points")}
+    out["cameras"] = pr["cameras"]
+    e = np.repeat(pr["edges"], K)
+    src = np.repeat(np.arange(len(pr["edges"])), K)
+    copy = np.tile(np.arange(K), len(pr["edges"]))
+    e["pose"] = e["pose"].astype(np.int64) * K + copy
+    e["point"] = e["point"].astype(np.int64) * K + copy
+    rng = np.random.RandomState(seed)
+    o = np.lexsort((rng.permutation(len(e)), e["point"]))
+    out.update(edges=e[o], edge_source=src[o], edge_copy=copy[o], copies=K)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def replicated_problem(name):
+    comp, K = REPLICATED[name]
+    return replicate(problem(comp), K)
+
+
+def replicated_model(m, rp):
+    """What the model would return on the replicated problem rp, from its result m on the component."""
+    K = rp["copies"]
+    r = fm.BaModelResult()
+    r.iters, r.trace = m.iters, m.trace * np.array([1.0, K, 1.0])
+    r.chi2_initial, r.chi2_final = K * m.chi2_initial, K * m.chi2_final
+    r.poses, r.poses64, r.points = np.repeat(m.poses, K, axis=0), np.repeat(m.poses64, K, axis=0), np.repeat(m.points, K, axis=0)
+    r.point_included = np.repeat(m.point_included, K)
+    r.edge_chi2, r.edge_depth_pos = m.edge_chi2[rp["edge_source"]], m.edge_depth_pos[rp["edge_source"]]
+    return r
+
+
+def replicated_sum_figure(m, pr, robust, K):
+    """Forward against reversed for the chi2 sum of K interleaved copies (rho of every edge of the model's last evaluation on the
+    component pr, one term per edge of the replicated problem), relative."""
+    chi = np.asarray(m.edge_chi2, np.float64)
+    delta = np.where(pr["edges"]["ur"] < 0, fm.D_MONO, fm.D_STEREO)
+    rho = np.where(robust & (chi > delta * delta), 2 * np.sqrt(chi) * delta - delta * delta, chi)
+    terms = np.repeat(rho, K)
+    fwd, rev = 0.0, 0.0
+    for v in terms.tolist():
+        fwd += v
+    for v in terms[::-1].tolist():
+        rev += v
+    return abs(fwd - rev) / fwd
+
+
+def replicated_trace_rtol(name):
+    """max(1e-9, 10 x the larger of: the component's trace forward against reversed, the replicated chi2 sum forward against
+    reversed) -- measured on the CPU, tests/test_full_ba_cpu.py::test_copies_of_a_component_follow_its_trajectory prints both."""
+    return max(1e-9, 10.0 * max(REPLICATED_MEASURED[name]))
+
+
+# name -> (component's trace forward against reversed, chi2 sum of the K copies forward against reversed).  Three copies against
+# three times the component, for the record: lambda 0, chi2 1.1e-14, poses 1.3e-13, points 0.
+REPLICATED_MEASURED = {"cap1365": (9.79e-15, 9.07e-14), "kilo1040": (9.79e-15, 6.58e-15)}
+
+
 @functools.lru_cache(maxsize=None)
 def model(name, reverse=False, stop_after_trials=None, kb8_angles="oracle"):
     _, its, robust = CASES[name]

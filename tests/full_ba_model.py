@@ -129,6 +129,7 @@ def solve(pr, iterations, robust, stop_after_trials=None, reverse_sums=False, po
     res.iters = 0
     res.chi2_initial = res.chi2_final = 0.0
     res.min_abs_rho = np.inf
+    res.trial_gain = []                         # per trial: (chi2 before - chi2 of the trial, computeScale): rho = first / (second + 1e-3)
     res.max_kb8_residual_shift = 0.0            # px: largest difference between kb8_residual and the oracle's residual
     res.max_edge_chi2 = 0.0                     # over every evaluation of the solve, rejected trials included
     res.point_included = included
@@ -226,6 +227,7 @@ def solve(pr, iterations, robust, stop_after_trials=None, reverse_sums=False, po
             temp = float(np.sum(rho0_t)) if solved else np.finfo(np.float64).max
             rho = (cur_chi - temp) / (scale + 1e-3)
             res.min_abs_rho = min(res.min_abs_rho, abs(rho))
+            res.trial_gain.append((cur_chi - temp, scale))
             if rho > 0 and np.isfinite(temp):
                 alpha = min(1.0 - (2 * rho - 1) ** 3, 2.0 / 3.0)
                 lam *= max(1.0 / 3.0, alpha)

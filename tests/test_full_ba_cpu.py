@@ -247,6 +247,68 @@ def test_float_angles_of_the_fisheye_projection_bound_the_kb8_case():
     assert worst_chi2 <= fc.KB8_CHI2_RTOL / 10 * 1.0001 and worst_edge <= fc.KB8_EDGE_CHI2_ATOL / 10 * 1.0001
 
 
+def test_copies_of_a_component_follow_its_trajectory():
+    """The argument the cap cases of tests/test_gpu_full_ba.py rest on (fc.REPLICATED), on three interleaved copies where the model
+    can still solve the whole problem: trial counts equal the component's, lambda equal and chi2 three times the component's within
+    the rule of the cases past the first lap, states equal.  For the K of the GPU cases the one term that does not scale -- the
+    1e-3 next to computeScale in the gain ratio -- is shown not to matter from the component's own trials: every ratio has the
+    component's sign and stays above the 0.937 from which the factor on lambda is the clamped 1/3.  Prints the forward-against-
+    reversed figures the GPU bound is made of."""
+    name = "component13"
+    _, its, robust = fc.CASES[name]
+    pr, one = fc.problem(name), fc.model(name)
+    assert robust and one.iters == its and (one.edge_chi2 > fm.D_MONO ** 2 * 4).sum() >= 5          # robust, with outliers that stay
+    rp = fc.replicate(pr, 3)
+    K = rp["copies"]
+    nP, deg, obs, pairs, shared = _shape(rp)
+    assert nP == 3 * 13 and rp["pose_fixed"][:K].all() and not rp["pose_fixed"][K:].any()           # every copy its own fixed keyframe
+    assert np.array_equal(rp["edges"]["pose"] % K, rp["edge_copy"]) and np.array_equal(rp["edges"]["point"] % K, rp["edge_copy"])
+    assert (np.diff(rp["edges"]["point"].astype(np.int64)) >= 0).all() and _has_descending_run(rp) and _validates(rp, robust)
+    three, want = fm.solve(rp, its, robust), fc.replicated_model(one, rp)
+    assert three.iters == one.iters and np.array_equal(three.trace[:, 2], one.trace[:, 2])
+    rel = np.abs(three.trace[:, :2] - want.trace[:, :2]) / np.abs(want.trace[:, :2])
+    chi2 = max(rel[:, 1].max(), abs(three.chi2_initial - want.chi2_initial) / want.chi2_initial)
+    dp, dx = np.abs(three.poses64 - want.poses64).max(), np.abs(three.points.astype(np.float64) - want.points).max()
+    print("three copies against 3 x one: lambda %.3g chi2 %.3g poses %.3g points %.3g" % (rel[:, 0].max(), chi2, dp, dx))
+    assert max(rel[:, 0].max(), chi2) <= 1e-9 and dp <= 1e-9 and dx <= 1e-6                       # (points: float32 values)
+    assert np.array_equal(three.edge_depth_pos, want.edge_depth_pos) and np.array_equal(three.point_included, want.point_included)
+    assert np.allclose(three.edge_chi2, want.edge_chi2, rtol=1e-9, atol=1e-9)
+    # the gain ratios at the K of the GPU cases
+    assert len(one.trial_gain) == int(one.trace[:, 2].sum())
+    for d, s in one.trial_gain:
+        assert s > 1.0
+        for k in (1, 3) + tuple(c for _, c in fc.REPLICATED.values()):
+            assert k * d / (k * s + 1e-3) > 0.95
+    # the bounds of the replicated cases
+    rev = fc.model(name, True)
+    assert np.array_equal(rev.trace[:, 2], one.trace[:, 2])
+    r2 = np.abs(one.trace[:, :2] - rev.trace[:, :2]) / np.abs(one.trace[:, :2])
+    f_comp = max(r2.max(), abs(one.chi2_initial - rev.chi2_initial) / one.chi2_initial)
+    assert max(c for _, c in fc.REPLICATED.values()) == fc.REPLICATED_MAX_K and set(fc.REPLICATED_MEASURED) == set(fc.REPLICATED)
+    for rname, (comp, copies) in sorted(fc.REPLICATED.items()):
+        f_sum = fc.replicated_sum_figure(one, pr, robust, copies)
+        print("%s: component forward against reversed %.3g, chi2 sum of %d copies forward against reversed %.3g; bound %.3g" %
+              (rname, f_comp, copies, f_sum, fc.replicated_trace_rtol(rname)))
+        assert comp == name and max(f_comp, f_sum) <= fc.replicated_trace_rtol(rname) / 10 * 1.0001
+
+
+def test_the_cap_case_is_at_the_cap_and_spans_every_index_range():
+    rp = fc.replicated_problem("cap1365")
+    K = rp["copies"]
+    nP = int((rp["pose_fixed"] == 0).sum())
+    deg, obs = np.bincount(rp["edges"]["pose"], minlength=len(rp["poses"])), np.bincount(rp["edges"]["point"], minlength=len(rp["points"]))
+    assert nP == capi.BA_MAX_FREE_POSES == 1365 and 6 * nP == 8190 and (nP + 31) // 32 == 43        # 43 bitmap words per row
+    free = np.flatnonzero(rp["pose_fixed"] == 0)
+    assert deg[free].min() >= 1 and obs.min() >= 2
+    e = rp["edges"]
+    assert np.array_equal(e["pose"] % K, e["point"] % K)                       # disjoint copies ...
+    first = e["pose"][np.r_[True, e["point"][1:] != e["point"][:-1]]]
+    assert len(set((first // K).tolist())) > 1 and _has_descending_run(rp)       # ... interleaved, the runs in no pose order
+    assert _validates(rp, True)
+    nP2 = int((fc.replicated_problem("kilo1040")["pose_fixed"] == 0).sum())
+    assert 1024 < nP2 == 1040 < capi.BA_MAX_FREE_POSES
+
+
 def test_per_keyframe_cameras_matter():
     pr = fc.problem("loop_closing")
     a = fc.model("loop_closing")

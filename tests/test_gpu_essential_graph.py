@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import essential_graph_model as em
-from test_essential_graph_cpu import api_arrays, yardstick
+from test_essential_graph_cpu import RING_ITERATIONS, api_arrays, ring_err0_rtol, yardstick
 from multi_orbslam3_amd import _capi as capi, api
 
 pytestmark = pytest.mark.gpu
@@ -233,7 +233,54 @@ def test_structure_cases(name):
         assert g.errEnd >= float((e01 * e01).sum()) * (1 - 1e-12)               # the fixed pair's edges contribute chi2 only
 
 
-# ------------------------------------------------------------------ 5. determinism
+# ------------------------------------------------------------------ 5. the cap of 1170 free keyframes, and one size below it
+
+@needs_long_double
+@pytest.mark.parametrize("fix_scale", [True, False])
+@pytest.mark.parametrize("name", sorted(em.RING_COPIES))
+def test_copies_of_a_ring_at_and_below_the_cap(name, fix_scale):
+    """EG_MAX_FREE_KEYFRAMES free keyframes (8190 unknowns on k_wide_*) and 1040 (past 1024, below the cap) as interleaved disjoint
+    copies of one ring of 13 free keyframes with drift, each with its own fixed keyframe: the float64 model on ONE ring is the
+    reference of every copy (tests/test_essential_graph_cpu.py::test_copies_of_a_ring_follow_its_trajectory).  Trials and verdict
+    per iteration equal; chi2 at entry the number of copies times the ring's, to max(1e-12, ten times what reversing that sum
+    moves it by); estimates and points of every copy, and of the copies among each other, within 4 x the float64-vs-long-double
+    distance of the band of 43 and more free keyframes; chi2 along the trace within 4 x the ring's own float64-vs-long-double
+    distance in it (the state it is evaluated at differs by that much)."""
+    fam = yardstick()
+    key = (em.BANDS[-1], fix_scale)
+    band_est, band_pts = fam["band_est"][key], fam["band_pts"][key]
+    K = em.RING_COPIES[name]
+    p = em.ring_problem(fix_scale)
+    one, ld = em.run(p, np.float64, iterations=RING_ITERATIONS), em.run(p, em.L, iterations=RING_ITERATIONS)
+    rp = em.replicate(p, K)
+    assert rp.n_free == 13 * K and (name != "cap1170" or rp.n_free == capi.EG_MAX_FREE_KEYFRAMES)
+    g = solve(rp, iterations=RING_ITERATIONS)
+    assert device_trace(g) == em.trace_key(one) == em.trace_key(ld) and g.iters == one["iters"]
+    rel0 = abs(g.err0 - K * float(one["err0"])) / (K * float(one["err0"]))
+    chi_g, chi_1, chi_ld = g.trace[:, 2], np.array([float(t[2]) for t in one["trace"]]), np.array([float(t[2]) for t in ld["trace"]])
+    band_chi = float((np.abs(chi_1 - chi_ld) / chi_ld).max())
+    rel = float((np.abs(chi_g - K * chi_1) / (K * chi_1)).max())
+    d_est = max(em.est_diff(g.estimates[c::K], one["est"]) for c in range(K))
+    pts = g.points.reshape(-1, K, 3).astype(np.float64)
+    m = p.ref >= 0
+    d_pts = float(np.abs(pts[m] - one["points"][m][:, None, :]).max())
+    among_est = max(em.est_diff(g.estimates[c::K], g.estimates[0::K]) for c in range(1, K))
+    among_pts = float(np.abs(pts[m] - pts[m][:, :1]).max())
+    print("%s fix_scale %d: err0 %.3g (bound %.3g), chi2 of the trace %.3g (4 x %.3g), |d est| %.3g among the copies %.3g (4 x %.3g), |d pts| %.3g among %.3g (4 x %.3g)" %
+          (name, fix_scale, rel0, ring_err0_rtol(name, fix_scale), rel, band_chi, d_est, among_est, band_est, d_pts, among_pts, band_pts))
+    assert rel0 <= ring_err0_rtol(name, fix_scale)
+    assert rel <= 4 * band_chi
+    assert d_est <= 4 * band_est and among_est <= 4 * band_est
+    assert d_pts <= 4 * band_pts and among_pts <= 4 * band_pts
+    assert abs(g.errEnd - g.trace[-1, 2]) <= 1e-12 * g.errEnd and g.errEnd < g.err0
+    fixed_in = np.concatenate([rp.q, rp.t, rp.s[:, None]], axis=1)[rp.fixed]
+    assert g.estimates[rp.fixed].tobytes() == fixed_in.tobytes()                      # every copy's fixed keyframe stays
+    assert g.points[rp.ref < 0].tobytes() == rp.pos[rp.ref < 0].tobytes()
+    if fix_scale:
+        assert g.estimates[:, 7].tobytes() == rp.s.tobytes()
+
+
+# ------------------------------------------------------------------ 6. determinism
 
 def _bits(r):
     return (r.estimates.tobytes(), r.points.tobytes(), r.trace.tobytes(), r.edge_error0.tobytes(), r.err0, r.errEnd, r.iters)

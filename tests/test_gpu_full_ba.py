@@ -83,6 +83,25 @@ def test_equals_the_model(opt, name):
         _assert_equals_model(out, fc.model(name))
 
 
+@pytest.mark.parametrize("name", sorted(fc.REPLICATED))
+def test_copies_of_a_component_at_and_below_the_cap(opt, name):
+    """BA_MAX_FREE_POSES free poses (8190 unknowns on k_wide_*: 64 KB of LDS in k_wide_back, 43 bitmap words per row, the counting
+    sort over 1365 columns) and 1040 (the second workgroup of the thread-per-pose kernels, below the cap), as interleaved disjoint
+    copies of component13: the model's result on ONE component is the reference for every copy (chi2 times the number of copies;
+    tests/test_full_ba_cpu.py::test_copies_of_a_component_follow_its_trajectory), with the bounds of every other case."""
+    comp, K = fc.REPLICATED[name]
+    _, its, robust = fc.CASES[comp]
+    rp = fc.replicated_problem(name)
+    out = _solve(opt, rp, its, robust)
+    _assert_equals_model(out, fc.replicated_model(fc.model(comp), rp), fc.replicated_trace_rtol(name))
+    assert out.trace_rows()[:, 2].tolist() == fc.model(comp).trace[:, 2].tolist()
+    P, L = len(rp["poses"]) // K, len(rp["points"]) // K
+    poses, points = out.poses.reshape(P, K, 16), out.points.reshape(L, K, 3)
+    dp, dx = np.abs(poses - poses[:, :1]).max(), np.abs(points - points[:, :1]).max()
+    print("the %d copies among each other: poses %.3g points %.3g" % (K, dp, dx))
+    assert dp <= STATE_TOL and dx <= STATE_TOL
+
+
 def test_per_keyframe_cameras_reach_the_kernels(opt):
     pr = fc.problem("loop_closing")
     a = _solve(opt, pr, 10, False)
