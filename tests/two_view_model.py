@@ -336,10 +336,12 @@ def motions_H(H21, cam, ft):
     return np.stack(Rs), np.stack(ts)
 
 
-def check_rt(R, t, m, inliers, cam, sigma, ft):
+def check_rt(R, t, m, inliers, cam, sigma, ft, details=False):
     """CheckRT, :802-911, for one motion hypothesis over the matches m = (u1, v1, u2, v2) -> nGood, parallax, counted (N) bool,
     good (N) bool, p3d (N, 3), and the gate record per match (0 not an inlier, 1 non-finite, 2 depth 1, 3 depth 2, 4 reprojection 1,
-    5 reprojection 2, 6 counted)."""
+    5 reprojection 2, 6 counted).  details: a seventh entry with the quantities the gates are taken on, per match and whether or not
+    the match reaches the gate (e1, e2 against th2; z1, z2 against 0; cosP against 0.99998), th2 and the sorted cosP of the counted
+    matches."""
     fx, fy, cx, cy = (ft(v) for v in cam)
     u1, v1, u2, v2 = (np.asarray(x, ft) for x in m)
     N = len(u1)
@@ -385,11 +387,20 @@ def check_rt(R, t, m, inliers, cam, sigma, ft):
         gate[alive] = 6
         nGood = int(alive.sum())
         parallax = ft(0)
+        srt = np.sort(cosP[alive])
         if nGood > 0:
-            srt = np.sort(cosP[alive])
             c = srt[min(50, nGood - 1)]
-            parallax = ft(f64(ft(np.arccos(f64(c))) * ft(180)) / np.pi)
-    return nGood, parallax, alive, alive & low, np.where(alive[:, None], p, ft(0)).astype(ft), gate
+            parallax = parallax_of(c, ft)
+    res = (nGood, parallax, alive, alive & low, np.where(alive[:, None], p, ft(0)).astype(ft), gate)
+    if details:
+        res += (Out(e1=e1, e2=e2, z1=p[:, 2], z2=p2[:, 2], cosP=cosP, th2=th2, sorted=srt),)
+    return res
+
+
+def parallax_of(c, ft):
+    """:898 on one cosine: acos in double, degrees as the reference's types give them (T-8)."""
+    with np.errstate(all="ignore"):
+        return ft(f64(ft(np.arccos(f64(c))) * ft(180)) / np.pi)
 
 
 def decide_F(nGood, parallax, n_inliers, minParallax=1.0, minTriangulated=50):
@@ -466,7 +477,7 @@ def finish(o, scores, cam, sigma, n1, ft=np.float32, motion_stats=None):
     r = Out(SH=SH, SF=SF, bestH=bH, bestF=bF, model=model, ok=False, best_motion=-1, n_motions=0, h_degenerate=False,
             motion_nGood=np.zeros(0, np.int32), motion_parallax=np.zeros(0, ft), motion_R=np.zeros((0, 3, 3), ft),
             motion_t=np.zeros((0, 3), ft), R21=np.zeros((3, 3), ft), t21=np.zeros(3, ft), vP3D=np.zeros((n1, 3), ft),
-            vbTriangulated=np.zeros(n1, bool), n_inliers=0, gates=None)
+            vbTriangulated=np.zeros(n1, bool), n_inliers=0, gates=None, counted=None, good=None, rt=None)
     if model == 0:
         return r
     inl = o.masks[0, bH] if model == 1 else o.masks[1, bF]
@@ -476,12 +487,14 @@ def finish(o, scores, cam, sigma, n1, ft=np.float32, motion_stats=None):
         r.h_degenerate = True
         return r
     Rs, ts = mot
-    res = [check_rt(Rs[k], ts[k], o.m, inl, cam, sigma, ft) for k in range(len(Rs))]
+    res = [check_rt(Rs[k], ts[k], o.m, inl, cam, sigma, ft, details=True) for k in range(len(Rs))]
     r.n_motions = len(Rs)
     r.motion_R, r.motion_t = Rs, ts
     r.motion_nGood = np.array([x[0] for x in res], np.int32)
     r.motion_parallax = np.array([x[1] for x in res], ft)
     r.gates = np.stack([x[5] for x in res])
+    r.counted, r.good = np.stack([x[2] for x in res]), np.stack([x[3] for x in res])
+    r.rt = [x[6] for x in res]
     ng, par = (r.motion_nGood, r.motion_parallax) if motion_stats is None else motion_stats
     k = decide_H(ng, par, r.n_inliers) if model == 1 else decide_F(ng, par, r.n_inliers)
     r.best_motion = k
@@ -616,6 +629,96 @@ def flagged(o64, delta):
     return near.any(axis=(1, 3))
 
 
+def near_directions(o64, delta):
+    """(2, 2, H, N) bool: (model, direction, hypothesis, match) whose float64 chi-square is within delta relative of its gate."""
+    th = gate_thresholds()
+    with np.errstate(all="ignore"):
+        return np.abs(o64.chi - th) <= delta * th
+
+
+def near_pairs(o64, delta):
+    """(2, H, N) bool: a (model, hypothesis, match) pair is near when the float64 chi-square of either direction lies within delta
+    relative of its gate.  Only these mask bits may differ from the float32 model's."""
+    return near_directions(o64, delta).any(axis=1)
+
+
+# CheckRT's gates (:835-891): squareError1 / squareError2 > th2, z1 / z2 <= 0, cosParallax < 0.99998
+COS_GATE = 0.99998
+Z_BAND = 2.0        # the depth gate is 0: "within a factor 2" has no meaning there, so its band is |z| <= 2 baselines (t21 has unit length)
+RT_STAGE = dict(z1=2, z2=3, e1=4, e2=5)   # the smallest gate record of a match that reached the gate on this quantity
+
+
+def same_rt(a, b):
+    """The two models ran CheckRT on the same thing: one model chosen, its winning row equal, as many motions."""
+    if a.model != b.model or a.model == 0 or a.n_motions != b.n_motions or a.n_motions == 0:
+        return False
+    return a.bestH == b.bestH if a.model == 1 else a.bestF == b.bestF
+
+
+def measured_rt_differences(pairs):
+    """The largest float32-to-float64 difference of CheckRT's gate quantities over (float32 model, float64 model) pairs, each over the
+    matches that reach the gate in the float64 model and whose float64 value lies within a factor 2 of the gate: relative for e1 / e2
+    (th2 / 2 .. 2 th2); absolute for cosP, the band taken on what the gate measures, 1 - cosP within a factor 2 of 1 - 0.99998; absolute
+    for z over |z| <= Z_BAND where the depth gates are live (cosP < 0.99998) -> dict(e, cos, z) and the matches in each band."""
+    w, cnt = dict(e=0.0, cos=0.0, z=0.0), dict(e=0, cos=0, z=0)
+    for a, b in pairs:
+        if not same_rt(a, b):
+            continue
+        for k in range(b.n_motions):
+            qa, qb, g = a.rt[k], b.rt[k], b.gates[k]
+            with np.errstate(all="ignore"):
+                for name in ("e1", "e2"):
+                    x, y = qa[name].astype(f64), qb[name]
+                    band = (g >= RT_STAGE[name]) & (y >= qb.th2 / 2) & (y <= 2 * qb.th2) & np.isfinite(x)
+                    if band.any():
+                        w["e"] = max(w["e"], float((np.abs(x - y) / y)[band].max())); cnt["e"] += int(band.sum())
+                low = qb.cosP < COS_GATE
+                for name in ("z1", "z2"):
+                    x, y = qa[name].astype(f64), qb[name]
+                    band = (g >= RT_STAGE[name]) & low & (np.abs(y) <= Z_BAND) & np.isfinite(x)
+                    if band.any():
+                        w["z"] = max(w["z"], float(np.abs(x - y)[band].max())); cnt["z"] += int(band.sum())
+                x, y = qa.cosP.astype(f64), qb.cosP
+                band = (g >= 2) & (1 - y >= (1 - COS_GATE) / 2) & (1 - y <= 2 * (1 - COS_GATE)) & np.isfinite(x)
+                if band.any():
+                    w["cos"] = max(w["cos"], float(np.abs(x - y)[band].max())); cnt["cos"] += int(band.sum())
+    return w, cnt
+
+
+def open_matches(a, b, margins):
+    """(n_motions of a, N) bool: the matches of each motion hypothesis on which the float32 model's CheckRT record is not binding.
+    A match is open when the two models give it different gate records, or when a float64 gate quantity it reaches lies within its
+    margin of the gate (margins: dict(e relative, cos absolute, z absolute), 4 x measured_rt_differences).  Where the two models did
+    not run CheckRT on the same thing (same_rt) every match is open.  Formed from the models alone."""
+    if a.n_motions == 0:
+        return np.zeros((0, a.N), bool)
+    if not same_rt(a, b):
+        return np.ones((a.n_motions, a.N), bool)
+    op = a.gates != b.gates
+    for k in range(b.n_motions):
+        q, g = b.rt[k], b.gates[k]
+        with np.errstate(all="ignore"):
+            op[k] |= (g >= RT_STAGE["e1"]) & (np.abs(q.e1 - q.th2) <= margins["e"] * q.th2)
+            op[k] |= (g >= RT_STAGE["e2"]) & (np.abs(q.e2 - q.th2) <= margins["e"] * q.th2)
+            low = q.cosP < COS_GATE                      # a depth gate is live; a cosP near its gate opens the match by itself
+            op[k] |= (g >= RT_STAGE["z1"]) & low & (np.abs(q.z1) <= margins["z"])
+            op[k] |= (g >= RT_STAGE["z2"]) & low & (np.abs(q.z2) <= margins["z"])
+            op[k] |= (g >= 2) & (np.abs(q.cosP - COS_GATE) <= margins["cos"])
+    return op
+
+
+def rank_neighbours(r, k):
+    """The parallax CheckRT would return for motion k had it taken rank want - 1 / want / want + 1 of the sorted cosines (None where the
+    rank does not exist), want = min(50, nGood - 1)."""
+    srt = r.rt[k].sorted
+    n = len(srt)
+    if n == 0:
+        return None, None, None
+    want = min(50, n - 1)
+    ft = srt.dtype.type
+    return tuple(parallax_of(srt[j], ft) if 0 <= j < n else None for j in (want - 1, want, want + 1))
+
+
 def unit(M):
     """A homogeneous matrix (or a batch) with unit Frobenius norm and a positive largest entry: what H21 / F21 are compared as."""
     M = np.asarray(M, f64)
@@ -627,11 +730,12 @@ def unit(M):
     return (flat * sgn).reshape(M.shape)
 
 
-def measured_output_differences(names=CASES):
-    """max |float32 model - float64 model| of the best H21 / F21 (as unit()), R21, t21 and vP3D over the committed cases."""
+def measured_output_differences(names=CASES, case_fn=None):
+    """max |float32 model - float64 model| of the best H21 / F21 (as unit()), R21, t21 and vP3D over the committed cases (or over
+    `names` as `case_fn` makes them)."""
     w = dict(M=0.0, R=0.0, t=0.0, P=0.0)
     for n in names:
-        _, _, a, b = case(n)
+        _, _, a, b = (case_fn or case)(n)
         if a.bestH == b.bestH and a.bestH >= 0:
             w["M"] = max(w["M"], float(np.abs(unit(a.H21[a.bestH]) - unit(b.H21[b.bestH])).max()))
         if a.bestF == b.bestF and a.bestF >= 0:
