@@ -1271,6 +1271,54 @@ int ba_solve_hb(ba_handle* h, const ba_problem* p, const volatile uint8_t* stop_
 int ba_set_profiling(ba_handle* h, int on);
 int ba_get_phase_ms(ba_handle* h, double* ms /* 5 */);
 
+/* ---------------------------------------------------------------- welding BA (Optimizer::LocalBundleAdjustment of a map merge) */
+
+/* void Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF, bool*),
+ * numerical core (S/Optimizer.cc:6305-6983, called by LoopClosing::MergeLocal at S/LoopClosing.cc:1814): a ba_problem solved in two
+ * rounds with an outlier level between them.
+ *   round 1   optimize(ba.iterations) with Huber kernels on every edge (sqrt 5.99 / sqrt 7.815, S/Optimizer.cc:6459-6460): exactly
+ *             ba_solve with robust = 1
+ *   levels    only if the flag is down after round 1 (S/Optimizer.cc:6610-6647): an edge whose chi2 -- of round 1's LAST error
+ *             evaluation, which may be a rejected trial's -- exceeds chi2_mono (ur < 0) / chi2_stereo, or whose depth in its camera
+ *             is not positive at round 1's estimate, goes to level 1; every edge loses its kernel
+ *   round 2   optimize(iterations_second) over the level-0 edges alone, no kernels, from round 1's float64 estimate; structure,
+ *             lambda's first value and the rejection factor start over.  A point or free keyframe without a level-0 edge keeps
+ *             round 1's estimate.  Nothing runs when no edge is left at level 0 or iterations_second <= 0.
+ * The levels, the compaction of the edge list and round 2 stay on the device. */
+typedef struct ba_weld_problem {
+  uint32_t   struct_size;        /* sizeof(ba_weld_problem) */
+  ba_problem ba;                 /* ba.iterations: round 1's count (5).  ba.robust is NOT READ: round 1 is always robust, round 2 never */
+  int32_t    iterations_second;  /* round 2's count (10) */
+  double     chi2_mono, chi2_stereo;   /* 5.991 and 7.815: both the level test and the caller's final check; finite and > 0 */
+} ba_weld_problem;
+
+typedef struct ba_weld_result {
+  uint32_t  struct_size;         /* sizeof(ba_weld_result) */
+  /* Round 1's iters / chi2_initial / chi2_final / trace; poses and points: the final estimate; point_included: round 1's meaning
+   * (the point has an edge at all).  edge_chi2 / edge_depth_pos are what the reference's final check reads (S/Optimizer.cc:6665-6705):
+   * chi2 of round 2's last evaluation for a level-0 edge, round 1's for a level-1 edge (it was not active in round 2); the depth
+   * test of every edge with the final estimate.  Both arrays may be NULL. */
+  ba_result ba;
+  uint8_t*  edge_level;          /* n_edges, required: 0 or 1; all 0 when no level was assigned (rounds_run == 0, or the flag up after round 1) */
+  int32_t   n_level1;
+  int32_t   rounds_run;          /* 0: no iteration ran at all; 1: round 1 alone; 2: round 2 was entered */
+  int32_t   iters_second;
+  double    chi2_initial_second, chi2_final_second;
+  double*   trace_second;        /* optional: round 2's rows, as ba_result.trace */
+  int32_t   trace_second_cap, trace_second_len;
+} ba_weld_result;
+
+/* stop_flag / stop_bool as in the ba_solve family; the count of evaluated trials behind the -k form runs on through both rounds.
+ * Up before the call: status LBA_ABORTED_BEFORE_OPT, the input comes back through the float32 conversions, rounds_run = 0 (the
+ * reference returns without writing anything back).  Up after round 1: no levels, no round 2.  Refused before a device is selected
+ * (ORBG_BAD_ARG): a short struct_size, what ba_solve refuses, thresholds that are not finite and positive, edge_level == NULL with
+ * n_edges > 0.  Called with iterations_second = 0 and no flag, `ba` comes back with the bits of ba_solve_h(robust = 1) on the same
+ * handle.  Two calls on the same input return the same bits. */
+int ba_weld_solve(const ba_weld_problem* p, const volatile int32_t* stop_flag, ba_weld_result* r);
+int ba_weld_solve_b(const ba_weld_problem* p, const volatile uint8_t* stop_bool, ba_weld_result* r);
+int ba_weld_solve_h(ba_handle* h, const ba_weld_problem* p, const volatile int32_t* stop_flag, ba_weld_result* r);
+int ba_weld_solve_hb(ba_handle* h, const ba_weld_problem* p, const volatile uint8_t* stop_bool, ba_weld_result* r);
+
 /* ---------------------------------------------------------------- essential graph (Optimizer::OptimizeEssentialGraph) */
 
 /* The Sim3 pose graph that LoopClosing::CorrectLoop optimises between the fuse and the full BA (S/LoopClosing.cc:1272, body

@@ -207,11 +207,23 @@ struct GpuOps {
   }
   // the full BA: one persistent workspace per calling thread (LoopClosing's GBA thread, or Tracking at initialisation); &mbStopGBA
   // goes through as it is (ba_solve_hb)
-  static int ba(const ba_problem& p, const volatile bool* stop, ba_result& r) {
+  static int ba_workspace(int device, ba_handle** h) {
     struct Holder { ba_handle* h = nullptr; ~Holder() { if (h) ba_destroy(h); } };
     static thread_local Holder s;
-    if (!s.h) { const int rc = ba_create(p.device, 0, 0, 0, &s.h); if (rc) return rc; }
-    return ba_solve_hb(s.h, &p, Optimizer::stop_byte(stop), &r);
+    if (!s.h) { const int rc = ba_create(device, 0, 0, 0, &s.h); if (rc) return rc; }
+    *h = s.h;
+    return ORBG_OK;
+  }
+  static int ba(const ba_problem& p, const volatile bool* stop, ba_result& r) {
+    ba_handle* h = nullptr;
+    if (const int rc = ba_workspace(p.device, &h)) return rc;
+    return ba_solve_hb(h, &p, Optimizer::stop_byte(stop), &r);
+  }
+  // the welding BA of a map merge, on the same workspace (LoopClosing's thread runs both); &mbStopGBA goes through as it is
+  static int ba_weld(const ba_weld_problem& p, const volatile bool* stop, ba_weld_result& r) {
+    ba_handle* h = nullptr;
+    if (const int rc = ba_workspace(p.ba.device, &h)) return rc;
+    return ba_weld_solve_hb(h, &p, Optimizer::stop_byte(stop), &r);
   }
   static int pose_opt(const pose_opt_problem& p, pose_opt_result& r) { return pose_optimize(&p, &r); }
   static int search_init(const FrameKey& k1, const orbm_frame_view& v1, const FrameKey& k2, const orbm_frame_view& v2, float* prev, int n_prev,
@@ -1347,6 +1359,167 @@ int GlobalBundleAdjustemnt(MapT* pMap, int nIterations = 5, bool* pbStopFlag = n
   const auto vpKFs = pMap->GetAllKeyFrames();
   const auto vpMP = pMap->GetAllMapPoints();
   return BundleAdjustment<Ops>(vpKFs, vpMP, nIterations, pbStopFlag, bUseUniqueId, nLoopKF, bRobust);
+}
+
+// void Optimizer::LocalBundleAdjustment(KeyFrame* pMainKF, vector<KeyFrame*> vpAdjustKF, vector<KeyFrame*> vpFixedKF, bool* pbStopFlag),
+// S/Optimizer.cc:6305-6983: the welding BA that LoopClosing::MergeLocal runs over the keyframes around a merge (S/LoopClosing.cc:1814).
+// The member function's body statement by statement over one ba_weld_solve, with the parts that look odd:
+//   * mnBALocalForMerge is stamped on the FIXED keyframes only (:6335); the adjusted ones get mnBALocalForKF (:6384), and the edge
+//     filter tests mnBALocalForMerge (:6491).  An adjusted keyframe contributes edges only if it carries that stamp already; otherwise
+//     the problem has free poses without edges: a points-only solve against the fixed keyframes.  Reproduced, not repaired.
+//   * vertex ids are mnUniqueId for keyframes and points alike.  Where the reference would hand g2o a duplicate id (a keyframe and a
+//     point, two keyframes) or a null vertex (an observing keyframe that carries the stamp and is in neither list) this throws.
+//   * the flag up before round 1: return, nothing written back (:6594-6596).
+// Not built: the debug counters, images and Verbose messages behind dist > 1 / bShowImages (:6590, :6760-6963: output only), and the
+// mpCamera2 observations (they throw, as in BundleAdjustment).  Returns the LBA_* status (the reference returns void).
+template <class Ops = GpuOps, class KeyFrameT>
+int LocalBundleAdjustment(KeyFrameT* pMainKF, std::vector<KeyFrameT*> vpAdjustKF, std::vector<KeyFrameT*> vpFixedKF, bool* pbStopFlag) {
+  using MapPointT = typename std::remove_pointer<typename decltype(pMainKF->GetMapPoints())::value_type>::type;
+  std::vector<MapPointT*> vpMPs;
+  long unsigned maxKFid = 0;
+  auto* pCurrentMap = pMainKF->GetMap();                                                     // :6326
+  const auto stamp = pMainKF->mnUniqueId;
+  struct KfV { unsigned long id; KeyFrameT* kf; bool fixed; };
+  std::vector<KfV> kfs;
+  auto collect_points = [&](KeyFrameT* kf) {                                                 // :6349-6358, :6398-6413
+    for (MapPointT* mp : kf->GetMapPoints())
+      if (mp && !mp->isBad() && mp->GetMap() == pCurrentMap && mp->mnBALocalForMerge != stamp) {
+        vpMPs.push_back(mp);
+        mp->mnBALocalForMerge = stamp;
+      }
+  };
+  for (KeyFrameT* kf : vpFixedKF) {                                                          // :6329-6379
+    if (kf->isBad() || kf->GetMap() != pCurrentMap) continue;
+    kf->mnBALocalForMerge = stamp;
+    kfs.push_back(KfV{kf->mnUniqueId, kf, true});
+    if (kf->mnId > maxKFid) maxKFid = kf->mnId;
+    collect_points(kf);
+  }
+  for (KeyFrameT* kf : vpAdjustKF) {                                                         // :6382-6428
+    if (kf->isBad() || kf->GetMap() != pCurrentMap) continue;
+    kf->mnBALocalForKF = stamp;                                                              // (not mnBALocalForMerge: see above)
+    kfs.push_back(KfV{kf->mnUniqueId, kf, false});
+    if (kf->mnId > maxKFid) maxKFid = kf->mnId;
+    collect_points(kf);
+  }
+  // ---- keyframe vertices in ascending id, as in BundleAdjustment above; one camera entry per distinct (camera object, five scalars)
+  std::stable_sort(kfs.begin(), kfs.end(), [](const KfV& a, const KfV& b) { return a.id < b.id; });
+  std::unordered_map<unsigned long, int32_t> kf_vertex;                                      // optimizer.vertex(id) of a keyframe
+  std::vector<float> poses(16 * kfs.size()); std::vector<uint8_t> fixed(kfs.size()); std::vector<int32_t> pose_camera(kfs.size());
+  std::vector<ba_camera> cameras;
+  struct CamKey { const void* cam; float s[5]; };
+  std::vector<CamKey> camKeys;
+  for (size_t i = 0; i < kfs.size(); i++) {
+    KeyFrameT* kf = kfs[i].kf;
+    if (!kf_vertex.emplace(kfs[i].id, (int32_t)i).second) throw std::runtime_error("orbgpu LocalBundleAdjustment (merge): two keyframe vertices with one mnUniqueId");
+    const auto Tm = kf->GetPose();
+    std::memcpy(&poses[16 * i], mat_f32(Tm), 64);
+    fixed[i] = kfs[i].fixed ? 1 : 0;
+    const CamKey key{kf->mpCamera, {kf->fx, kf->fy, kf->cx, kf->cy, kf->mbf}};
+    size_t c = 0;
+    for (; c < camKeys.size(); c++)
+      if (camKeys[c].cam == key.cam && !std::memcmp(camKeys[c].s, key.s, sizeof(key.s))) break;
+    if (c == camKeys.size()) {
+      camKeys.push_back(key);
+      ba_camera bc{};
+      bc.fx = kf->fx; bc.fy = kf->fy; bc.cx = kf->cx; bc.cy = kf->cy; bc.bf = kf->mbf;
+      if (kf->mpCamera) fill_camera(bc.model, kf->mpCamera);
+      else { bc.model.model = ORBG_CAM_PINHOLE; bc.model.fx = kf->fx; bc.model.fy = kf->fy; bc.model.cx = kf->cx; bc.model.cy = kf->cy; }
+      cameras.push_back(bc);
+    }
+    pose_camera[i] = (int32_t)c;
+  }
+  // ---- point vertices (:6464-6586): the collected points that are not bad NOW, in ascending id; `created` keeps the reference's order
+  struct PtV { unsigned long id; MapPointT* mp; size_t created; };
+  std::vector<PtV> pts_v;
+  for (size_t i = 0; i < vpMPs.size(); i++)
+    if (!vpMPs[i]->isBad()) pts_v.push_back(PtV{(unsigned long)vpMPs[i]->mnUniqueId, vpMPs[i], i});
+  std::stable_sort(pts_v.begin(), pts_v.end(), [](const PtV& a, const PtV& b) { return a.id < b.id; });
+  std::vector<float> pts(3 * pts_v.size());
+  std::vector<lba_edge> edges;
+  struct EdgeRef { KeyFrameT* kf; MapPointT* mp; size_t created; };                          // vpEdgeKFMono / vpMapPointEdgeMono and the stereo pair
+  std::vector<EdgeRef> edge_ref;
+  struct ObsRef { unsigned long vid; KeyFrameT* kf; int li; int32_t col; };
+  std::vector<ObsRef> obs;
+  for (size_t j = 0; j < pts_v.size(); j++) {
+    MapPointT* mp = pts_v[j].mp;
+    if (kf_vertex.count(pts_v[j].id) || (j > 0 && pts_v[j - 1].id == pts_v[j].id))
+      throw std::runtime_error("orbgpu LocalBundleAdjustment (merge): a point vertex with the mnUniqueId of another vertex");
+    const auto Xm = mp->GetWorldPos();
+    std::memcpy(&pts[3 * j], mat_f32(Xm), 12);
+    obs.clear();
+    for (const auto& ob : mp->GetObservations()) {
+      KeyFrameT* kf = ob.first;
+      const int li = std::get<0>(ob.second);
+      if (kf->isBad() || kf->mnId > maxKFid || kf->mnBALocalForMerge != stamp || li < 0 || !kf->GetMapPoint(li)) continue;       // :6491
+      const auto it = kf_vertex.find(kf->mnUniqueId);
+      if (it == kf_vertex.end() || kfs[it->second].kf != kf)
+        throw std::runtime_error("orbgpu LocalBundleAdjustment (merge): an observing keyframe carries the stamp but has no vertex");
+      if (kf->mpCamera2 && std::get<1>(ob.second) != -1) throw std::runtime_error("orbgpu LocalBundleAdjustment (merge): mpCamera2 observations are not supported");
+      obs.push_back(ObsRef{kf->mnUniqueId, kf, li, it->second});
+    }
+    std::sort(obs.begin(), obs.end(), [](const ObsRef& a, const ObsRef& b) { return a.vid < b.vid; });
+    for (const ObsRef& o : obs) {
+      const auto& kp = o.kf->mvKeysUn[o.li];
+      edges.push_back(lba_edge{o.col, (int32_t)j, kp.pt.x, kp.pt.y, o.kf->mvuRight[o.li] /* < 0: monocular (:6498) */, o.kf->mvInvLevelSigma2[kp.octave]});
+      edge_ref.push_back(EdgeRef{o.kf, mp, pts_v[j].created});
+    }
+  }
+  ba_weld_problem P{};
+  P.struct_size = sizeof(P);
+  P.ba.n_poses = (int32_t)kfs.size(); P.ba.n_points = (int32_t)pts_v.size(); P.ba.n_edges = (int32_t)edges.size(); P.ba.n_cameras = (int32_t)cameras.size();
+  P.ba.poses = poses.data(); P.ba.pose_fixed = fixed.data(); P.ba.pose_camera = pose_camera.data(); P.ba.points = pts.data();
+  P.ba.edges = edges.data(); P.ba.cameras = cameras.data();
+  P.ba.iterations = 5; P.ba.robust = 1;                                                      // :6599 (robust: not read, round 1 always is)
+  P.ba.device = 0;
+  P.iterations_second = 10;                                                                  // :6653
+  P.chi2_mono = 5.991; P.chi2_stereo = 7.815;                                                // :6620,6640 and :6675,6695
+  std::vector<float> oposes(poses.size()), opts(pts.size());
+  std::vector<double> chi2(edges.size() + 1);
+  std::vector<uint8_t> depth_pos(edges.size() + 1), level(edges.size() + 1);
+  ba_weld_result R{};
+  R.struct_size = sizeof(R);
+  R.ba.poses = oposes.data(); R.ba.points = opts.data(); R.ba.edge_chi2 = chi2.data(); R.ba.edge_depth_pos = depth_pos.data();
+  R.edge_level = level.data();
+  check(Ops::ba_weld(P, pbStopFlag, R), "LocalBundleAdjustment (merge)");
+  if (R.ba.status == LBA_ABORTED_BEFORE_OPT) return R.ba.status;                             // :6594-6596: nothing is written back
+  // ---- the final check (:6665-6705): the monocular edges, then the stereo ones, each in creation order
+  std::vector<size_t> order(edges.size());
+  for (size_t k = 0; k < order.size(); k++) order[k] = k;
+  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    const bool sa = edges[a].ur >= 0, sb = edges[b].ur >= 0;
+    return sa != sb ? sb : edge_ref[a].created < edge_ref[b].created;
+  });
+  std::vector<std::pair<KeyFrameT*, MapPointT*>> vToErase;
+  for (size_t k : order) {
+    if (edge_ref[k].mp->isBad()) continue;
+    if (chi2[k] > (edges[k].ur < 0 ? P.chi2_mono : P.chi2_stereo) || !depth_pos[k]) vToErase.push_back(std::make_pair(edge_ref[k].kf, edge_ref[k].mp));
+  }
+  // ---- write-back (:6708-6982)
+  auto& mapMutex = pMainKF->GetMap()->mMutexMapUpdate;
+  std::unique_lock<typename std::remove_reference<decltype(mapMutex)>::type> lock(mapMutex);
+  for (const auto& ke : vToErase) {                                                          // :6722-6729
+    ke.first->EraseMapPointMatch(ke.second);
+    ke.second->EraseObservation(ke.first);
+  }
+  for (KeyFrameT* kf : vpAdjustKF) {                                                         // :6785-6966
+    if (kf->isBad()) continue;
+    const auto it = kf_vertex.find(kf->mnUniqueId);
+    if (it == kf_vertex.end() || kfs[it->second].kf != kf)
+      throw std::runtime_error("orbgpu LocalBundleAdjustment (merge): an adjusted keyframe of another map has no vertex to read");
+    decltype(kf->GetPose()) T; make_mat(T, 4, 4, &oposes[16 * (size_t)it->second]);
+    kf->SetPose(T, true);                                                                    // :6965
+  }
+  std::vector<int32_t> pt_of(vpMPs.size(), -1);
+  for (size_t j = 0; j < pts_v.size(); j++) pt_of[pts_v[j].created] = (int32_t)j;
+  for (size_t i = 0; i < vpMPs.size(); i++) {                                                // :6970-6981
+    MapPointT* mp = vpMPs[i];
+    if (mp->isBad() || pt_of[i] < 0) continue;
+    decltype(mp->GetWorldPos()) X; make_mat(X, 3, 1, &opts[3 * (size_t)pt_of[i]]);
+    mp->SetWorldPos(X, true);
+    mp->UpdateNormalAndDepth();
+  }
+  return R.ba.status;
 }
 
 // int Optimizer::PoseOptimization(Frame *pFrame), S/Optimizer.cc:964-1278: the rectified-stereo / mono frames of every BASELINE

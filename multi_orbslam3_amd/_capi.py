@@ -153,6 +153,19 @@ class BaResult(C.Structure):
                 ("chi2_final", C.c_double), ("trace", C.c_void_p), ("trace_cap", C.c_int32), ("trace_len", C.c_int32)]
 
 
+class BaWeldProblem(C.Structure):
+    """ba_weld_problem: `ba` is round 1's problem (its robust field is not read), then round 2's count and the two chi2 thresholds."""
+    _fields_ = [("struct_size", C.c_uint32), ("ba", BaProblem), ("iterations_second", C.c_int32), ("chi2_mono", C.c_double),
+                ("chi2_stereo", C.c_double)]
+
+
+class BaWeldResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("ba", BaResult), ("edge_level", C.c_void_p), ("n_level1", C.c_int32),
+                ("rounds_run", C.c_int32), ("iters_second", C.c_int32), ("chi2_initial_second", C.c_double),
+                ("chi2_final_second", C.c_double), ("trace_second", C.c_void_p), ("trace_second_cap", C.c_int32),
+                ("trace_second_len", C.c_int32)]
+
+
 BA_MAX_FREE_POSES = 1365
 
 # Optimizer::OptimizeEssentialGraph (include/orbgpu.h: eg_vertex, eg_edge, eg_point)
@@ -360,7 +373,8 @@ EXPORTED_SYMBOLS = [
 # declarations under the prefixes above only.  build() and load() treat both lists alike; tests/test_two_view_cpu.py holds this one.
 INITIALISER_SYMBOLS = ["orbi_two_view_resolve_draws", "orbi_two_view_reconstruct"]
 # The full bundle adjustment (prefix ba_), likewise a list of its own; tests/test_full_ba_cpu.py holds it against the header.
-FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solve_h", "ba_solve_hb", "ba_set_profiling", "ba_get_phase_ms"]
+FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solve_h", "ba_solve_hb", "ba_set_profiling", "ba_get_phase_ms",
+                   "ba_weld_solve", "ba_weld_solve_b", "ba_weld_solve_h", "ba_weld_solve_hb"]
 # The essential graph (prefix eg_), likewise; tests/test_essential_graph_cpu.py holds it against the header.
 ESSENTIAL_GRAPH_SYMBOLS = ["eg_solve", "eg_set_profiling", "eg_get_phase_ms"]
 

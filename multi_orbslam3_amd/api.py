@@ -982,6 +982,15 @@ class Optimizer:
             p.robust = int(bool(bRobust))
         return self._ba.solve(p, pbStopFlag, out=out)
 
+    def MergeLocalBundleAdjustment(self, problem, pbStopFlag=None, trace_cap=64, out=None):
+        """void Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, pbStopFlag) (S/Optimizer.cc:6305-6983, the welding BA
+        of LoopClosing::MergeLocal), numerical core: a robust round, the outlier level, a second round over the level-0 edges without
+        kernels -- all on the device (ba_weld_solve_h).  problem: views.ba_weld_problem(...)[0]; pbStopFlag as in BundleAdjustment.
+        Returns a views.BaWeldOutput: the BundleAdjustment result's fields plus edge_level, rounds_run, both traces and to_erase."""
+        if getattr(self, "_ba", None) is None:
+            self._ba = FullBA(self.device)
+        return self._ba.weld(problem, pbStopFlag, trace_cap=trace_cap, out=out)
+
 
 class FullBA:
     """Persistent workspace of Optimizer::BundleAdjustment (include/orbgpu.h: ba_create ... ba_solve_hb)."""
@@ -1010,6 +1019,23 @@ class FullBA:
         sp = None if pbStopFlag is None else C.c_void_p(pbStopFlag.ctypes.data)
         fn = self.lib.ba_solve_hb if Optimizer._is_bool_flag(pbStopFlag) else self.lib.ba_solve_h
         capi.check(fn(self.h, C.byref(problem), sp, C.byref(out.c)), "ba_solve_h")
+        return out
+
+    def weld(self, problem, pbStopFlag=None, trace_cap=64, out=None):
+        """ba_weld_solve_h / ba_weld_solve_hb on this workspace; problem: views.ba_weld_problem(...)[0]."""
+        b = problem.ba
+        if out is None:
+            out = views.BaWeldOutput(b.n_poses, b.n_points, b.n_edges, trace_cap, problem.chi2_mono, problem.chi2_stereo)
+        else:
+            out.c.trace_len = 0
+            out.w.trace_second_len = 0
+            out.chi2_mono, out.chi2_stereo = problem.chi2_mono, problem.chi2_stereo
+        sp = None if pbStopFlag is None else C.c_void_p(pbStopFlag.ctypes.data)
+        fn = self.lib.ba_weld_solve_hb if Optimizer._is_bool_flag(pbStopFlag) else self.lib.ba_weld_solve_h
+        capi.check(fn(self.h, C.byref(problem), sp, C.byref(out.w)), "ba_weld_solve_h")
+        # (mono / stereo of every edge, for to_erase's order)
+        out._ur = (np.frombuffer(C.string_at(b.edges, b.n_edges * capi.EDGE_DTYPE.itemsize), capi.EDGE_DTYPE)["ur"].copy()
+                   if b.n_edges > 0 else np.zeros(0, np.float32))
         return out
 
     def set_profiling(self, on=True):

@@ -22,6 +22,12 @@
 //     k_ba_update   thread/vertex  back-substitution, trial state, computeScale terms
 //     k_ba_errors + k_ba_finish   robust chi2, scale, largest diagonal -> the record the host reads
 // Every sum has a fixed order: two calls on the same input return the same bits.
+//
+// ba_weld_solve() is the welding BA of LoopClosing::MergeLocal (Optimizer::LocalBundleAdjustment(pMainKF, vpAdjustKF, vpFixedKF, ...),
+// S/Optimizer.cc:6305-6983) on the same run: round 1 is the solve above with kernels on, then on the device
+//     k_ba_weld_classify  thread/edge  level by chi2 threshold and depth test; k_ba_scan of the keep flags;
+//     k_ba_weld_compact   thread/edge  the level-0 edges, in order, into a second edge list + their origins
+// round 2 = structure + optimize over that list with kernels off, and k_ba_weld_scatter puts its chi2 back into the full list.
 
 #include <time.h>
 #include <unistd.h>
@@ -632,6 +638,41 @@ __global__ __launch_bounds__(256) void k_ba_depth(int NE, const lba_edge* __rest
 
 __global__ void k_ba_set_ok(int* ok) { *ok = 1; }
 
+// ------------------------------------------------------------------------------------------ welding BA: between the rounds
+
+// S/Optimizer.cc:6610-6647: level 1 for an edge whose chi2 (of round 1's last evaluation) exceeds its threshold or whose depth is
+// not positive at the current estimate; keep = 1 for the edges that stay at level 0
+__global__ __launch_bounds__(256) void k_ba_weld_classify(int NE, const lba_edge* __restrict__ edges, const PoseQ* __restrict__ poses,
+                                                          const double* __restrict__ points, const double* __restrict__ chi2, double th_mono,
+                                                          double th_stereo, uint8_t* __restrict__ level, int* __restrict__ keep) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= NE) return;
+  const lba_edge e = edges[k];
+  double rr[3];
+  quat_rotate(poses[e.pose].q, points + 3 * (size_t)e.point, rr);
+  const bool depth_pos = rr[2] + poses[e.pose].t[2] > 0.0;
+  const bool out = chi2[k] > (e.ur < 0 ? th_mono : th_stereo) || !depth_pos;
+  level[k] = out ? 1 : 0;
+  keep[k] = out ? 0 : 1;
+}
+// the level-0 edges in their order (offset = exclusive scan of keep): a subsequence keeps "the edges of a point are consecutive,
+// point never decreases"; origin[j] = the edge compacted edge j came from
+__global__ __launch_bounds__(256) void k_ba_weld_compact(int NE, const lba_edge* __restrict__ edges, const int* __restrict__ keep,
+                                                         const int* __restrict__ offset, lba_edge* __restrict__ kept, int* __restrict__ origin) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= NE || !keep[k]) return;
+  const int j = offset[k];
+  kept[j] = edges[k];
+  origin[j] = k;
+}
+// round 2's chi2 back to the full list: the level-1 edges keep round 1's value
+__global__ __launch_bounds__(256) void k_ba_weld_scatter(int n_kept, const int* __restrict__ origin, const double* __restrict__ chi2_kept,
+                                                         double* __restrict__ chi2) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_kept) return;
+  chi2[origin[j]] = chi2_kept[j];
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------- handle
@@ -655,6 +696,11 @@ struct ba_handle {
   DevBuf<CamRig> d_cams;
   DevBuf<double> d_chi2, d_partial, d_EB, d_Hll, d_bl, d_Hpp, d_bp, d_Dinv, d_Db, d_S, d_bs, d_x, d_St, d_wfac, d_wide, d_scale_v;
   DevBuf<uint8_t> d_depth;
+  // welding BA: the level-0 edges and their chi2 (exchanged with d_edges / d_chi2 while round 2 runs), levels, keep flags, their scan, origins
+  DevBuf<lba_edge> d_edges_kept;
+  DevBuf<double> d_chi2_kept;
+  DevBuf<uint8_t> d_level;
+  DevBuf<int> d_keep, d_keep_off, d_origin;
   DevBuf<BaRec> d_rec;
   PinnedBuf<BaRec> rec;
   PinnedBuf<long long> total_h;
@@ -720,9 +766,10 @@ struct BaRun {
   bool use_mfma = false, use_xcd = false, use_wide = false;
   int cur = 0;
   int trials = 0;
+  int robust;                          // Huber kernels on every edge: the value of the round that is running
 
-  BaRun(ba_handle* h_, const ba_problem* p_, ba_result* r_, StopRef ref, int nP_)
-      : h(h_), st(h_->stream), p(p_), r(r_), NP(p_->n_poses), NX(p_->n_points), NE(p_->n_edges), nP(nP_), n(6 * nP_) {
+  BaRun(ba_handle* h_, const ba_problem* p_, ba_result* r_, StopRef ref, int nP_, int robust_)
+      : h(h_), st(h_->stream), p(p_), r(r_), NP(p_->n_poses), NX(p_->n_points), NE(p_->n_edges), nP(nP_), n(6 * nP_), robust(robust_ ? 1 : 0) {
     stop.ref = ref;
     hb.delta_mono = (float)std::sqrt(5.99); hb.dsqr_mono = hb.delta_mono * hb.delta_mono;           // S/Optimizer.cc:131-132: 5.99 here, not the local BA's 5.991
     hb.delta_stereo = (float)std::sqrt(7.815); hb.dsqr_stereo = hb.delta_stereo * hb.delta_stereo;
@@ -939,13 +986,13 @@ struct BaRun {
     ph_begin(kPhLin);
     if (NE > 0) {
       hipLaunchKernelGGL(k_ba_lin, dim3(n_blocks_e), dim3(256), 0, st, NE, h->d_edges.p, h->d_poses[buf].p, h->d_points[buf].p, h->d_pose_cam.p,
-                         h->d_cams.p, p->robust ? 1 : 0, hb, h->d_chi2.p, h->d_partial.p, h->d_EB.p);
+                         h->d_cams.p, robust, hb, h->d_chi2.p, h->d_partial.p, h->d_EB.p);
     }
     if (NX > 0)
       hipLaunchKernelGGL(k_ba_points, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_pt_start.p, h->d_pt_end.p, h->d_EB.p, h->d_Hll.p, h->d_bl.p);
     if (nP > 0)
       hipLaunchKernelGGL(k_ba_poses, dim3(nP), dim3(256), 0, st, h->d_row_start.p, h->d_row_edges.p, h->d_edges.p, h->d_poses[buf].p,
-                         h->d_points[buf].p, h->d_pose_cam.p, h->d_cams.p, p->robust ? 1 : 0, hb, h->d_chi2.p, h->d_Hpp.p, h->d_bp.p);
+                         h->d_points[buf].p, h->d_pose_cam.p, h->d_cams.p, robust, hb, h->d_chi2.p, h->d_Hpp.p, h->d_bp.p);
     hipLaunchKernelGGL(k_ba_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, 0, h->d_scale_v.p, nP, h->d_Hpp.p, NX, h->d_Hll.p,
                        h->d_pt_start.p, h->d_pt_end.p, (const int*)nullptr, h->d_rec.p);
     ph_end();
@@ -987,7 +1034,7 @@ struct BaRun {
                        h->d_poses[to].p, h->d_points[to].p, h->d_scale_v.p);
     if (NE > 0)
       hipLaunchKernelGGL(k_ba_errors, dim3(n_blocks_e), dim3(256), 0, st, NE, h->d_edges.p, h->d_poses[to].p, h->d_points[to].p, h->d_pose_cam.p,
-                         h->d_cams.p, p->robust ? 1 : 0, hb, h->d_chi2.p, h->d_partial.p);
+                         h->d_cams.p, robust, hb, h->d_chi2.p, h->d_partial.p);
     hipLaunchKernelGGL(k_ba_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, NP + NX, h->d_scale_v.p, 0, (const double*)nullptr, 0,
                        (const double*)nullptr, h->d_pt_start.p, h->d_pt_end.p, h->d_ok.p, h->d_rec.p);
     ph_end();
@@ -1058,7 +1105,7 @@ bool ba_runs_no_iteration(const ba_problem* p, StopRef ref) {
 }
 
 int ba_attempt(ba_handle* h, const ba_problem* p, StopRef ref, ba_result* r, int nP) {
-  BaRun run(h, p, r, ref, nP);
+  BaRun run(h, p, r, ref, nP, p->robust);
   int rc;
   r->status = LBA_APPLIED; r->iters = 0; r->trace_len = 0; r->chi2_initial = r->chi2_final = 0;
   if (run.stop()) r->status = LBA_ABORTED_BEFORE_OPT;
@@ -1111,6 +1158,144 @@ int ba_solve_once(const ba_problem* p, StopRef ref, ba_result* r) {
   return rc;
 }
 
+// ---------------------------------------------------------------------------------------------- welding BA
+
+int weld_validate(const ba_weld_problem* wp, const ba_weld_result* wr, int* n_free) {
+  if (!wp || !wr) return ORBG_BAD_ARG;
+  if (wp->struct_size < sizeof(ba_weld_problem) || wr->struct_size < sizeof(ba_weld_result)) return ORBG_BAD_ARG;
+  if (!std::isfinite(wp->chi2_mono) || !std::isfinite(wp->chi2_stereo) || !(wp->chi2_mono > 0) || !(wp->chi2_stereo > 0)) return ORBG_BAD_ARG;
+  if (wr->trace_second && wr->trace_second_cap < 0) return ORBG_BAD_ARG;
+  const int rc = ba_validate(&wp->ba, &wr->ba, n_free);
+  if (rc) return rc;
+  if (!wr->edge_level && wp->ba.n_edges > 0) return ORBG_BAD_ARG;
+  return ORBG_OK;
+}
+
+template <class T>
+void exchange(DevBuf<T>& a, DevBuf<T>& b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+
+// While round 2 runs, the run's edge list, its count and the per-edge chi2 are those of the level-0 edges, and the trace it writes
+// is the second one: the handle's buffers and the result's round fields are exchanged here and put back on every way out.
+struct WeldSecondRound {
+  BaRun& run;
+  ba_weld_result* const wr;
+  const int NE_all, blocks_all, robust_first;
+  const ba_result first;
+  WeldSecondRound(BaRun& run_, ba_weld_result* wr_, int n_kept)
+      : run(run_), wr(wr_), NE_all(run_.NE), blocks_all(run_.n_blocks_e), robust_first(run_.robust), first(*run_.r) {
+    exchange(run.h->d_edges, run.h->d_edges_kept);
+    exchange(run.h->d_chi2, run.h->d_chi2_kept);
+    run.NE = n_kept; run.n_blocks_e = (n_kept + 255) / 256; run.robust = 0;
+    ba_result* r = run.r;
+    r->trace = wr->trace_second; r->trace_cap = wr->trace_second ? wr->trace_second_cap : 0; r->trace_len = 0;
+    r->chi2_initial = r->chi2_final = 0;
+  }
+  ~WeldSecondRound() {
+    ba_result* r = run.r;
+    wr->chi2_initial_second = r->chi2_initial; wr->chi2_final_second = r->chi2_final; wr->trace_second_len = r->trace_len;
+    r->trace = first.trace; r->trace_cap = first.trace_cap; r->trace_len = first.trace_len;
+    r->chi2_initial = first.chi2_initial; r->chi2_final = first.chi2_final;
+    run.NE = NE_all; run.n_blocks_e = blocks_all; run.robust = robust_first;
+    exchange(run.h->d_edges, run.h->d_edges_kept);
+    exchange(run.h->d_chi2, run.h->d_chi2_kept);
+  }
+};
+
+int weld_attempt(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_weld_result* wr, int nP) {
+  const ba_problem* p = &wp->ba;
+  ba_result* r = &wr->ba;
+  BaRun run(h, p, r, ref, nP, 1);                  // round 1: Huber kernels on every edge, whatever p->robust says
+  int rc;
+  r->status = LBA_APPLIED; r->iters = 0; r->trace_len = 0; r->chi2_initial = r->chi2_final = 0;
+  wr->n_level1 = 0; wr->rounds_run = 0; wr->iters_second = 0; wr->trace_second_len = 0;
+  wr->chi2_initial_second = wr->chi2_final_second = 0;
+  if (p->n_edges > 0) memset(wr->edge_level, 0, (size_t)p->n_edges);
+  if (run.stop()) r->status = LBA_ABORTED_BEFORE_OPT;
+  run.stop.past_precheck = true;
+  run.initial_state();
+  if (ba_runs_no_iteration(p, ref)) return run.finish_without_iterations();       // (uses the handle's host arrays only)
+  if ((rc = select_device(h->device))) return rc;
+  if (h->prof_on) {
+    for (double& m : h->phase_ms) m = 0;
+    h->ev_n = 0;
+    for (hipEvent_t& e : h->ev) if (!e) ORBG_HIP(hipEventCreate(&e));
+  }
+  StreamDrain drain{h->stream};
+  if ((rc = run.buffers()) || (rc = run.upload()) || (rc = run.structure())) return rc;
+  int done = 0;
+  if ((rc = run.optimize(p->iterations, &done))) return rc;
+  r->iters = done;
+  if (done == 0) return run.finish_without_iterations();
+  wr->rounds_run = 1;
+  const int NE = run.NE;
+  if (!run.stop()) {                               // S/Optimizer.cc:6606: bDoMore
+    const size_t sNE = (size_t)NE;
+    if ((rc = h->d_level.reserve(sNE)) || (rc = h->d_keep.reserve(sNE)) || (rc = h->d_keep_off.reserve(sNE + 1)) ||
+        (rc = h->d_origin.reserve(sNE)) || (rc = h->d_edges_kept.reserve(sNE)) || (rc = h->d_chi2_kept.reserve(sNE)))
+      return rc;
+    run.ph_begin(kPhStructure);
+    hipLaunchKernelGGL(k_ba_weld_classify, dim3(run.n_blocks_e), dim3(256), 0, run.st, NE, h->d_edges.p, h->d_poses[run.cur].p,
+                       h->d_points[run.cur].p, h->d_chi2.p, wp->chi2_mono, wp->chi2_stereo, h->d_level.p, h->d_keep.p);
+    hipLaunchKernelGGL(k_ba_scan, dim3(1), dim3(1024), 0, run.st, NE, h->d_keep.p, h->d_keep_off.p, h->d_total.p);
+    hipLaunchKernelGGL(k_ba_weld_compact, dim3(run.n_blocks_e), dim3(256), 0, run.st, NE, h->d_edges.p, h->d_keep.p, h->d_keep_off.p,
+                       h->d_edges_kept.p, h->d_origin.p);
+    run.ph_end();
+    ORBG_HIP(hipGetLastError());
+    ORBG_HIP(hipMemcpyAsync(wr->edge_level, h->d_level.p, sNE, hipMemcpyDeviceToHost, run.st));
+    long long kept64 = 0;
+    if ((rc = run.read_total(&kept64))) return rc;
+    if (kept64 < 0 || kept64 > NE) return ORBG_INTERNAL;
+    const int n_kept = (int)kept64;
+    wr->n_level1 = NE - n_kept;
+    if (n_kept > 0 && wp->iterations_second > 0) {
+      int done2 = 0;
+      {
+        WeldSecondRound second(run, wr, n_kept);
+        wr->rounds_run = 2;
+        if (!(rc = run.structure())) rc = run.optimize(wp->iterations_second, &done2);
+      }
+      if (rc) return rc;
+      wr->iters_second = done2;
+      if (done2 > 0) {
+        hipLaunchKernelGGL(k_ba_weld_scatter, dim3((n_kept + 255) / 256), dim3(256), 0, run.st, n_kept, h->d_origin.p, h->d_chi2_kept.p,
+                           h->d_chi2.p);
+        ORBG_HIP(hipGetLastError());
+      }
+    }
+  }
+  rc = run.download();
+  run.flush();
+  return rc;
+}
+
+int weld_solve_impl(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_weld_result* wr, int validated_free = -1) {
+  if (!h) return ORBG_BAD_ARG;
+  int nP = validated_free, rc;
+  if (nP < 0 && (rc = weld_validate(wp, wr, &nP))) return rc;
+  rc = weld_attempt(h, wp, ref, wr, nP);
+  if (rc != BaRun::kRcTimedOut) return rc;
+  // as in ba_solve_impl, for the whole call: both rounds again from the caller's untouched input on the one-workgroup kernels
+  h->ldlt_xcd = 0;
+  if (hipStreamSynchronize(h->stream) != hipSuccess) return ORBG_HIP_ERROR;
+  rc = weld_attempt(h, wp, ref, wr, nP);
+  return rc == BaRun::kRcTimedOut ? ORBG_HIP_ERROR : rc;
+}
+
+int weld_solve_once(const ba_weld_problem* wp, StopRef ref, ba_weld_result* wr) {
+  int nP = 0;
+  int rc = weld_validate(wp, wr, &nP);
+  if (rc) return rc;
+  if (ba_runs_no_iteration(&wp->ba, ref)) {
+    ba_handle host;
+    return weld_attempt(&host, wp, ref, wr, nP);
+  }
+  ba_handle* h = nullptr;
+  if ((rc = ba_create(wp->ba.device, wp->ba.n_poses, wp->ba.n_points, wp->ba.n_edges, &h))) return rc;
+  rc = weld_solve_impl(h, wp, ref, wr, nP);
+  ba_destroy(h);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" int ba_create(int device, int cap_poses, int cap_points, int cap_edges, ba_handle** out) {
@@ -1140,6 +1325,7 @@ extern "C" int ba_destroy(ba_handle* h) {
   for (DevBuf<double>* b : {&h->d_chi2, &h->d_partial, &h->d_EB, &h->d_Hll, &h->d_bl, &h->d_Hpp, &h->d_bp, &h->d_Dinv, &h->d_Db, &h->d_S, &h->d_bs,
                             &h->d_x, &h->d_St, &h->d_wfac, &h->d_wide, &h->d_scale_v})
     b->release();
+  h->d_edges_kept.release(); h->d_chi2_kept.release(); h->d_level.release(); h->d_keep.release(); h->d_keep_off.release(); h->d_origin.release();
   h->d_bitmap.release(); h->d_total.release(); h->d_items.release(); h->d_cams.release(); h->d_depth.release(); h->d_rec.release();
   h->rec.release(); h->total_h.release();
   for (hipEvent_t& e : h->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1163,6 +1349,22 @@ extern "C" int ba_solve(const ba_problem* p, const volatile int32_t* stop_flag, 
 extern "C" int ba_solve_b(const ba_problem* p, const volatile uint8_t* stop_bool, ba_result* r) {
   StopRef s; s.u8 = stop_bool;
   return ba_solve_once(p, s, r);
+}
+extern "C" int ba_weld_solve_h(ba_handle* h, const ba_weld_problem* p, const volatile int32_t* stop_flag, ba_weld_result* r) {
+  StopRef s; s.i32 = stop_flag;
+  return weld_solve_impl(h, p, s, r);
+}
+extern "C" int ba_weld_solve_hb(ba_handle* h, const ba_weld_problem* p, const volatile uint8_t* stop_bool, ba_weld_result* r) {
+  StopRef s; s.u8 = stop_bool;
+  return weld_solve_impl(h, p, s, r);
+}
+extern "C" int ba_weld_solve(const ba_weld_problem* p, const volatile int32_t* stop_flag, ba_weld_result* r) {
+  StopRef s; s.i32 = stop_flag;
+  return weld_solve_once(p, s, r);
+}
+extern "C" int ba_weld_solve_b(const ba_weld_problem* p, const volatile uint8_t* stop_bool, ba_weld_result* r) {
+  StopRef s; s.u8 = stop_bool;
+  return weld_solve_once(p, s, r);
 }
 extern "C" int ba_set_profiling(ba_handle* h, int on) {
   if (!h) return ORBG_BAD_ARG;

@@ -245,6 +245,65 @@ class BaOutput:
         return self.trace[: self.c.trace_len].copy()
 
 
+def ba_weld_problem(poses, pose_fixed, pose_camera, points, edges, cameras, iterations=5, iterations_second=10, chi2_mono=5.991,
+                    chi2_stereo=7.815, device=0):
+    """The welding BA's inputs (include/orbgpu.h: ba_weld_problem): ba_problem's arrays, round 1's and round 2's iteration counts and
+    the two chi2 thresholds of the level test (S/Optimizer.cc:6598, 6652, 6620, 6640).  Round 1 is always robust and round 2 never is:
+    there is no robust argument."""
+    inner, keep = ba_problem(poses, pose_fixed, pose_camera, points, edges, cameras, iterations=iterations, robust=True, device=device)
+    p = capi.BaWeldProblem()
+    p.struct_size = C.sizeof(capi.BaWeldProblem)
+    p.ba = inner
+    p.iterations_second, p.chi2_mono, p.chi2_stereo = int(iterations_second), float(chi2_mono), float(chi2_stereo)
+    return p, keep
+
+
+class BaWeldOutput(BaOutput):
+    """Owns the result arrays of one welding-BA call: BaOutput's (round 1's trace and counts, the final estimate, the final check's
+    edge_chi2 / edge_depth_pos) plus edge_level and round 2's trace.  `c` stays the ba_result, `w` is the ba_weld_result around it."""
+
+    def __init__(self, n_poses, n_points, n_edges, trace_cap=64, chi2_mono=5.991, chi2_stereo=7.815):
+        super().__init__(n_poses, n_points, n_edges, trace_cap)
+        self.edge_level = np.zeros(n_edges, dtype=np.uint8)
+        self.trace_second = np.zeros((trace_cap, 3), dtype=np.float64)
+        self.chi2_mono, self.chi2_stereo = float(chi2_mono), float(chi2_stereo)
+        w = capi.BaWeldResult()
+        w.struct_size = C.sizeof(capi.BaWeldResult)
+        w.ba = self.c
+        w.edge_level = capi.ptr(self.edge_level)
+        w.trace_second, w.trace_second_cap, w.trace_second_len = capi.ptr(self.trace_second), trace_cap, 0
+        self.w = w
+        self.c = w.ba                                  # (a view into w, not a copy: the library writes there)
+        self._ur = None
+
+    @property
+    def rounds_run(self):
+        return self.w.rounds_run
+
+    @property
+    def n_level1(self):
+        return self.w.n_level1
+
+    @property
+    def iters_second(self):
+        return self.w.iters_second
+
+    @property
+    def chi2_second(self):
+        return (self.w.chi2_initial_second, self.w.chi2_final_second)
+
+    def trace_second_rows(self):
+        return self.trace_second[: self.w.trace_second_len].copy()
+
+    @property
+    def to_erase(self):
+        """Indices of the edges the reference's final check rejects (S/Optimizer.cc:6665-6705: chi2 above the threshold or a depth that
+        is not positive), in its order: the monocular edges first, then the stereo ones, each in creation order."""
+        mono = self._ur < 0
+        bad = (self.edge_chi2 > np.where(mono, self.chi2_mono, self.chi2_stereo)) | (self.edge_depth_pos == 0)
+        return np.concatenate([np.flatnonzero(bad & mono), np.flatnonzero(bad & ~mono)]).astype(np.int64)
+
+
 def pose_opt_problem(Xw, u, v, ur, inv_sigma2, cam, Tcw, device=0, rig=None):
     """cam = (fx, fy, cx, cy, bf); Tcw = pFrame->mTcw (4x4); rig: camera_rig(...) or None."""
     arrs = [_c(np.asarray(Xw, np.float32).reshape(-1, 3), np.float32), _c(u, np.float32), _c(v, np.float32), _c(ur, np.float32),
