@@ -1008,6 +1008,16 @@ int orbd_database_destroy(orbd_database* d);
 int orbd_detect_n_best_candidates(orbd_database* d, const int32_t* q_word, const double* q_value, int nq, const uint8_t* connected,
                                   int32_t query_map_id, int n_candidates, float* place_score, int32_t* loop_cand, int32_t* n_loop,
                                   int32_t* merge_cand, int32_t* n_merge);
+/* vector<KeyFrame*> KeyFrameDatabase::DetectRelocalizationCandidates(Frame* F, Map* pMap), S/KeyFrameDatabase.cc:764-876, for the query
+ * BowVector of F: the first call of Tracking::Relocalization.  The device phase is the one of orbd_detect_n_best_candidates (walk,
+ * minCommonWords = int(max * 0.8f) with the strict >, float L1 scores, covisibility accumulation); what differs is honoured: no
+ * connected-keyframe exclusion; no map or bad filter before the very end, so keyframes of other maps are scored and take part in
+ * bestAccScore; the selection runs in first-encounter order without a sort and keeps acc > 0.75f * bestAccScore, then filters
+ * GetMap() != pMap and de-duplicates; isBad() is not looked at (Relocalization does that itself).  reloc_score[n_kfs] is mRelocScore,
+ * in / out like place_score: a neighbour that shares a word without reaching the word threshold contributes what an earlier query
+ * left.  cand: n_kfs entries (caller's), *n_cand of them written. */
+int orbd_detect_relocalization_candidates(orbd_database* d, const int32_t* q_word, const double* q_value, int nq,
+                                          int32_t query_map_id, float* reloc_score, int32_t* cand, int32_t* n_cand);
 
 /* ---------------------------------------------------------------- KeyFrame wire blocks */
 
@@ -1499,6 +1509,109 @@ int orbx_get_fast_kernel_stats(orbx_handle* h, double* sum_ms, int64_t* n);
  * ORBG_HOST_OCTREE=1, a per-level target too large for the node list (4 N + 8 > 2048) -- are no redos and do not count.  Read-only;
  * counts from the handle's creation, for synchronous calls and for the two-halves constructors alike. */
 int orbx_get_host_redo_count(orbx_handle* h, int64_t* n);
+
+/* ---------------------------------------------------------------- MLPnPsolver (Tracking::Relocalization's RANSAC, prefix orbp_)
+ * S/MLPnPsolver.cpp, I/MLPnPsolver.h: RANSAC over minimal sets of six matched map points, MLPnP per hypothesis (null spaces of the
+ * bearings, the 12 x 12 -- planar: 9 x 9 -- linear solve, nearest rotation, sign choice, at most five Gauss-Newton iterations), inliers
+ * by reprojection.  Every hypothesis of a call is evaluated in ONE kernel launch, all in FP64 up to CheckInliers' float statements; the
+ * serial loop of :99-216 is then replayed on the host over the inlier counts in draw order, so the outcome is the one the serial loop
+ * gives for the same draws.  Two behaviours of the reference are reproduced as they are:
+ *   - Refine() (:288-342) solves on all inliers into a local variable, never stores that pose and then counts the inliers of the
+ *     hypothesis that is still in mRi / mti: what iterate returns is the CURRENT hypothesis converted to float, with its inliers, and
+ *     exactly when its count exceeds mRansacMinInliers (strictly).  No N-point solve runs on the device.
+ *   - the loop condition (:113) is an OR: a call runs max(n_iterations, mRansacMaxIts - mnIterations) iterations unless it returns.
+ * The flat problem is what the constructor keeps per surviving match (:54-96): P2D = mvKeysUn[i].pt, sigma2 = mvLevelSigma2[octave],
+ * bearing = mpCamera->unproject(pt) divided by its z (NOT normalised to unit length: the reference does not, and the sign test uses it
+ * as it is), P3Dw = the map point, kp_index = mvKeyPointIndices with m = mvpMapPointMatches.size(), and the camera of CheckInliers'
+ * mpCamera->project(cv::Point3f).  camera.model must be ORBG_CAM_PINHOLE (S/CameraModels/Pinhole.cpp:30-33 in float); any other model
+ * is refused with ORBG_BAD_ARG.  Not provided: the covariance path (use_cov, never taken: covs(1)) and a rig's right camera (:70 skips
+ * those matches).  struct_size as in orbm_sim3_problem. */
+typedef struct orbp_mlpnp_problem {
+  uint32_t struct_size;
+  int32_t  n;                    /* N = mvP2D.size() */
+  const float* P2D;              /* n x 2 */
+  const float* sigma2;           /* n */
+  const float* bearing;          /* n x 3 */
+  const float* P3Dw;             /* n x 3 */
+  const int32_t* kp_index;       /* n, each in [0, m) */
+  int32_t  m;                    /* mvpMapPointMatches.size() */
+  orbg_camera camera;
+} orbp_mlpnp_problem;
+
+/* SetRansacParameters' arguments (:218; defaults 0.99, 8, 300, 6, 0.4, 5.991 in I/MLPnPsolver.h; Relocalization uses
+ * 0.99, 10, 300, 6, 0.5, 5.991).  min_set must be 6: computePose asserts more than five points and the sign test reads six. */
+typedef struct orbp_mlpnp_params {
+  double  probability;
+  int32_t min_inliers;
+  int32_t max_iterations;
+  int32_t min_set;
+  float   epsilon;
+  float   th2;
+} orbp_mlpnp_params;
+
+/* Outcome of one iterate().  returned: a non-empty matrix came back -- Tcw (the 4 x 4 float matrix), n_inliers = nInliers and inliers
+ * = vbInliers (m bytes through kp_index; caller's buffer, NULL: not wanted) are then set, otherwise zero.  After a return without
+ * no_more this is the hypothesis that exceeded min_inliers, which after an earlier call need not be the best one.  best_* / have_best /
+ * best_iteration (0-based mnIterations index): mBestTcw, mnBestInliers as they persist between calls.  iterations_run: iterations the
+ * serial loop ran in this call; iterations_done: mnIterations after it.
+ * hyp_*: optional per-hypothesis outputs of THIS call in draw order, for checkers (NULL: not read back): inlier counts, the planar
+ * flag, the pose in double (R: 9 per hypothesis row-major, t: 3) and bit-packed masks (ceil(n / 64) words per hypothesis, bit i & 63
+ * of word i >> 6).  They cover every hypothesis of the launch (orbp_mlpnp_iterations_of_call), also those behind the one that returned. */
+typedef struct orbp_mlpnp_result {
+  uint32_t struct_size;
+  int32_t  no_more;                /* bNoMore */
+  int32_t  returned;
+  int32_t  n_inliers;              /* nInliers */
+  int32_t  iterations_done;
+  int32_t  iterations_run;
+  int32_t  best_iteration;
+  int32_t  have_best;
+  int32_t  best_inliers;           /* mnBestInliers */
+  float    Tcw[16];
+  float    best_Tcw[16];           /* mBestTcw */
+  uint8_t* inliers;
+  int32_t* hyp_n_inliers;
+  int32_t* hyp_planar;
+  double*  hyp_R;
+  double*  hyp_t;
+  uint64_t* hyp_masks;
+} orbp_mlpnp_result;
+
+typedef struct orbp_mlpnp orbp_mlpnp;
+
+/* The constructor after its loop over the matches: create + set_problem.  set_problem copies the arrays, resets mnIterations /
+ * mnBestInliers and applies SetRansacParameters() at its defaults, as the constructor does. */
+int orbp_mlpnp_create(int device, orbp_mlpnp** out);
+int orbp_mlpnp_destroy(orbp_mlpnp* h);
+int orbp_mlpnp_set_stream(orbp_mlpnp* h, void* hip_stream);
+int orbp_mlpnp_set_problem(orbp_mlpnp* h, const orbp_mlpnp_problem* p);
+/* SetRansacParameters (:218-253, host) with its oddities: int(N * epsilon) truncated, min_inliers raised to it and to min_set, epsilon
+ * raised to min_inliers / N in float, pow(epsilon, 3) for a minimal set of six, mvMaxError[i] = sigma2[i] * th2 in float.  It does not
+ * reset mnIterations or the best so far. */
+int orbp_mlpnp_set_ransac_parameters(orbp_mlpnp* h, double probability, int min_inliers, int max_iterations, int min_set,
+                                     float epsilon, float th2);
+/* ... the same formula without a handle: *max_its = mRansacMaxIts and *min_inliers_out = mRansacMinInliers for N = n.  No device. */
+int orbp_mlpnp_ransac_iterations(int n, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                                 int* max_its, int* min_inliers_out);
+/* How many iterations the serial loop can run in the next iterate(n_iterations): max(n_iterations, mRansacMaxIts - mnIterations), or
+ * 0 when N < mRansacMinInliers.  The caller supplies six raw draws for each of them. */
+int orbp_mlpnp_iterations_of_call(orbp_mlpnp* h, int n_iterations, int* k);
+/* The minimal sets of :126-138: draws = the raw DUtils::Random::RandomInt(0, size - 1) results, six per iteration (draw j from a list
+ * of n - j entries; anything else is ORBG_BAD_ARG); idx = the six correspondence indices of the swap-with-back removal.  Host only. */
+int orbp_mlpnp_resolve_draws(int n, const int32_t* draws, int n_iterations, int32_t* idx);
+/* cv::Mat MLPnPsolver::iterate(int nIterations, bool& bNoMore, vector<bool>& vbInliers, int& nInliers), :99-216: all hypotheses the
+ * call can run in one launch, one completion wait.  N < mRansacMinInliers: no_more without a launch (:104-108). */
+int orbp_mlpnp_iterate(orbp_mlpnp* h, int n_iterations, const int32_t* draws, orbp_mlpnp_result* result);
+/* The first iterate() of B fresh solvers -- the candidate keyframes of one Relocalization (S/Tracking.cc:3400-3425) -- in ONE launch:
+ * problems[b] with SetRansacParameters(params[b]) and draws[b] (6 * mRansacMaxIts(b) values).  Because of the OR above every solver is
+ * finished or exhausted after that call, so solving them together changes nothing the caller can observe.  All arguments and the
+ * device are checked before any result is written. */
+int orbp_mlpnp_solve_batch(int device, const orbp_mlpnp_problem* problems, int B, const orbp_mlpnp_params* params,
+                           const int32_t* const* draws, orbp_mlpnp_result* results);
+/* Stage 5 of computePose alone (:635-647) for the six points given, on the device: rot2rodrigues(R), mlpnp_gn, rodrigues2rot.  For
+ * checkers: a rotation with trace 3 gives a NaN pose, as the reference's Jacobian (a division by |omega|^2) does. */
+int orbp_mlpnp_gn(int device, const float* P3Dw /*6x3*/, const float* bearing /*6x3*/, const double* R /*9*/, const double* t /*3*/,
+                  double* R_out /*9*/, double* t_out /*3*/);
 
 #ifdef __cplusplus
 }

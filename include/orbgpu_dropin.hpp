@@ -17,6 +17,7 @@
 //   class Sim3Solver(KeyFrame*, KeyFrame*, const vector<MapPoint*>&, bFixScale, vpKeyFrameMatchedMP)  I/Sim3Solver.h:36-131, S/Sim3Solver.cc (orbgpu::Sim3Solver, at the end)
 //   int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, mAcumHessian, bAllPoints)   S/Optimizer.cc:4031-4310 (orbgpu::OptimizeSim3, at the end)
 //   int ORBmatcher::SearchForInitialization(Frame&, Frame&, vector<cv::Point2f>&, vector<int>&, int)  S/ORBmatcher.cc:702 (dropin::SearchForInitialization)
+//   class MLPnPsolver(const Frame&, const vector<MapPoint*>&), SetRansacParameters, iterate         I/MLPnPsolver.h, S/MLPnPsolver.cpp (orbgpu::MLPnPsolver, at the end)
 //   class TwoViewReconstruction(cv::Mat& K, float sigma, int iterations), bool Reconstruct(...)   I/TwoViewReconstruction.h, S/TwoViewReconstruction.cc (orbgpu::TwoViewReconstruction, at the end)
 //
 // Matrix access goes through mat_f32 / mat_u8 / make_mat (overloads for cv::Mat below, for the mock in the test header).
@@ -1878,6 +1879,116 @@ inline int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*
 }
 
 // ------------------------------------------------------------------------------------------------ TwoViewReconstruction
+// ------------------------------------------------------------------------------------------------ MLPnPsolver
+// class MLPnPsolver(const Frame& F, const vector<MapPoint*>& vpMapPointMatches) (I/MLPnPsolver.h, S/MLPnPsolver.cpp): the RANSAC of
+// Tracking::Relocalization, in two separable halves like Sim3Solver above: mlpnp_collect() -- the constructor's loop (:54-96), host
+// only -- and the handle calls.
+
+// What the constructor keeps per surviving match, flat.
+struct MLPnPFlat {
+  std::vector<float> P2D, sigma2, bearing, P3Dw;
+  std::vector<int32_t> kp_index;               // mvKeyPointIndices
+  int m = 0;                                   // mvpMapPointMatches.size()
+  float k[4] = {0, 0, 0, 0};
+  int model = 0;
+  orbp_mlpnp_problem problem() const {
+    orbp_mlpnp_problem p;
+    std::memset(&p, 0, sizeof(p));
+    p.struct_size = sizeof(p); p.n = (int32_t)kp_index.size();
+    p.P2D = P2D.data(); p.sigma2 = sigma2.data(); p.bearing = bearing.data(); p.P3Dw = P3Dw.data(); p.kp_index = kp_index.data();
+    p.m = m;
+    p.camera.model = model; p.camera.fx = k[0]; p.camera.fy = k[1]; p.camera.cx = k[2]; p.camera.cy = k[3];
+    return p;
+  }
+};
+
+// The constructor's loop, S/MLPnPsolver.cpp:65-93.  The bearing is mpCamera->unproject(kp.pt) divided by its z and NOT normalised,
+// whatever the comment at :76 says; a match beyond mvKeysUn (the right camera of a rig) is skipped (:70).
+template <class FrameT, class MapPointT>
+inline MLPnPFlat mlpnp_collect(const FrameT& F, const std::vector<MapPointT*>& vpMapPointMatches) {
+  using dropin::mat_f32;
+  MLPnPFlat f;
+  f.m = (int)vpMapPointMatches.size();
+  for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
+    MapPointT* pMP = vpMapPointMatches[i];
+    if (!pMP) continue;                                                            // :68
+    if (pMP->isBad()) continue;                                                    // :69
+    if (i >= F.mvKeysUn.size()) continue;                                          // :70
+    const auto& kp = F.mvKeysUn[i];
+    f.P2D.push_back(kp.pt.x); f.P2D.push_back(kp.pt.y);                            // :73
+    f.sigma2.push_back(F.mvLevelSigma2[kp.octave]);                                // :74
+    auto br = F.mpCamera->unproject(kp.pt);                                        // :77-78: cv::Point3f /= float
+    const float z = br.z;
+    f.bearing.push_back(br.x / z); f.bearing.push_back(br.y / z); f.bearing.push_back(br.z / z);
+    const auto pos = pMP->GetWorldPos();                                           // :83-85
+    const float* X = mat_f32(pos);
+    f.P3Dw.push_back(X[0]); f.P3Dw.push_back(X[1]); f.P3Dw.push_back(X[2]);
+    f.kp_index.push_back((int32_t)i);                                              // :87
+  }
+  f.model = (int)F.mpCamera->GetType();
+  for (int c = 0; c < 4; c++) f.k[c] = F.mpCamera->getParameter(c);
+  return f;
+}
+
+// RandomIntT: DUtils::Random::RandomInt's formula over rand() by default (Sim3RandomInt above); a tree that links DUtils passes a
+// functor that calls DUtils::Random::RandomInt, so that a seeded run draws from the same sequence in the same order (six per
+// iteration, from lists of n, n - 1, ... n - 5 entries).  All draws of a call are taken BEFORE the launch: after a call that returns
+// early the generator has advanced further than the reference's, which stops drawing at the returning iteration.
+// Throws std::runtime_error when the library refuses (no device, a camera model other than pinhole): there is no CPU fallback.
+template <class FrameT, class MapPointT, class RandomIntT = Sim3RandomInt>
+class MLPnPsolver {
+ public:
+  using MatT = decltype(std::declval<MapPointT&>().GetWorldPos());
+
+  MLPnPsolver(const FrameT& F, const std::vector<MapPointT*>& vpMapPointMatches, int device = 0, RandomIntT random_int = RandomIntT())
+      : mFlat(mlpnp_collect(F, vpMapPointMatches)), mRandomInt(random_int) {
+    check(orbp_mlpnp_create(device, &mHandle), "orbp_mlpnp_create");
+    const orbp_mlpnp_problem p = mFlat.problem();
+    const int rc = orbp_mlpnp_set_problem(mHandle, &p);                            // (ends with SetRansacParameters(), :95)
+    if (rc != ORBG_OK) { orbp_mlpnp_destroy(mHandle); mHandle = nullptr; check(rc, "orbp_mlpnp_set_problem"); }
+  }
+  ~MLPnPsolver() { if (mHandle) orbp_mlpnp_destroy(mHandle); }
+  MLPnPsolver(const MLPnPsolver&) = delete;
+  MLPnPsolver& operator=(const MLPnPsolver&) = delete;
+
+  const MLPnPFlat& flat() const { return mFlat; }
+
+  void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 6, float epsilon = 0.4,
+                           float th2 = 5.991) {
+    check(orbp_mlpnp_set_ransac_parameters(mHandle, probability, minInliers, maxIterations, minSet, epsilon, th2), "orbp_mlpnp_set_ransac_parameters");
+  }
+
+  MatT iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers) {                  // :99-216
+    const int n = (int)mFlat.kp_index.size();
+    int k = 0;
+    check(orbp_mlpnp_iterations_of_call(mHandle, std::max(nIterations, 0), &k), "orbp_mlpnp_iterations_of_call");
+    std::vector<int32_t> draws;
+    draws.reserve(6 * (size_t)k);
+    for (int it = 0; it < k; it++)
+      for (int j = 0; j < 6; j++) draws.push_back(mRandomInt(0, n - j - 1));        // :128
+    std::vector<uint8_t> mask(std::max(mFlat.m, 1));
+    orbp_mlpnp_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.struct_size = sizeof(r); r.inliers = mask.data();
+    check(orbp_mlpnp_iterate(mHandle, std::max(nIterations, 0), draws.empty() ? nullptr : draws.data(), &r), "orbp_mlpnp_iterate");
+    bNoMore = r.no_more != 0;
+    vbInliers.clear();                                                             // :101; filled only when a matrix comes back
+    nInliers = 0;
+    if (!r.returned) return MatT();
+    nInliers = r.n_inliers;
+    vbInliers = std::vector<bool>(mFlat.m, false);
+    for (int i = 0; i < mFlat.m; i++) if (mask[i]) vbInliers[i] = true;
+    MatT T;
+    dropin::make_mat(T, 4, 4, r.Tcw);
+    return T;
+  }
+
+ private:
+  MLPnPFlat mFlat;
+  RandomIntT mRandomInt;
+  orbp_mlpnp* mHandle = nullptr;
+};
+
 // DUtils::Random::RandomInt(min, max) after DUtils::Random::SeedRandOnce(0) (S/TwoViewReconstruction.cc:79,88;
 // Thirdparty/DBoW2/DUtils/Random.cpp:38-50): the first draw of the PROCESS seeds rand() with 0, whoever takes it.  The reference keeps
 // that flag in DUtils::Random; a tree that links DUtils passes a functor that calls DUtils::Random::SeedRandOnce(0) and

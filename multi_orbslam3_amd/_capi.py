@@ -221,6 +221,25 @@ class Sim3Result(C.Structure):
                 ("hyp_T12", C.c_void_p), ("hyp_masks", C.c_void_p)]
 
 
+class MLPnPProblem(C.Structure):
+    """orbp_mlpnp_problem: what MLPnPsolver's constructor keeps per surviving match, flat."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("P2D", C.c_void_p), ("sigma2", C.c_void_p), ("bearing", C.c_void_p),
+                ("P3Dw", C.c_void_p), ("kp_index", C.c_void_p), ("m", C.c_int32), ("camera", Camera)]
+
+
+class MLPnPParams(C.Structure):
+    _fields_ = [("probability", C.c_double), ("min_inliers", C.c_int32), ("max_iterations", C.c_int32), ("min_set", C.c_int32),
+                ("epsilon", C.c_float), ("th2", C.c_float)]
+
+
+class MLPnPResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("no_more", C.c_int32), ("returned", C.c_int32), ("n_inliers", C.c_int32),
+                ("iterations_done", C.c_int32), ("iterations_run", C.c_int32), ("best_iteration", C.c_int32), ("have_best", C.c_int32),
+                ("best_inliers", C.c_int32), ("Tcw", C.c_float * 16), ("best_Tcw", C.c_float * 16), ("inliers", C.c_void_p),
+                ("hyp_n_inliers", C.c_void_p), ("hyp_planar", C.c_void_p), ("hyp_R", C.c_void_p), ("hyp_t", C.c_void_p),
+                ("hyp_masks", C.c_void_p)]
+
+
 class Sim3OptProblem(C.Structure):
     """orbm_sim3opt_problem: what OptimizeSim3's loop over the matches hands to g2o, flat."""
     _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("X3Dc1", C.c_void_p), ("X3Dc2", C.c_void_p),
@@ -353,7 +372,7 @@ EXPORTED_SYMBOLS = [
     "lba_solve", "lba_create", "lba_destroy", "lba_solve_h", "lba_solve_async", "lba_wait", "pose_optimize",
     "lba_solve_b", "lba_solve_hb", "lba_solve_async_b",
     "lba_set_profiling", "lba_get_solver_stats", "lba_event_overhead", "lba_get_watchdog_count",
-    "orbd_database_create", "orbd_database_destroy", "orbd_detect_n_best_candidates",
+    "orbd_database_create", "orbd_database_destroy", "orbd_detect_n_best_candidates", "orbd_detect_relocalization_candidates",
     "orbx_set_stream", "orbm_frame_set_stream", "orbm_map_set_stream", "lba_set_stream", "orbv_vocab_set_stream", "orbd_database_set_stream",
     "pose_opt_set_stream", "orbx_get_ctor_timeline", "orbm_map_set_observations", "orbm_search_by_projection_reloc", "orbm_search_by_projection_reloc_cam", "orbm_search_by_projection_sim3_cam", "orbm_lastview_create", "orbm_lastview_destroy", "orbm_lastview_upload",
     "orbm_search_by_projection_frame_resident", "orbg_quiesce", "orbg_set_wait_policy", "orbg_get_wait_policy",
@@ -377,6 +396,11 @@ FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solv
                    "ba_weld_solve", "ba_weld_solve_b", "ba_weld_solve_h", "ba_weld_solve_hb"]
 # The essential graph (prefix eg_), likewise; tests/test_essential_graph_cpu.py holds it against the header.
 ESSENTIAL_GRAPH_SYMBOLS = ["eg_solve", "eg_set_profiling", "eg_get_phase_ms"]
+
+# MLPnPsolver (prefix orbp_), likewise; tests/test_mlpnp_cpu.py holds it against the header.
+MLPNP_SYMBOLS = ["orbp_mlpnp_create", "orbp_mlpnp_destroy", "orbp_mlpnp_set_stream", "orbp_mlpnp_set_problem",
+                 "orbp_mlpnp_set_ransac_parameters", "orbp_mlpnp_ransac_iterations", "orbp_mlpnp_iterations_of_call",
+                 "orbp_mlpnp_resolve_draws", "orbp_mlpnp_iterate", "orbp_mlpnp_solve_batch", "orbp_mlpnp_gn"]
 
 _lib = None
 
@@ -434,7 +458,10 @@ def load():
     lib.eg_solve.argtypes = [C.c_void_p, C.c_void_p]
     lib.eg_set_profiling.argtypes = [C.c_int]
     lib.eg_get_phase_ms.argtypes = [C.c_void_p]
-    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS:
+    lib.orbp_mlpnp_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
+    lib.orbp_mlpnp_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    lib.orbp_mlpnp_gn.argtypes = [C.c_int] + [C.c_void_p] * 6
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS + MLPNP_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

@@ -1116,6 +1116,17 @@ class KeyFrameDatabase:
                    "orbd_detect_n_best_candidates")
         return loop[: nl.value].copy(), merge[: nm.value].copy()
 
+    def DetectRelocalizationCandidates(self, q_word, q_value, query_map_id, reloc_score):
+        """KeyFrameDatabase::DetectRelocalizationCandidates (S/KeyFrameDatabase.cc:764-876) for the query BowVector -> vpRelocCandidates
+        as keyframe indices; reloc_score (float32[n_kfs], mRelocScore) is updated in place."""
+        qw = np.ascontiguousarray(q_word, np.int32); qv = np.ascontiguousarray(q_value, np.float64)
+        assert reloc_score.dtype == np.float32 and reloc_score.flags["C_CONTIGUOUS"] and len(reloc_score) == self.n_kfs
+        cand = np.zeros(max(self.n_kfs, 1), np.int32)
+        n = C.c_int32(0)
+        capi.check(self.lib.orbd_detect_relocalization_candidates(self.h, _vp(qw), _vp(qv), len(qw), int(query_map_id), _vp(reloc_score),
+                                                                  _vp(cand), C.byref(n)), "orbd_detect_relocalization_candidates")
+        return cand[: n.value].copy()
+
 
 # ---------------------------------------------------------------- Sim3Solver (S/Sim3Solver.cc)
 
@@ -1304,6 +1315,188 @@ class Sim3Solver:
         R = (capi.Sim3Result * max(B, 1))(*[o[0] for o in outs])
         capi.check(lib.orbm_sim3_solve_batch(int(device), P, B, Q, D, R), "orbm_sim3_solve_batch")
         return [_sim3_unpack(p, R[b], outs[b][1], outs[b][2], its[b] if p.n >= params[b][1] else 0) for b, p in enumerate(problems)]
+
+
+# ---------------------------------------------------------------- MLPnPsolver (S/MLPnPsolver.cpp)
+
+MLPNP_DEFAULTS = (0.99, 8, 300, 6, 0.4, 5.991)        # I/MLPnPsolver.h; Tracking::Relocalization sets (0.99, 10, 300, 6, 0.5, 5.991)
+
+
+def mlpnp_ransac_iterations(n, probability=0.99, minInliers=8, maxIterations=300, minSet=6, epsilon=0.4, th2=5.991):
+    """(mRansacMaxIts, mRansacMinInliers) of MLPnPsolver::SetRansacParameters (S/MLPnPsolver.cpp:218-248) for N = n.  Host code."""
+    its, mi = C.c_int(0), C.c_int(0)
+    capi.check(capi.load().orbp_mlpnp_ransac_iterations(int(n), float(probability), int(minInliers), int(maxIterations), int(minSet),
+                                                        float(epsilon), C.byref(its), C.byref(mi)), "orbp_mlpnp_ransac_iterations")
+    return its.value, mi.value
+
+
+def mlpnp_draws(n, k, seed):
+    """The raw DUtils::Random::RandomInt(0, size - 1) results of k iterations (S/MLPnPsolver.cpp:128): int32 (k, 6), column j uniform
+    in [0, n - j).  seed: a numpy Generator or a seed."""
+    rng = seed if isinstance(seed, np.random.Generator) else np.random.default_rng(seed)
+    d = np.empty((int(k), 6), np.int32)
+    for j in range(6):
+        d[:, j] = rng.integers(0, max(int(n) - j, 1), size=int(k))
+    return d
+
+
+def mlpnp_resolve_draws(n, draws):
+    """Raw draws -> the six correspondence indices of each minimal set (swap-with-back removal on mvAllIndices, :126-138)."""
+    d = np.ascontiguousarray(draws, np.int32).reshape(-1, 6)
+    idx = np.zeros_like(d)
+    capi.check(capi.load().orbp_mlpnp_resolve_draws(int(n), _vp(d), len(d), _vp(idx)), "orbp_mlpnp_resolve_draws")
+    return idx
+
+
+def mlpnp_gn(P3Dw, bearing, R, t, device=0):
+    """rot2rodrigues, mlpnp_gn, rodrigues2rot (S/MLPnPsolver.cpp:635-647) for six points on the device -> (R, t) in double."""
+    X = np.ascontiguousarray(P3Dw, np.float32).reshape(6, 3)
+    f = np.ascontiguousarray(bearing, np.float32).reshape(6, 3)
+    R = np.ascontiguousarray(R, np.float64).reshape(3, 3)
+    t = np.ascontiguousarray(t, np.float64).reshape(3)
+    Ro, to = np.zeros((3, 3)), np.zeros(3)
+    capi.check(capi.load().orbp_mlpnp_gn(int(device), _vp(X), _vp(f), _vp(R), _vp(t), _vp(Ro), _vp(to)), "orbp_mlpnp_gn")
+    return Ro, to
+
+
+class MLPnPProblem:
+    """The flat problem MLPnPsolver's constructor builds (S/MLPnPsolver.cpp:54-96): per surviving match the undistorted keypoint, the
+    level's sigma2, the bearing (unproject divided by z, not normalised), the map point, and its index among the m matches; `camera`
+    is (fx, fy, cx, cy) of a pinhole mpCamera."""
+
+    def __init__(self, P2D, sigma2, bearing, P3Dw, camera, kp_index=None, m=None):
+        self.P2D = np.ascontiguousarray(P2D, np.float32).reshape(-1, 2)
+        self.sigma2 = np.ascontiguousarray(sigma2, np.float32).reshape(-1)
+        self.bearing = np.ascontiguousarray(bearing, np.float32).reshape(-1, 3)
+        self.P3Dw = np.ascontiguousarray(P3Dw, np.float32).reshape(-1, 3)
+        self.n = len(self.P2D)
+        assert len(self.sigma2) == self.n and len(self.bearing) == self.n and len(self.P3Dw) == self.n
+        self.camera = tuple(float(v) for v in camera)
+        self.kp_index = np.arange(self.n, dtype=np.int32) if kp_index is None else np.ascontiguousarray(kp_index, np.int32).reshape(-1)
+        self.m = int(m) if m is not None else (int(self.kp_index.max()) + 1 if self.n else 0)
+
+    def struct(self, camera_model=0):
+        cam = capi.Camera(int(camera_model), *self.camera)
+        return capi.MLPnPProblem(C.sizeof(capi.MLPnPProblem), self.n, capi.ptr(self.P2D), capi.ptr(self.sigma2), capi.ptr(self.bearing),
+                                 capi.ptr(self.P3Dw), capi.ptr(self.kp_index), self.m, cam)
+
+
+class MLPnPIteration:
+    """What one iterate() call returned.  Tcw is the reference's return value (None for an empty matrix); nInliers / vbInliers (length
+    m) are zero unless a matrix came back.  best_* is the solver's persisting state.  hyp_*: per hypothesis of the launch."""
+
+    def __init__(self, prob, r, mask, hyp):
+        self.bNoMore, self.returned = bool(r.no_more), bool(r.returned)
+        self.nInliers = r.n_inliers
+        self.iterations_done, self.iterations_run, self.best_iteration = r.iterations_done, r.iterations_run, r.best_iteration
+        self.have_best, self.best_inliers = bool(r.have_best), r.best_inliers
+        self.Tcw = np.array(r.Tcw, np.float32).reshape(4, 4) if self.returned else None
+        self.best_Tcw = np.array(r.best_Tcw, np.float32).reshape(4, 4) if self.have_best else None
+        self.vbInliers = mask.astype(bool)
+        self.hyp_n_inliers, self.hyp_planar, self.hyp_R, self.hyp_t, self.hyp_masks = hyp
+
+    def fields(self):
+        """Every field as plain values, for comparisons."""
+        return (self.bNoMore, self.returned, self.nInliers, self.iterations_done, self.iterations_run, self.best_iteration, self.have_best,
+                self.best_inliers, None if self.Tcw is None else self.Tcw.tobytes(),
+                None if self.best_Tcw is None else self.best_Tcw.tobytes(), self.vbInliers.tobytes())
+
+
+def _mlpnp_result(prob, n_hyp, per_hypothesis):
+    mask = np.zeros(max(prob.m, 1), np.uint8)
+    hyp = (None,) * 5
+    if per_hypothesis:
+        k = max(n_hyp, 1)
+        hyp = (np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros((k, 3, 3)), np.zeros((k, 3)),
+               np.zeros((k, max((prob.n + 63) // 64, 1)), np.uint64))
+    r = capi.MLPnPResult()
+    r.struct_size = C.sizeof(capi.MLPnPResult)
+    r.inliers = capi.ptr(mask)
+    r.hyp_n_inliers, r.hyp_planar, r.hyp_R, r.hyp_t, r.hyp_masks = (capi.ptr(a) for a in hyp)
+    return r, mask, hyp
+
+
+def _mlpnp_unpack(prob, r, mask, hyp, n_hyp):
+    if hyp[0] is not None:
+        bits = np.unpackbits(hyp[4][:n_hyp].view(np.uint8), axis=1, bitorder="little")[:, : prob.n].astype(bool)
+        hyp = (hyp[0][:n_hyp], hyp[1][:n_hyp].astype(bool), hyp[2][:n_hyp], hyp[3][:n_hyp], bits)
+    return MLPnPIteration(prob, r, mask[: prob.m], hyp)
+
+
+class MLPnPsolver:
+    """ORB_SLAM3::MLPnPsolver over a flat MLPnPProblem: every hypothesis of a call in one kernel launch, the serial loop replayed over
+    the counts.  Draws come from the caller (raw RandomInt results as mlpnp_draws makes them) or from the solver's seeded generator."""
+
+    def __init__(self, problem, device=0, seed=0):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        self.prob = problem
+        self.rng = np.random.default_rng(seed)
+        self.device = device
+        capi.check(self.lib.orbp_mlpnp_create(device, C.byref(self.h)), "orbp_mlpnp_create")
+        st = problem.struct()
+        capi.check(self.lib.orbp_mlpnp_set_problem(self.h, C.byref(st)), "orbp_mlpnp_set_problem")
+        self.mRansacMaxIts, self.mRansacMinInliers = mlpnp_ransac_iterations(problem.n, *MLPNP_DEFAULTS)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.orbp_mlpnp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        capi.check(self.lib.orbp_mlpnp_set_stream(self.h, C.c_void_p(hip_stream) if hip_stream else None), "orbp_mlpnp_set_stream")
+
+    def SetRansacParameters(self, probability=0.99, minInliers=8, maxIterations=300, minSet=6, epsilon=0.4, th2=5.991):
+        capi.check(self.lib.orbp_mlpnp_set_ransac_parameters(self.h, float(probability), int(minInliers), int(maxIterations), int(minSet),
+                                                             float(epsilon), float(th2)), "orbp_mlpnp_set_ransac_parameters")
+        self.mRansacMaxIts, self.mRansacMinInliers = mlpnp_ransac_iterations(self.prob.n, probability, minInliers, maxIterations, minSet, epsilon)
+
+    def iterations_of_call(self, nIterations):
+        k = C.c_int(0)
+        capi.check(self.lib.orbp_mlpnp_iterations_of_call(self.h, int(nIterations), C.byref(k)), "orbp_mlpnp_iterations_of_call")
+        return k.value
+
+    def iterate(self, nIterations, draws=None, per_hypothesis=False):
+        """-> MLPnPIteration.  draws: int32 (iterations_of_call(nIterations), 6) raw draws; None: from the solver's generator (all of
+        them before the launch, so after an early return the generator is further on than a serial loop's would be)."""
+        k = self.iterations_of_call(nIterations)
+        if draws is None:
+            draws = mlpnp_draws(self.prob.n, k, self.rng)
+        d = np.ascontiguousarray(draws, np.int32).reshape(-1, 6)
+        assert len(d) >= k, "six raw draws per iteration that can run"
+        r, mask, hyp = _mlpnp_result(self.prob, k, per_hypothesis)
+        capi.check(self.lib.orbp_mlpnp_iterate(self.h, int(nIterations), _vp(d), C.byref(r)), "orbp_mlpnp_iterate")
+        return _mlpnp_unpack(self.prob, r, mask, hyp, k)
+
+    @staticmethod
+    def solve_batch(problems, params=None, draws=None, device=0, seed=0, per_hypothesis=False):
+        """The first iterate() of len(problems) fresh solvers in ONE launch.  params: SetRansacParameters' six arguments per problem
+        (None: the defaults); draws: per problem the raw draws of mRansacMaxIts iterations (None: from a generator seeded with
+        `seed`).  -> list of MLPnPIteration."""
+        lib = capi.load()
+        B = len(problems)
+        params = [MLPNP_DEFAULTS] * B if params is None else [tuple(p) for p in params]
+        rng = np.random.default_rng(seed)
+        its = [mlpnp_ransac_iterations(p.n, *q[:5]) for p, q in zip(problems, params)]
+        ks = [h if p.n >= mi else 0 for p, (h, mi) in zip(problems, its)]
+        if draws is None:
+            draws = [mlpnp_draws(p.n, k, rng) for p, k in zip(problems, ks)]
+        ds = [np.ascontiguousarray(d, np.int32).reshape(-1, 6) for d in draws]
+        for d, k in zip(ds, ks):
+            assert len(d) >= k, "six raw draws per iteration of mRansacMaxIts"
+        P = (capi.MLPnPProblem * max(B, 1))(*[p.struct() for p in problems])
+        Q = (capi.MLPnPParams * max(B, 1))(*[capi.MLPnPParams(float(q[0]), int(q[1]), int(q[2]), int(q[3]), float(q[4]), float(q[5])) for q in params])
+        D = (C.c_void_p * max(B, 1))(*[d.ctypes.data for d in ds])
+        outs = [_mlpnp_result(p, k, per_hypothesis) for p, k in zip(problems, ks)]
+        R = (capi.MLPnPResult * max(B, 1))(*[o[0] for o in outs])
+        capi.check(lib.orbp_mlpnp_solve_batch(int(device), P, B, Q, D, R), "orbp_mlpnp_solve_batch")
+        return [_mlpnp_unpack(p, R[b], outs[b][1], outs[b][2], ks[b]) for b, p in enumerate(problems)]
 
 
 # ---------------------------------------------------------------- TwoViewReconstruction (S/TwoViewReconstruction.cc)

@@ -498,23 +498,22 @@ extern "C" int orbd_database_destroy(orbd_database* d) {
   return ORBG_OK;
 }
 
-extern "C" int orbd_detect_n_best_candidates(orbd_database* d, const int32_t* q_word, const double* q_value, int nq, const uint8_t* connected,
-                                             int32_t query_map_id, int n_candidates, float* place_score, int32_t* loop_cand, int32_t* n_loop,
-                                             int32_t* merge_cand, int32_t* n_merge) {
-  if (!d || nq < 0 || (nq > 0 && (!q_word || !q_value)) || n_candidates < 0 || !n_loop || !n_merge || (n_candidates > 0 && (!loop_cand || !merge_cand)))
-    return ORBG_BAD_ARG;
+namespace {
+// The device phase DetectNBestCandidates (:606-701) and DetectRelocalizationCandidates (:766-852) share: the inverted-file walk (common
+// words, first-encounter keys), the 0.8 * max word threshold, the L1 scores of the selected keyframes written into `score` (in / out:
+// what an earlier query left stays for the others) and the covisibility accumulation.  connected == NULL: no keyframe is excluded.
+// Leaves h_sel / h_acc / h_best / h_key on the host.
+int db_device_phase(orbd_database* d, const int32_t* q_word, const double* q_value, int nq, const uint8_t* connected, float* score) {
   const int K = d->n_kfs;
-  if (K > 0 && (!connected || !place_score)) return ORBG_BAD_ARG;
-  *n_loop = 0; *n_merge = 0;
-  if (K == 0 || nq == 0) return ORBG_OK;
   int rc = select_device(d->device);
   if (rc) return rc;
   hipStream_t st = d->stream;
   if ((rc = d->qw.reserve(nq)) || (rc = d->qv.reserve(nq))) return rc;
   ORBG_HIP(hipMemcpyAsync(d->qw.p, q_word, (size_t)nq * 4, hipMemcpyHostToDevice, st));
   ORBG_HIP(hipMemcpyAsync(d->qv.p, q_value, (size_t)nq * 8, hipMemcpyHostToDevice, st));
-  ORBG_HIP(hipMemcpyAsync(d->connected.p, connected, (size_t)K, hipMemcpyHostToDevice, st));
-  ORBG_HIP(hipMemcpyAsync(d->place_score.p, place_score, (size_t)K * 4, hipMemcpyHostToDevice, st));
+  if (connected) ORBG_HIP(hipMemcpyAsync(d->connected.p, connected, (size_t)K, hipMemcpyHostToDevice, st));
+  else ORBG_HIP(hipMemsetAsync(d->connected.p, 0, (size_t)K, st));
+  ORBG_HIP(hipMemcpyAsync(d->place_score.p, score, (size_t)K * 4, hipMemcpyHostToDevice, st));
   ORBG_HIP(hipMemsetAsync(d->words.p, 0, (size_t)K * 4, st));
   ORBG_HIP(hipMemsetAsync(d->first_key.p, 0xFF, (size_t)K * 8, st));
   hipLaunchKernelGGL(db_walk_kernel, dim3(nq), dim3(256), 0, st, d->qw.p, nq, d->inv_start.p, d->inv_kf.p, d->n_words, d->words.p, d->first_key.p);
@@ -529,17 +528,38 @@ extern "C" int orbd_detect_n_best_candidates(orbd_database* d, const int32_t* q_
   ORBG_HIP(hipMemcpyAsync(d->h_acc.data(), d->acc.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
   ORBG_HIP(hipMemcpyAsync(d->h_best.data(), d->best.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
   ORBG_HIP(hipMemcpyAsync(d->h_key.data(), d->first_key.p, (size_t)K * 8, hipMemcpyDeviceToHost, st));
-  ORBG_HIP(hipMemcpyAsync(place_score, d->place_score.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
+  ORBG_HIP(hipMemcpyAsync(score, d->place_score.p, (size_t)K * 4, hipMemcpyDeviceToHost, st));
   ORBG_HIP(hipStreamSynchronize(st));
-  // lScoreAndMatch order = order of first encounter in the inverted-file walk; list::sort(compFirst) is a stable sort
-  struct Ent { unsigned long long key; float acc; int best; };
-  std::vector<Ent> ents;
-  for (int i = 0; i < K; i++)
-    if (d->h_sel[i]) ents.push_back(Ent{d->h_key[i], d->h_acc[i], d->h_best[i]});
-  std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.key < b.key; });
-  std::stable_sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) { return a.acc > b.acc; });
+  return ORBG_OK;
+}
+
+struct DbEnt { unsigned long long key; float acc; int best; };
+// lScoreAndMatch order = order of first encounter in the inverted-file walk
+std::vector<DbEnt> db_entries_in_walk_order(const orbd_database* d) {
+  std::vector<DbEnt> ents;
+  for (int i = 0; i < d->n_kfs; i++)
+    if (d->h_sel[i]) ents.push_back(DbEnt{d->h_key[i], d->h_acc[i], d->h_best[i]});
+  std::sort(ents.begin(), ents.end(), [](const DbEnt& a, const DbEnt& b) { return a.key < b.key; });
+  return ents;
+}
+}  // namespace
+
+extern "C" int orbd_detect_n_best_candidates(orbd_database* d, const int32_t* q_word, const double* q_value, int nq, const uint8_t* connected,
+                                             int32_t query_map_id, int n_candidates, float* place_score, int32_t* loop_cand, int32_t* n_loop,
+                                             int32_t* merge_cand, int32_t* n_merge) {
+  if (!d || nq < 0 || (nq > 0 && (!q_word || !q_value)) || n_candidates < 0 || !n_loop || !n_merge || (n_candidates > 0 && (!loop_cand || !merge_cand)))
+    return ORBG_BAD_ARG;
+  const int K = d->n_kfs;
+  if (K > 0 && (!connected || !place_score)) return ORBG_BAD_ARG;
+  *n_loop = 0; *n_merge = 0;
+  if (K == 0 || nq == 0) return ORBG_OK;
+  int rc = db_device_phase(d, q_word, q_value, nq, connected, place_score);
+  if (rc) return rc;
+  // list::sort(compFirst) is a stable sort
+  std::vector<DbEnt> ents = db_entries_in_walk_order(d);
+  std::stable_sort(ents.begin(), ents.end(), [](const DbEnt& a, const DbEnt& b) { return a.acc > b.acc; });
   std::vector<uint8_t> added(K, 0);
-  for (const Ent& e : ents) {
+  for (const DbEnt& e : ents) {
     if (!(*n_loop < n_candidates || *n_merge < n_candidates)) break;              // :714
     const int k = e.best;
     if (d->bad[k]) continue;                                                       // pinned: skipped (see orbgpu.h)
@@ -547,6 +567,33 @@ extern "C" int orbd_detect_n_best_candidates(orbd_database* d, const int32_t* q_
     if (d->map_id[k] == query_map_id && *n_loop < n_candidates) loop_cand[(*n_loop)++] = k;
     else if (d->map_id[k] != query_map_id && *n_merge < n_candidates && !d->map_bad[k]) merge_cand[(*n_merge)++] = k;
     added[k] = 1;
+  }
+  return ORBG_OK;
+}
+
+// KeyFrameDatabase::DetectRelocalizationCandidates (S/KeyFrameDatabase.cc:764-876): the device phase above without an exclusion, then
+// on the host the selection in lKFsSharingWords order (no sort): acc > 0.75f * bestAccScore, the map filter, the de-duplication.
+extern "C" int orbd_detect_relocalization_candidates(orbd_database* d, const int32_t* q_word, const double* q_value, int nq,
+                                                     int32_t query_map_id, float* reloc_score, int32_t* cand, int32_t* n_cand) {
+  if (!d || nq < 0 || (nq > 0 && (!q_word || !q_value)) || !n_cand) return ORBG_BAD_ARG;
+  const int K = d->n_kfs;
+  if (K > 0 && (!reloc_score || !cand)) return ORBG_BAD_ARG;
+  *n_cand = 0;
+  if (K == 0 || nq == 0) return ORBG_OK;
+  int rc = db_device_phase(d, q_word, q_value, nq, nullptr, reloc_score);
+  if (rc) return rc;
+  const std::vector<DbEnt> ents = db_entries_in_walk_order(d);
+  float bestAcc = 0.f;
+  for (const DbEnt& e : ents)
+    if (e.acc > bestAcc) bestAcc = e.acc;                                          // :850
+  const float minScoreToRetain = 0.75f * bestAcc;
+  std::vector<uint8_t> added(K, 0);
+  for (const DbEnt& e : ents) {
+    if (!(e.acc > minScoreToRetain)) continue;
+    const int k = e.best;
+    if (d->map_id[k] != query_map_id) continue;                                    // keyframes of other maps were scored and counted in bestAcc
+    if (added[k]) continue;
+    cand[(*n_cand)++] = k; added[k] = 1;                                           // isBad() is not looked at: Relocalization does that itself
   }
   return ORBG_OK;
 }
