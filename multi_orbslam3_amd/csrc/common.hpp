@@ -163,6 +163,47 @@ struct StreamDrain {
   ~StreamDrain() { (void)hipStreamSynchronize(s); }
 };
 
+// how many owners of an eight-workgroup LDL^T context (ldlt_solver.hpp) this process has had before the caller: each takes another XCD
+int next_ldlt_xcd_user();
+
+// Phase timing of a solve (ba_set_profiling, eg_set_profiling): event pairs around launch groups, read at the next synchronisation;
+// ms[phase] sums them.  While `on` is false (and before the first reset() with it true) no member makes a HIP call.
+template <int N>
+struct PhaseTimer {
+  bool on = false;
+  double ms[N] = {};
+  hipEvent_t ev[32] = {};
+  int ev_phase[16] = {};
+  int ev_n = 0;
+  // the start of a solve: zeroed sums, the events created on first use
+  int reset() {
+    if (!on) return ORBG_OK;
+    for (double& m : ms) m = 0;
+    ev_n = 0;
+    for (hipEvent_t& e : ev) if (!e) ORBG_HIP(hipEventCreate(&e));
+    return ORBG_OK;
+  }
+  void begin(int phase, hipStream_t st) {
+    if (!on) return;
+    if (ev_n == 16) flush(st);
+    if (hipEventRecord(ev[2 * ev_n], st) == hipSuccess) ev_phase[ev_n] = phase;
+  }
+  void end(hipStream_t st) {
+    if (!on) return;
+    if (hipEventRecord(ev[2 * ev_n + 1], st) == hipSuccess) ev_n++;
+  }
+  void flush(hipStream_t st) {
+    if (!on) return;
+    (void)hipStreamSynchronize(st);
+    for (int i = 0; i < ev_n; i++) {
+      float t = 0;
+      if (hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) == hipSuccess) ms[ev_phase[i]] += t;
+    }
+    ev_n = 0;
+  }
+  void release() { for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; } }
+};
+
 // The work area of an entry point WITHOUT a handle (pose_optimize, orbm_sim3_solve_batch, ...: the reference calls a static member, so
 // the buffers belong to the calling thread: `static thread_local WorkArea<...>`), also the device half of a small handle.  Bufs holds
 // the site's buffers and `void release_buffers()`; the area adds the device they live on and the stream the calls run on.  It derives

@@ -50,6 +50,7 @@ namespace {
 #include "ldlt_mfma.hpp"
 #include "ldlt_xcd.hpp"
 #include "ldlt_wide.hpp"
+#include "ldlt_solver.hpp"
 
 constexpr int kEJ = 105;                 // per edge: Ji (7 x 7 row-major: error row, update column) | Jj | e
 constexpr int kLinEdges = 8;             // edges per workgroup of k_eg_lin (32 lanes each)
@@ -281,32 +282,24 @@ __global__ __launch_bounds__(256) void k_eg_points(int NP, const eg_point* __res
 // ---------------------------------------------------------------------------------------------- the calling thread's work area
 
 struct EgBufs {
-  int ldlt_xcd = 1;                    // ORBG_LDLT_XCD=0: the eight-workgroup sizes stay on the one-workgroup kernels
-  bool ldlt_wide = false;              // ORBG_LDLT_WIDE: every size on k_wide_*
-  bool env_read = false;
-  ldltm::AttrCache ldlt_attr;
-  ldltx::Context ldlt_x;
-  DevBuf<double> d_xscr; DevBuf<unsigned> d_xflags;
+  LdltSolver ldlt;                     // the solver of the normal equations (its switches: read on the thread's first solve)
   DevBuf<EgEdge> d_edges;
   DevBuf<S3> d_est[3];                 // two LM states and the initial estimate
   DevBuf<int> d_col, d_fixs, d_task_start, d_items, d_pair_i, d_pair_j, d_ok;
-  DevBuf<double> d_EJ, d_partial, d_Hd, d_bv, d_Hp, d_S, d_St, d_x, d_wfac, d_wide, d_scale_v, d_err0;
+  DevBuf<double> d_EJ, d_partial, d_Hd, d_bv, d_Hp, d_x, d_scale_v, d_err0;
   DevBuf<eg_point> d_pts;
   DevBuf<float> d_pts_out;
   DevBuf<EgRec> d_rec;
   PinnedBuf<EgRec> rec;
-  double phase_ms[4] = {0, 0, 0, 0};
-  hipEvent_t ev[32] = {};
-  int ev_phase[16] = {};
-  int ev_n = 0;
+  PhaseTimer<4> timer;
   void release_buffers() {
-    d_xscr.release(); d_xflags.release(); ldlt_x.scr = nullptr; ldlt_x.flags = nullptr;
+    ldlt.release();
     d_edges.release();
     for (DevBuf<S3>& b : d_est) b.release();
     for (DevBuf<int>* b : {&d_col, &d_fixs, &d_task_start, &d_items, &d_pair_i, &d_pair_j, &d_ok}) b->release();
-    for (DevBuf<double>* b : {&d_EJ, &d_partial, &d_Hd, &d_bv, &d_Hp, &d_S, &d_St, &d_x, &d_wfac, &d_wide, &d_scale_v, &d_err0}) b->release();
+    for (DevBuf<double>* b : {&d_EJ, &d_partial, &d_Hd, &d_bv, &d_Hp, &d_x, &d_scale_v, &d_err0}) b->release();
     d_pts.release(); d_pts_out.release(); d_rec.release(); rec.release();
-    for (hipEvent_t& e : ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    timer.release();
   }
 };
 typedef WorkArea<EgBufs> EgArea;
@@ -361,7 +354,6 @@ struct EgRun {
   LmScalars lm;
   const int NV, NE, NP, F, n;
   int n_pairs = 0, n_tasks = 0, n_blocks_lin = 0, n_blocks_e = 0;
-  bool use_mfma = false, use_xcd = false, use_wide = false;
   int cur = 0;
   const bool prof;
   std::vector<S3> s_est;
@@ -373,25 +365,6 @@ struct EgRun {
         prof(g_eg_profiling.load() != 0) {
     n_blocks_lin = (NE + kLinEdges - 1) / kLinEdges;
     n_blocks_e = (NE + 255) / 256;
-  }
-
-  void ph_begin(int phase) {
-    if (!prof) return;
-    if (h->ev_n == 16) flush();
-    if (hipEventRecord(h->ev[2 * h->ev_n], st) == hipSuccess) h->ev_phase[h->ev_n] = phase;
-  }
-  void ph_end() {
-    if (!prof) return;
-    if (hipEventRecord(h->ev[2 * h->ev_n + 1], st) == hipSuccess) h->ev_n++;
-  }
-  void flush() {
-    if (!prof) return;
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < h->ev_n; i++) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]) == hipSuccess) h->phase_ms[h->ev_phase[i]] += ms;
-    }
-    h->ev_n = 0;
   }
 
   void host_state() {
@@ -477,11 +450,7 @@ struct EgRun {
 
   int buffers() {
     int rc;
-    if (!h->env_read) {
-      h->ldlt_wide = getenv("ORBG_LDLT_WIDE") != nullptr;
-      if (const char* e = getenv("ORBG_LDLT_XCD")) h->ldlt_xcd = !strcmp(e, "0") ? 0 : !strcmp(e, "safe") ? 2 : 1;
-      h->env_read = true;
-    }
+    h->ldlt.read_env();
     const size_t sNV = (size_t)std::max(NV, 1), sNE = (size_t)std::max(NE, 1), sF = (size_t)std::max(F, 1), sP = (size_t)std::max(n_pairs, 1);
     for (DevBuf<S3>& b : h->d_est) if ((rc = b.reserve(sNV))) return rc;
     if ((rc = h->d_edges.reserve(sNE)) || (rc = h->d_col.reserve(sNV)) || (rc = h->d_fixs.reserve(sNV)) ||
@@ -492,28 +461,9 @@ struct EgRun {
         (rc = h->d_pts.reserve((size_t)std::max(NP, 1))) || (rc = h->d_pts_out.reserve(3 * (size_t)std::max(NP, 1))) || (rc = h->d_rec.reserve(1)) ||
         (rc = h->rec.reserve(1)))
       return rc;
-    // the solver of the normal equations, by size (as full_ba.hip chooses for the reduced camera system)
-    use_mfma = ldltm::supports(n) && !h->ldlt_wide;
-    use_wide = !use_mfma;
-    if (use_wide && n > kWideMaxUnknowns) return ORBG_CAP_EXCEEDED;
-    if (use_wide && ((rc = h->d_wide.reserve(2 * (size_t)n + 32)) || (rc = h->d_S.reserve((size_t)n * n)))) return rc;
-    if (use_mfma && ((rc = h->d_St.reserve(ldltm::tile_image_doubles(n))) || (rc = h->d_wfac.reserve(ldltm::wglob_doubles(ldltm::make_geo(n))))))
-      return rc;
-    use_xcd = use_mfma && h->ldlt_xcd != 0 && ldltx::pays(n);
-    if (use_xcd && !h->ldlt_x.scr) {
-      if ((rc = h->d_xscr.reserve(ldltx::scratch_doubles())) || (rc = h->d_xflags.reserve(ldltx::kFlagWords))) return rc;
-      ORBG_HIP(hipMemsetAsync(h->d_xflags.p, 0, ldltx::kFlagWords * sizeof(unsigned), st));
-      ORBG_HIP(hipMemsetAsync(h->d_xscr.p + ldltx::kGbOff, 0, (ldltx::kWOff - ldltx::kGbOff) * sizeof(double), st));
-      h->ldlt_x.bind(h->d_xscr.p, h->d_xflags.p);
-      static std::atomic<int> n_users{0};
-      h->ldlt_x.pick = ((int)getpid() + n_users.fetch_add(1)) & 7;
-    }
-    if (prof) {
-      for (double& m : h->phase_ms) m = 0;
-      h->ev_n = 0;
-      for (hipEvent_t& e : h->ev) if (!e) ORBG_HIP(hipEventCreate(&e));
-    }
-    return ORBG_OK;
+    if ((rc = h->ldlt.plan(n, st))) return rc;
+    h->timer.on = prof;
+    return h->timer.reset();
   }
 
   int upload() {
@@ -536,94 +486,68 @@ struct EgRun {
     ORBG_HIP(hipGetLastError());
     ORBG_HIP(hipMemcpyAsync(h->rec.h, h->d_rec.p, sizeof(EgRec), hipMemcpyDeviceToHost, st));
     ORBG_HIP(hipStreamSynchronize(st));
-    flush();
+    h->timer.flush(st);
     return ORBG_OK;
   }
 
   // computeActiveErrors + buildSystem of state `buf`; the record brings chi2 and the largest diagonal entry
   int linearise(int buf) {
-    ph_begin(kPhLin);
+    h->timer.begin(kPhLin, st);
     hipLaunchKernelGGL(k_eg_lin, dim3(n_blocks_lin), dim3(256), 0, st, NE, h->d_edges.p, h->d_est[buf].p, h->d_col.p, h->d_fixs.p, h->d_EJ.p,
                        h->d_partial.p);
-    ph_end();
-    ph_begin(kPhAssemble);
+    h->timer.end(st);
+    h->timer.begin(kPhAssemble, st);
     hipLaunchKernelGGL(k_eg_blocks, dim3(n_tasks), dim3(64), 0, st, F, h->d_task_start.p, h->d_items.p, h->d_EJ.p, h->d_Hd.p, h->d_bv.p, h->d_Hp.p);
     hipLaunchKernelGGL(k_eg_finish, dim3(1), dim3(256), 0, st, n_blocks_lin, h->d_partial.p, 0, h->d_scale_v.p, F, h->d_Hd.p, (const int*)nullptr,
                        h->d_rec.p);
-    ph_end();
+    h->timer.end(st);
     return fetch_record();
   }
 
   // one trial: solve with lambda, trial state into buffer cur ^ 1, its chi2
   int trial(double lambda) {
     const int from = cur, to = cur ^ 1;
-    ph_begin(kPhAssemble);
-    if (use_mfma) {
-      ORBG_HIP(hipMemsetAsync(h->d_St.p, 0, sizeof(double) * ldltm::tile_image_doubles(n), st));
-      ORBG_HIP(ldltm::launch_image_pad(n, h->d_St.p, st));
-    } else {
-      ORBG_HIP(hipMemsetAsync(h->d_S.p, 0, sizeof(double) * (size_t)n * n, st));
-    }
-    ORBG_HIP(hipMemsetAsync(h->d_x.p, 0, sizeof(double) * (size_t)n, st));
+    int rc;
+    h->timer.begin(kPhAssemble, st);
+    if ((rc = h->ldlt.clear(h->d_x.p, st))) return rc;
     hipLaunchKernelGGL(k_eg_scatter, dim3(n_tasks), dim3(64), 0, st, F, h->d_pair_i.p, h->d_pair_j.p, h->d_Hd.p, h->d_bv.p, h->d_Hp.p, lambda,
-                       use_mfma ? (double*)nullptr : h->d_S.p, use_mfma ? h->d_St.p : (double*)nullptr);
-    ph_end();
-    ph_begin(kPhLdlt);
-    if (use_xcd) ORBG_HIP(ldltx::launch(h->ldlt_x, n, h->d_St.p, h->d_x.p, h->d_ok.p, st, ldltx::kMaxP, h->ldlt_xcd == 2, false));
-    else if (use_mfma) ORBG_HIP(ldltm::launch(n, h->d_St.p, h->d_x.p, h->d_ok.p, h->d_wfac.p, st, &h->ldlt_attr));
-    else ORBG_HIP(launch_ldlt_wide(n, h->d_S.p, h->d_bv.p, h->d_x.p, h->d_ok.p, h->d_wide.p, st));
-    ph_end();
-    ph_begin(kPhUpdate);
+                       h->ldlt.S(), h->ldlt.St());
+    h->timer.end(st);
+    h->timer.begin(kPhLdlt, st);
+    if ((rc = h->ldlt.launch(h->d_bv.p, h->d_x.p, h->d_ok.p, st))) return rc;
+    h->timer.end(st);
+    h->timer.begin(kPhUpdate, st);
     hipLaunchKernelGGL(k_eg_update, dim3((NV + 255) / 256), dim3(256), 0, st, NV, h->d_col.p, h->d_fixs.p, h->d_est[from].p, h->d_x.p, h->d_bv.p, lambda,
                        h->d_ok.p, h->d_est[to].p, h->d_scale_v.p);
     hipLaunchKernelGGL(k_eg_errors, dim3(n_blocks_e), dim3(256), 0, st, NE, h->d_edges.p, h->d_est[to].p, h->d_partial.p, (double*)nullptr);
     hipLaunchKernelGGL(k_eg_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, NV, h->d_scale_v.p, 0, (const double*)nullptr, h->d_ok.p,
                        h->d_rec.p);
-    ph_end();
+    h->timer.end(st);
     return fetch_record();
   }
 
-  static constexpr int kRcTimedOut = -70001;      // the eight-workgroup LDL^T missed a participant (never leaves the library)
-
-  // SparseOptimizer::optimize with OptimizationAlgorithmLevenberg::solve as its iteration (decisions: lm_driver.hpp); no stop flag
-  int optimize(int iterations, int* done_out) {
-    int done = 0, rc;
-    bool ok = true;
-    for (int it = 0; it < iterations && ok; it++) {
-      if ((rc = linearise(cur))) return rc;
-      lm.currentChi = h->rec.h->chi2;
-      if (it == 0) {
-        lm.lambda = lm_lambda_init(p->lambda_init, h->rec.h->maxdiag);
-        lm.ni = 2; lm.nBad = 0;
-        r->err0 = lm.currentChi;
-        if (r->edge_error0) {                      // the error vectors of the initial estimate, as the linearisation stored them
-          ORBG_HIP(hipMemcpy2DAsync(r->edge_error0, 7 * sizeof(double), h->d_EJ.p + 98, kEJ * sizeof(double), 7 * sizeof(double), (size_t)NE,
-                                    hipMemcpyDeviceToHost, st));
-          ORBG_HIP(hipStreamSynchronize(st));
-        }
-      }
-      const double iniChi = lm.currentChi;
-      double rho = 0;
-      int qmax = 0;
-      bool accepted = false;
-      do {
-        if ((rc = trial(lm.lambda))) return rc;
-        if (h->rec.h->ok == ldltx::kOkTimedOut) return kRcTimedOut;
-        rho = lm_trial_verdict(lm, h->rec.h->ok != 0, h->rec.h->chi2, h->rec.h->scale, &accepted);
-        if (accepted) cur ^= 1;                    // discardTop(): keep the trial state; pop() otherwise
-        qmax++;
-      } while (lm_try_again(rho, qmax < 10, false));
-      done++;
-      r->errEnd = lm.currentChi;
-      if (r->trace && r->trace_len < r->trace_cap) {
-        double* t = r->trace + 4 * (size_t)r->trace_len;
-        t[0] = qmax; t[1] = accepted ? 1 : 0; t[2] = lm.currentChi; t[3] = lm.lambda;
-        r->trace_len++;
-      }
-      ok = lm_iteration_continues(lm, qmax == 10, rho, iniChi);
+  // ---- what lm_optimize (lm_driver.hpp) asks of a solve; no stop flag here
+  int linearise() { return linearise(cur); }
+  const EgRec& record() const { return *h->rec.h; }
+  int timed_out() const { return LdltSolver::timed_out(h->rec.h->ok) ? kRcLdltTimedOut : ORBG_OK; }
+  void accept() { cur ^= 1; }
+  int first_linearisation(double* user_lambda) {
+    *user_lambda = p->lambda_init;
+    r->err0 = lm.currentChi;
+    if (r->edge_error0) {                        // the error vectors of the initial estimate, as the linearisation stored them
+      ORBG_HIP(hipMemcpy2DAsync(r->edge_error0, 7 * sizeof(double), h->d_EJ.p + 98, kEJ * sizeof(double), 7 * sizeof(double), (size_t)NE,
+                                hipMemcpyDeviceToHost, st));
+      ORBG_HIP(hipStreamSynchronize(st));
     }
-    *done_out = done;
     return ORBG_OK;
+  }
+  void iteration_done(int qmax, bool accepted) {
+    r->errEnd = lm.currentChi;
+    if (r->trace && r->trace_len < r->trace_cap) {
+      double* t = r->trace + 4 * (size_t)r->trace_len;
+      t[0] = qmax; t[1] = accepted ? 1 : 0; t[2] = lm.currentChi; t[3] = lm.lambda;
+      r->trace_len++;
+    }
   }
 
   int download() {
@@ -647,11 +571,12 @@ int eg_attempt(EgArea* h, EgRun& run) {
   run.r->trace_len = 0;
   if ((rc = run.buffers()) || (rc = run.upload())) return rc;
   int done = 0;
-  if ((rc = run.optimize(run.p->iterations, &done))) return rc;
+  StopCheck no_flag;
+  if ((rc = lm_optimize(run, run.p->iterations, no_flag, &done))) return rc;
   run.r->iters = done;
   rc = run.download();
-  run.flush();
-  if (run.prof) for (int i = 0; i < 4; i++) t_eg_phase_ms[i] = h->phase_ms[i];
+  h->timer.flush(h->stream);
+  if (run.prof) for (int i = 0; i < 4; i++) t_eg_phase_ms[i] = h->timer.ms[i];
   return rc;
 }
 
@@ -672,14 +597,8 @@ extern "C" int eg_solve(const eg_problem* p, eg_result* r) {
   EgRun run(&area, p, r, F);
   run.host_state();
   run.structure();
-  rc = eg_attempt(&area, run);
-  if (rc != EgRun::kRcTimedOut) return rc;
-  // as in the bundle adjustments: not a verdict on the system -- solved again from the caller's untouched input on the one-workgroup
-  // kernels, which this thread then keeps using
-  area.ldlt_xcd = 0;
-  if (hipStreamSynchronize(area.stream) != hipSuccess) return ORBG_HIP_ERROR;
-  rc = eg_attempt(&area, run);
-  return rc == EgRun::kRcTimedOut ? ORBG_HIP_ERROR : rc;
+  // (a timed-out launch: solved again on the one-workgroup kernels, which this thread then keeps using)
+  return ldlt_retry(area.ldlt, area.stream, [&] { return eg_attempt(&area, run); });
 }
 
 extern "C" int eg_set_profiling(int on) {

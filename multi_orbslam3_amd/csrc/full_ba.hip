@@ -59,6 +59,7 @@ namespace {
 #include "ldlt_xcd.hpp"
 #include "ba_edge.hpp"
 #include "ldlt_wide.hpp"
+#include "ldlt_solver.hpp"
 
 constexpr int kEB = 27;                 // per-edge blocks: Hpl (6x3, 18) | Hll upper (6) | bl (3), as in lba.hip
 constexpr int kMaxCols = BA_MAX_FREE_POSES;
@@ -680,11 +681,7 @@ __global__ __launch_bounds__(256) void k_ba_weld_scatter(int n_kept, const int* 
 struct ba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
-  int ldlt_xcd = 1;                    // ORBG_LDLT_XCD=0: 21 .. 50 free poses stay on the one-workgroup kernels
-  bool ldlt_wide = false;              // ORBG_LDLT_WIDE: every size on k_wide_*
-  ldltm::AttrCache ldlt_attr;
-  ldltx::Context ldlt_x;
-  DevBuf<double> d_xscr; DevBuf<unsigned> d_xflags;
+  LdltSolver ldlt;                     // the solver of the reduced camera system (its switches: read by ba_create)
   DevBuf<lba_edge> d_edges;
   DevBuf<PoseQ> d_poses[2];
   DevBuf<double> d_points[2];
@@ -694,7 +691,7 @@ struct ba_handle {
   DevBuf<long long> d_total;
   DevBuf<BaItem> d_items;
   DevBuf<CamRig> d_cams;
-  DevBuf<double> d_chi2, d_partial, d_EB, d_Hll, d_bl, d_Hpp, d_bp, d_Dinv, d_Db, d_S, d_bs, d_x, d_St, d_wfac, d_wide, d_scale_v;
+  DevBuf<double> d_chi2, d_partial, d_EB, d_Hll, d_bl, d_Hpp, d_bp, d_Dinv, d_Db, d_bs, d_x, d_scale_v;
   DevBuf<uint8_t> d_depth;
   // welding BA: the level-0 edges and their chi2 (exchanged with d_edges / d_chi2 while round 2 runs), levels, keep flags, their scan, origins
   DevBuf<lba_edge> d_edges_kept;
@@ -708,11 +705,7 @@ struct ba_handle {
   std::vector<double> s_points;
   std::vector<int> s_pose_col;
   std::vector<CamRig> s_cams;
-  int prof_on = 0;
-  double phase_ms[5] = {0, 0, 0, 0, 0};
-  hipEvent_t ev[32] = {};
-  int ev_phase[16] = {};
-  int ev_n = 0;
+  PhaseTimer<5> timer;                 // ba_set_profiling
 };
 
 namespace {
@@ -763,7 +756,6 @@ struct BaRun {
   Huber hb;
   int NP, NX, NE, nP, n;
   int n_blocks_e = 0, n_pairs = 0, n_tiles = 0, tile = kTileEdges;
-  bool use_mfma = false, use_xcd = false, use_wide = false;
   int cur = 0;
   int trials = 0;
   int robust;                          // Huber kernels on every edge: the value of the round that is running
@@ -774,26 +766,6 @@ struct BaRun {
     hb.delta_mono = (float)std::sqrt(5.99); hb.dsqr_mono = hb.delta_mono * hb.delta_mono;           // S/Optimizer.cc:131-132: 5.99 here, not the local BA's 5.991
     hb.delta_stereo = (float)std::sqrt(7.815); hb.dsqr_stereo = hb.delta_stereo * hb.delta_stereo;
     n_blocks_e = (NE + 255) / 256;
-  }
-
-  // ---- phase timing (ba_set_profiling): event pairs around launch groups, read at the next synchronisation
-  void ph_begin(int phase) {
-    if (!h->prof_on) return;
-    if (h->ev_n == 16) flush();
-    if (hipEventRecord(h->ev[2 * h->ev_n], st) == hipSuccess) h->ev_phase[h->ev_n] = phase;
-  }
-  void ph_end() {
-    if (!h->prof_on) return;
-    if (hipEventRecord(h->ev[2 * h->ev_n + 1], st) == hipSuccess) h->ev_n++;
-  }
-  void flush() {
-    if (!h->prof_on) return;
-    (void)hipStreamSynchronize(st);
-    for (int i = 0; i < h->ev_n; i++) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, h->ev[2 * i], h->ev[2 * i + 1]) == hipSuccess) h->phase_ms[h->ev_phase[i]] += ms;
-    }
-    h->ev_n = 0;
   }
 
   void initial_state() {
@@ -860,23 +832,7 @@ struct BaRun {
         (rc = h->d_depth.reserve(sNE)) || (rc = h->d_ok.reserve(4)) || (rc = h->d_rec.reserve(1)) || (rc = h->rec.reserve(1)) ||
         (rc = h->d_total.reserve(4)) || (rc = h->total_h.reserve(4)))
       return rc;
-    // the solver of the reduced camera system, by size
-    use_mfma = nP >= 1 && ldltm::supports(n) && !h->ldlt_wide;
-    use_wide = nP >= 1 && !use_mfma;
-    if (use_wide && n > kWideMaxUnknowns) return ORBG_CAP_EXCEEDED;
-    if (use_wide && ((rc = h->d_wide.reserve(2 * (size_t)n + 32)) || (rc = h->d_S.reserve((size_t)n * n)))) return rc;
-    if (use_mfma && ((rc = h->d_St.reserve(ldltm::tile_image_doubles(n))) || (rc = h->d_wfac.reserve(ldltm::wglob_doubles(ldltm::make_geo(n))))))
-      return rc;
-    use_xcd = use_mfma && h->ldlt_xcd != 0 && ldltx::pays(n);
-    if (use_xcd && !h->ldlt_x.scr) {
-      if ((rc = h->d_xscr.reserve(ldltx::scratch_doubles())) || (rc = h->d_xflags.reserve(ldltx::kFlagWords))) return rc;
-      ORBG_HIP(hipMemsetAsync(h->d_xflags.p, 0, ldltx::kFlagWords * sizeof(unsigned), st));
-      ORBG_HIP(hipMemsetAsync(h->d_xscr.p + ldltx::kGbOff, 0, (ldltx::kWOff - ldltx::kGbOff) * sizeof(double), st));
-      h->ldlt_x.bind(h->d_xscr.p, h->d_xflags.p);
-      static std::atomic<int> n_users{0};
-      h->ldlt_x.pick = ((int)getpid() + n_users.fetch_add(1)) & 7;
-    }
-    return ORBG_OK;
+    return h->ldlt.plan(n, st);
   }
 
   int upload() {
@@ -914,13 +870,13 @@ struct BaRun {
   // ---- BlockSolver::buildStructure on the device
   int structure() {
     int rc;
-    ph_begin(kPhStructure);
+    h->timer.begin(kPhStructure, st);
     if (NX > 0) {
       ORBG_HIP(hipMemsetAsync(h->d_pt_start.p, 0, sizeof(int) * (size_t)NX, st));
       ORBG_HIP(hipMemsetAsync(h->d_pt_end.p, 0, sizeof(int) * (size_t)NX, st));
     }
     if (NE > 0) hipLaunchKernelGGL(k_ba_ranges, dim3(n_blocks_e), dim3(256), 0, st, NE, h->d_edges.p, h->d_pt_start.p, h->d_pt_end.p);
-    if (nP == 0) { ph_end(); ORBG_HIP(hipGetLastError()); return ORBG_OK; }
+    if (nP == 0) { h->timer.end(st); ORBG_HIP(hipGetLastError()); return ORBG_OK; }
     // the edges of every free pose, ascending
     tile = kTileEdges * std::max(1, (int)(((long long)NE + (long long)kTileEdges * kMaxTiles - 1) / ((long long)kTileEdges * kMaxTiles)));
     n_tiles = std::max(1, (int)(((long long)NE + tile - 1) / tile));
@@ -967,7 +923,7 @@ struct BaRun {
     if ((rc = h->d_items.reserve((size_t)std::max<long long>(n_items, 1)))) return rc;
     hipLaunchKernelGGL(k_ba_items_fill, dim3(n_pairs), dim3(256), 0, st, n_pairs, h->d_pair_i.p, h->d_pair_j.p, h->d_row_start.p,
                        h->d_row_edges.p, h->d_edges.p, h->d_pt_start.p, h->d_pt_end.p, h->d_pose_col.p, h->d_item_start.p, h->d_items.p);
-    ph_end();
+    h->timer.end(st);
     ORBG_HIP(hipGetLastError());
     return ORBG_OK;
   }
@@ -977,13 +933,13 @@ struct BaRun {
     ORBG_HIP(hipGetLastError());
     ORBG_HIP(hipMemcpyAsync(h->rec.h, h->d_rec.p, sizeof(BaRec), hipMemcpyDeviceToHost, st));
     ORBG_HIP(hipStreamSynchronize(st));
-    flush();
+    h->timer.flush(st);
     return ORBG_OK;
   }
 
   // computeActiveErrors + buildSystem of state `buf`; the record brings chi2 and the largest diagonal entry
   int linearise(int buf) {
-    ph_begin(kPhLin);
+    h->timer.begin(kPhLin, st);
     if (NE > 0) {
       hipLaunchKernelGGL(k_ba_lin, dim3(n_blocks_e), dim3(256), 0, st, NE, h->d_edges.p, h->d_poses[buf].p, h->d_points[buf].p, h->d_pose_cam.p,
                          h->d_cams.p, robust, hb, h->d_chi2.p, h->d_partial.p, h->d_EB.p);
@@ -995,40 +951,32 @@ struct BaRun {
                          h->d_points[buf].p, h->d_pose_cam.p, h->d_cams.p, robust, hb, h->d_chi2.p, h->d_Hpp.p, h->d_bp.p);
     hipLaunchKernelGGL(k_ba_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, 0, h->d_scale_v.p, nP, h->d_Hpp.p, NX, h->d_Hll.p,
                        h->d_pt_start.p, h->d_pt_end.p, (const int*)nullptr, h->d_rec.p);
-    ph_end();
+    h->timer.end(st);
     return fetch_record();
   }
 
   // one trial: solve with lambda, trial state into buffer cur ^ 1, its evaluation
   int trial(double lambda) {
     const int from = cur, to = cur ^ 1;
-    ph_begin(kPhSchur);
+    int rc;
+    h->timer.begin(kPhSchur, st);
     if (NX > 0)
       hipLaunchKernelGGL(k_ba_dinv, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_Hll.p, h->d_bl.p, lambda, h->d_Dinv.p, h->d_Db.p);
     if (nP > 0) {
-      // absent pairs: ONE fill of the dense system (the tile image's padding and border follow, they do not depend on the values)
-      if (use_mfma) {
-        ORBG_HIP(hipMemsetAsync(h->d_St.p, 0, sizeof(double) * ldltm::tile_image_doubles(n), st));
-        ORBG_HIP(ldltm::launch_image_pad(n, h->d_St.p, st));
-      } else {
-        ORBG_HIP(hipMemsetAsync(h->d_S.p, 0, sizeof(double) * (size_t)n * n, st));
-      }
-      ORBG_HIP(hipMemsetAsync(h->d_x.p, 0, sizeof(double) * (size_t)n, st));
+      if ((rc = h->ldlt.clear(h->d_x.p, st))) return rc;
       hipLaunchKernelGGL(k_ba_schur, dim3(n_pairs), dim3(256), 0, st, nP, h->d_pair_i.p, h->d_pair_j.p, h->d_item_start.p, h->d_items.p,
-                         h->d_edges.p, h->d_EB.p, h->d_Dinv.p, h->d_Db.p, h->d_Hpp.p, h->d_bp.p, lambda, use_mfma ? (double*)nullptr : h->d_S.p,
-                         h->d_bs.p, use_mfma ? h->d_St.p : (double*)nullptr);
+                         h->d_edges.p, h->d_EB.p, h->d_Dinv.p, h->d_Db.p, h->d_Hpp.p, h->d_bp.p, lambda, h->ldlt.S(), h->d_bs.p,
+                         h->ldlt.St());
     }
-    ph_end();
-    ph_begin(kPhLdlt);
+    h->timer.end(st);
+    h->timer.begin(kPhLdlt, st);
     if (nP > 0) {
-      if (use_xcd) ORBG_HIP(ldltx::launch(h->ldlt_x, n, h->d_St.p, h->d_x.p, h->d_ok.p, st, ldltx::kMaxP, h->ldlt_xcd == 2, false));
-      else if (use_mfma) ORBG_HIP(ldltm::launch(n, h->d_St.p, h->d_x.p, h->d_ok.p, h->d_wfac.p, st, &h->ldlt_attr));
-      else ORBG_HIP(launch_ldlt_wide(n, h->d_S.p, h->d_bs.p, h->d_x.p, h->d_ok.p, h->d_wide.p, st));
+      if ((rc = h->ldlt.launch(h->d_bs.p, h->d_x.p, h->d_ok.p, st))) return rc;
     } else {
       hipLaunchKernelGGL(k_ba_set_ok, dim3(1), dim3(1), 0, st, h->d_ok.p);
     }
-    ph_end();
-    ph_begin(kPhUpdate);
+    h->timer.end(st);
+    h->timer.begin(kPhUpdate, st);
     hipLaunchKernelGGL(k_ba_update, dim3((NP + NX + 255) / 256), dim3(256), 0, st, NP, NX, h->d_pose_col.p, h->d_poses[from].p, h->d_points[from].p,
                        h->d_x.p, h->d_pt_start.p, h->d_pt_end.p, h->d_edges.p, h->d_EB.p, h->d_Dinv.p, h->d_bl.p, h->d_bp.p, lambda, h->d_ok.p,
                        h->d_poses[to].p, h->d_points[to].p, h->d_scale_v.p);
@@ -1037,47 +985,29 @@ struct BaRun {
                          h->d_cams.p, robust, hb, h->d_chi2.p, h->d_partial.p);
     hipLaunchKernelGGL(k_ba_finish, dim3(1), dim3(256), 0, st, n_blocks_e, h->d_partial.p, NP + NX, h->d_scale_v.p, 0, (const double*)nullptr, 0,
                        (const double*)nullptr, h->d_pt_start.p, h->d_pt_end.p, h->d_ok.p, h->d_rec.p);
-    ph_end();
+    h->timer.end(st);
+    trials++;
     return fetch_record();
   }
 
-  // ---- SparseOptimizer::optimize with OptimizationAlgorithmLevenberg::solve as its iteration (decisions: lm_driver.hpp)
-  int optimize(int iterations, int* done_out) {
-    int done = 0, rc;
-    bool ok = true;
-    for (int it = 0; it < iterations && !stop() && ok; it++) {
-      if ((rc = linearise(cur))) return rc;
-      lm.currentChi = h->rec.h->chi2;
-      if (it == 0) {
-        lm.lambda = lm_lambda_init(0.0, h->rec.h->maxdiag);
-        lm.ni = 2; lm.nBad = 0;
-        r->chi2_initial = lm.currentChi;
-      }
-      const double iniChi = lm.currentChi;
-      double rho = 0;
-      int qmax = 0;
-      do {
-        if ((rc = trial(lm.lambda))) return rc;
-        trials++;
-        if (h->rec.h->ok == ldltx::kOkTimedOut) return kRcTimedOut;
-        bool accepted;
-        rho = lm_trial_verdict(lm, h->rec.h->ok != 0, h->rec.h->chi2, h->rec.h->scale, &accepted);
-        if (accepted) cur ^= 1;                    // discardTop(): keep the trial state; pop() otherwise
-        qmax++;
-        stop.trials_done++;
-      } while (lm_try_again(rho, qmax < 10, stop()));
-      done++;
-      r->chi2_final = lm.currentChi;
-      if (r->trace && r->trace_len < r->trace_cap) {
-        r->trace[3 * r->trace_len] = lm.lambda; r->trace[3 * r->trace_len + 1] = lm.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
-        r->trace_len++;
-      }
-      ok = lm_iteration_continues(lm, qmax == 10, rho, iniChi);
-    }
-    *done_out = done;
+  // ---- what lm_optimize (lm_driver.hpp) asks of a solve
+  int linearise() { return linearise(cur); }
+  const BaRec& record() const { return *h->rec.h; }
+  int timed_out() const { return LdltSolver::timed_out(h->rec.h->ok) ? kRcLdltTimedOut : ORBG_OK; }
+  void accept() { cur ^= 1; }
+  int first_linearisation(double* user_lambda) {
+    *user_lambda = 0.0;
+    r->chi2_initial = lm.currentChi;
     return ORBG_OK;
   }
-  static constexpr int kRcTimedOut = -70001;      // the eight-workgroup LDL^T missed a participant (never leaves the library)
+  void iteration_done(int qmax, bool) {
+    r->chi2_final = lm.currentChi;
+    if (r->trace && r->trace_len < r->trace_cap) {
+      r->trace[3 * r->trace_len] = lm.lambda; r->trace[3 * r->trace_len + 1] = lm.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
+      r->trace_len++;
+    }
+  }
+  int optimize(int iterations, int* done) { return lm_optimize(*this, iterations, stop, done); }
 
   // ---- results: chi2 of the LAST error evaluation, depth test with the final estimate
   int download() {
@@ -1113,11 +1043,7 @@ int ba_attempt(ba_handle* h, const ba_problem* p, StopRef ref, ba_result* r, int
   run.initial_state();
   if (ba_runs_no_iteration(p, ref)) return run.finish_without_iterations();       // (uses the handle's host arrays only)
   if ((rc = select_device(h->device))) return rc;
-  if (h->prof_on) {
-    for (double& m : h->phase_ms) m = 0;
-    h->ev_n = 0;
-    for (hipEvent_t& e : h->ev) if (!e) ORBG_HIP(hipEventCreate(&e));
-  }
+  if ((rc = h->timer.reset())) return rc;
   StreamDrain drain{h->stream};
   if ((rc = run.buffers()) || (rc = run.upload()) || (rc = run.structure())) return rc;
   int done = 0;
@@ -1125,7 +1051,7 @@ int ba_attempt(ba_handle* h, const ba_problem* p, StopRef ref, ba_result* r, int
   r->iters = done;
   if (done == 0) return run.finish_without_iterations();
   rc = run.download();
-  run.flush();
+  h->timer.flush(h->stream);
   return rc;
 }
 
@@ -1133,14 +1059,8 @@ int ba_solve_impl(ba_handle* h, const ba_problem* p, StopRef ref, ba_result* r, 
   if (!h) return ORBG_BAD_ARG;
   int nP = validated_free, rc;
   if (nP < 0 && (rc = ba_validate(p, r, &nP))) return rc;
-  rc = ba_attempt(h, p, ref, r, nP);
-  if (rc != BaRun::kRcTimedOut) return rc;
-  // as in the local BA: not a verdict on the system -- the problem is solved again from the caller's untouched input on the
-  // one-workgroup kernels, which this handle then keeps using
-  h->ldlt_xcd = 0;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return ORBG_HIP_ERROR;
-  rc = ba_attempt(h, p, ref, r, nP);
-  return rc == BaRun::kRcTimedOut ? ORBG_HIP_ERROR : rc;
+  // (a timed-out launch: solved again on the one-workgroup kernels, which this handle then keeps using)
+  return ldlt_retry(h->ldlt, h->stream, [&] { return ba_attempt(h, p, ref, r, nP); });
 }
 
 int ba_solve_once(const ba_problem* p, StopRef ref, ba_result* r) {
@@ -1215,11 +1135,7 @@ int weld_attempt(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_weld_r
   run.initial_state();
   if (ba_runs_no_iteration(p, ref)) return run.finish_without_iterations();       // (uses the handle's host arrays only)
   if ((rc = select_device(h->device))) return rc;
-  if (h->prof_on) {
-    for (double& m : h->phase_ms) m = 0;
-    h->ev_n = 0;
-    for (hipEvent_t& e : h->ev) if (!e) ORBG_HIP(hipEventCreate(&e));
-  }
+  if ((rc = h->timer.reset())) return rc;
   StreamDrain drain{h->stream};
   if ((rc = run.buffers()) || (rc = run.upload()) || (rc = run.structure())) return rc;
   int done = 0;
@@ -1233,13 +1149,13 @@ int weld_attempt(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_weld_r
     if ((rc = h->d_level.reserve(sNE)) || (rc = h->d_keep.reserve(sNE)) || (rc = h->d_keep_off.reserve(sNE + 1)) ||
         (rc = h->d_origin.reserve(sNE)) || (rc = h->d_edges_kept.reserve(sNE)) || (rc = h->d_chi2_kept.reserve(sNE)))
       return rc;
-    run.ph_begin(kPhStructure);
+    h->timer.begin(kPhStructure, run.st);
     hipLaunchKernelGGL(k_ba_weld_classify, dim3(run.n_blocks_e), dim3(256), 0, run.st, NE, h->d_edges.p, h->d_poses[run.cur].p,
                        h->d_points[run.cur].p, h->d_chi2.p, wp->chi2_mono, wp->chi2_stereo, h->d_level.p, h->d_keep.p);
     hipLaunchKernelGGL(k_ba_scan, dim3(1), dim3(1024), 0, run.st, NE, h->d_keep.p, h->d_keep_off.p, h->d_total.p);
     hipLaunchKernelGGL(k_ba_weld_compact, dim3(run.n_blocks_e), dim3(256), 0, run.st, NE, h->d_edges.p, h->d_keep.p, h->d_keep_off.p,
                        h->d_edges_kept.p, h->d_origin.p);
-    run.ph_end();
+    h->timer.end(run.st);
     ORBG_HIP(hipGetLastError());
     ORBG_HIP(hipMemcpyAsync(wr->edge_level, h->d_level.p, sNE, hipMemcpyDeviceToHost, run.st));
     long long kept64 = 0;
@@ -1264,7 +1180,7 @@ int weld_attempt(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_weld_r
     }
   }
   rc = run.download();
-  run.flush();
+  h->timer.flush(h->stream);
   return rc;
 }
 
@@ -1272,13 +1188,8 @@ int weld_solve_impl(ba_handle* h, const ba_weld_problem* wp, StopRef ref, ba_wel
   if (!h) return ORBG_BAD_ARG;
   int nP = validated_free, rc;
   if (nP < 0 && (rc = weld_validate(wp, wr, &nP))) return rc;
-  rc = weld_attempt(h, wp, ref, wr, nP);
-  if (rc != BaRun::kRcTimedOut) return rc;
-  // as in ba_solve_impl, for the whole call: both rounds again from the caller's untouched input on the one-workgroup kernels
-  h->ldlt_xcd = 0;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return ORBG_HIP_ERROR;
-  rc = weld_attempt(h, wp, ref, wr, nP);
-  return rc == BaRun::kRcTimedOut ? ORBG_HIP_ERROR : rc;
+  // (as in ba_solve_impl, for the whole call: both rounds again)
+  return ldlt_retry(h->ldlt, h->stream, [&] { return weld_attempt(h, wp, ref, wr, nP); });
 }
 
 int weld_solve_once(const ba_weld_problem* wp, StopRef ref, ba_weld_result* wr) {
@@ -1304,8 +1215,7 @@ extern "C" int ba_create(int device, int cap_poses, int cap_points, int cap_edge
   if (rc) return rc;
   ba_handle* h = new ba_handle();
   h->device = device;
-  h->ldlt_wide = getenv("ORBG_LDLT_WIDE") != nullptr;
-  if (const char* e = getenv("ORBG_LDLT_XCD")) h->ldlt_xcd = !strcmp(e, "0") ? 0 : !strcmp(e, "safe") ? 2 : 1;
+  h->ldlt.read_env();
   if (orbg::create_stream(&h->stream, "lba") != hipSuccess) { delete h; return ORBG_HIP_ERROR; }
   (void)cap_poses; (void)cap_points; (void)cap_edges;   // unused: buffers grow on first use and are kept
   *out = h;
@@ -1316,19 +1226,19 @@ extern "C" int ba_destroy(ba_handle* h) {
   if (!h) return ORBG_BAD_ARG;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  h->d_xscr.release(); h->d_xflags.release(); h->ldlt_x.scr = nullptr; h->ldlt_x.flags = nullptr;
+  h->ldlt.release();
   h->d_edges.release();
   for (int i = 0; i < 2; i++) { h->d_poses[i].release(); h->d_points[i].release(); }
   for (DevBuf<int>* b : {&h->d_pose_col, &h->d_pose_cam, &h->d_pt_start, &h->d_pt_end, &h->d_table, &h->d_row_count, &h->d_row_start, &h->d_row_edges,
                          &h->d_pair_cnt, &h->d_pair_row_start, &h->d_pair_i, &h->d_pair_j, &h->d_item_cnt, &h->d_item_start, &h->d_ok})
     b->release();
-  for (DevBuf<double>* b : {&h->d_chi2, &h->d_partial, &h->d_EB, &h->d_Hll, &h->d_bl, &h->d_Hpp, &h->d_bp, &h->d_Dinv, &h->d_Db, &h->d_S, &h->d_bs,
-                            &h->d_x, &h->d_St, &h->d_wfac, &h->d_wide, &h->d_scale_v})
+  for (DevBuf<double>* b : {&h->d_chi2, &h->d_partial, &h->d_EB, &h->d_Hll, &h->d_bl, &h->d_Hpp, &h->d_bp, &h->d_Dinv, &h->d_Db, &h->d_bs,
+                            &h->d_x, &h->d_scale_v})
     b->release();
   h->d_edges_kept.release(); h->d_chi2_kept.release(); h->d_level.release(); h->d_keep.release(); h->d_keep_off.release(); h->d_origin.release();
   h->d_bitmap.release(); h->d_total.release(); h->d_items.release(); h->d_cams.release(); h->d_depth.release(); h->d_rec.release();
   h->rec.release(); h->total_h.release();
-  for (hipEvent_t& e : h->ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+  h->timer.release();
   orbg::release_stream(h->stream);
   delete h;
   return ORBG_OK;
@@ -1368,11 +1278,11 @@ extern "C" int ba_weld_solve_b(const ba_weld_problem* p, const volatile uint8_t*
 }
 extern "C" int ba_set_profiling(ba_handle* h, int on) {
   if (!h) return ORBG_BAD_ARG;
-  h->prof_on = on ? 1 : 0;
+  h->timer.on = on != 0;
   return ORBG_OK;
 }
 extern "C" int ba_get_phase_ms(ba_handle* h, double* ms) {
   if (!h || !ms) return ORBG_BAD_ARG;
-  for (int i = 0; i < 5; i++) ms[i] = h->phase_ms[i];
+  for (int i = 0; i < 5; i++) ms[i] = h->timer.ms[i];
   return ORBG_OK;
 }

@@ -1132,6 +1132,7 @@ __global__ __launch_bounds__(kSchurThreads) void k_schur(int nP, const int* __re
 }
 
 #include "ldlt_wide.hpp"   // k_wide_panel / k_wide_update / k_wide_back, launch_ldlt_wide: shared with full_ba.hip
+#include "ldlt_solver.hpp" // LdltSolver, ldlt_retry: shared with full_ba.hip and essential_graph.hip
 
 // trial state = oplus(current, x): poses exp(x_p) * T; points X + x_l with the landmark back-substitution
 // x_l = Dinv_l (bl_l - sum_i Hpl_il^T x_i) folded in (x_l is also stored for computeScale)
@@ -1310,24 +1311,8 @@ __global__ __launch_bounds__(256) void k_finish_items(int n_partial, const doubl
 
 // ---------------------------------------------------------------------------------------------- handle
 
-// The one switch of the solve (read ONCE, when the handle is created -- the solve path itself never calls getenv):
-// ORBG_LDLT_WIDE=1 sends every window to the many-workgroup blocked LDL^T (k_wide_*: the solver of windows beyond 50 free poses) so
-// that tests can run it on small problems.  Round 5 removed the measured-slower variants of rounds 1-4 (vector-ALU LDL^T kernels,
-// the fused solve + update launch, the A/B forms of the start of a solve): docs/experiments.md keeps their numbers.
-// ORBG_LDLT_XCD=0 keeps windows of 21 .. 50 free poses on the one-workgroup kernels instead of the eight-workgroup one
-// (ldlt_xcd.hpp); =safe forces that kernel's agent-scope hand-overs (the path it takes by itself when its workgroups do not
-// share an XCD).
-struct LbaSwitches {
-  bool ldlt_wide = false;
-  int ldlt_xcd = 1;                    // 0 off, 1 on (9 .. 19 tile rows), 2 on with forced safe hand-overs
-  bool ldlt_xcd_short_once = false;    // test hook (ORBG_LDLT_XCD=short): the handle's first eight-workgroup launch misses a participant
-  static LbaSwitches from_env() {
-    LbaSwitches w;
-    w.ldlt_wide = getenv("ORBG_LDLT_WIDE") != nullptr;
-    if (const char* e = getenv("ORBG_LDLT_XCD")) { w.ldlt_xcd = !strcmp(e, "0") ? 0 : !strcmp(e, "safe") ? 2 : 1; w.ldlt_xcd_short_once = !strcmp(e, "short"); }
-    return w;
-  }
-};
+// (Round 5 removed the measured-slower variants of rounds 1-4 -- vector-ALU LDL^T kernels, the fused solve + update launch, the A/B
+// forms of the start of a solve: docs/experiments.md keeps their numbers.  The switches that are left are the solver's, ldlt_solver.hpp.)
 // One linearisation of the system: per edge the Jacobian products (EB), per active point Hll / bl, per free pose Hpp / bp.  The
 // handle keeps two: while the host waits for the verdict on a trial, the linearisation of the TRIAL state (= the next
 // iteration's, if the trial is accepted -- the usual case) is already running into the other set.
@@ -1347,23 +1332,17 @@ struct lba_handle {
   int device = 0;
   hipStream_t stream = nullptr;
   bool ext_stream = false;             // `stream` was handed in through lba_set_stream (never destroyed here)
-  LbaSwitches sw;
-  ldltm::AttrCache ldlt_attr;          // which kernels of THIS handle's device already allow their dynamic LDS size
-  ldltx::Context ldlt_x;               // flags / scratch / launch counter of the eight-workgroup LDL^T
-  long long xcd_timeouts = 0;          // launches of it that reported kOkTimedOut (each one: the window re-solved on the one-workgroup kernels)
-  DevBuf<double> d_xscr;
-  DevBuf<unsigned> d_xflags;
+  LdltSolver ldlt;                     // the solver of the reduced camera system (its switches: read by lba_create); k_schur writes its dense S on every path
+  long long xcd_timeouts = 0;          // eight-workgroup launches that reported kOkTimedOut (each one: the window re-solved on the one-workgroup kernels)
   DevBuf<lba_edge> d_edges;
   PinnedBuf<lba_edge> edges_pin;       // the caller's edge list, copied (and validated, counted) in ONE pass
   DevBuf<PairItem> d_items_dev;        // pair items built by k_build_items (fixed-capacity segment per pose pair)
   DevBuf<int> d_pair_count;
   DevBuf<PoseQ> d_poses[2];
   DevBuf<double> d_points[2];
-  DevBuf<double> d_err, d_chi2, d_partial, d_S, d_bs, d_x;
+  DevBuf<double> d_err, d_chi2, d_partial, d_bs, d_x;
   LinSet lin[2];
   DevBuf<double> d_lambda0;            // lambda of a round's first trial / of the next trial, chi2 the round starts from (k_finish, k_errlin)
-  DevBuf<double> d_wide;               // running / scaled right-hand side of the many-workgroup LDL^T (k_wide_*)
-  DevBuf<double> d_St, d_wfac;         // reduced camera matrix as a tile image / factor scratch of the matrix-core LDL^T (ldlt_mfma.hpp)
   DevBuf<int> d_ok;
   PinnedBuf<HostRec> rec;
   unsigned rec_seq = 0;
@@ -1399,7 +1378,8 @@ extern "C" int lba_create(int device, int cap_poses, int cap_points, int cap_edg
   if (rc) return rc;
   lba_handle* h = new lba_handle();
   h->device = device;
-  h->sw = LbaSwitches::from_env();
+  h->ldlt.read_env();
+  h->ldlt.keep_dense = true;
   if (orbg::create_stream(&h->stream, "lba") != hipSuccess) { delete h; return ORBG_HIP_ERROR; }
   if ((rc = h->rec.reserve(4)) || (rc = h->d_ok.reserve(4))) { delete h; return rc; }
   memset(h->rec.h, 0, 4 * sizeof(HostRec));
@@ -1425,12 +1405,12 @@ extern "C" int lba_destroy(lba_handle* h) {
   }
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
-  h->d_xscr.release(); h->d_xflags.release(); h->ldlt_x.scr = nullptr; h->ldlt_x.flags = nullptr;
+  h->ldlt.release();
   h->d_edges.release(); h->edges_pin.release(); h->d_items_dev.release(); h->d_pair_count.release();
   for (int i = 0; i < 2; i++) { h->d_poses[i].release(); h->d_points[i].release(); }
-  h->d_err.release(); h->d_chi2.release(); h->d_partial.release(); h->d_S.release(); h->d_bs.release(); h->d_x.release();
+  h->d_err.release(); h->d_chi2.release(); h->d_partial.release(); h->d_bs.release(); h->d_x.release();
   for (LinSet& L : h->lin) L.release();
-  h->d_lambda0.release(); h->d_wide.release(); h->d_St.release(); h->d_wfac.release(); h->d_ok.release(); h->rec.release();
+  h->d_lambda0.release(); h->d_ok.release(); h->rec.release();
   h->up_h.release(); h->dl_h.release(); h->up_d.release(); h->d_scale_partial.release(); h->d_ticket.release(); h->sig.release();
   for (auto& e : h->prof_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   if (!h->ext_stream) orbg::release_stream(h->stream);
@@ -1471,21 +1451,14 @@ static int upload_arena(lba_handle* h, size_t off0, size_t off1, hipStream_t st)
   return ORBG_OK;
 }
 
-// internal: k_ldlt_xcd reported kOkTimedOut during this attempt (never leaves the library)
-constexpr int kRcLdltTimedOut = -70001;
 static int lba_solve_attempt(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r);
-// A launch of the eight-workgroup LDL^T whose participants were not all placed in time says so (ldlt_xcd.hpp: kOkTimedOut) instead of
-// posing as a non-positive-definite system, which the LM loop would answer with a rejected step and another trajectory than the
-// reference's.  The window is then solved again from the caller's (untouched) problem with that kernel switched off for this handle
-// -- the ORBG_LDLT_XCD=0 path, parity-tested like the default -- and the event is counted (lba_get_watchdog_count).
+// a timed-out eight-workgroup launch: the window is solved again from the caller's (untouched) problem with that kernel switched off
+// for this handle (ldlt_retry), and the event is counted (lba_get_watchdog_count)
 static int lba_solve_impl(lba_handle* h, const lba_problem* p, StopRef stop_ref, lba_result* r) {
-  int rc = lba_solve_attempt(h, p, stop_ref, r);
-  if (rc != kRcLdltTimedOut) return rc;
-  h->xcd_timeouts++;
-  h->sw.ldlt_xcd = 0;
-  if (hipStreamSynchronize(h->stream) != hipSuccess) return ORBG_HIP_ERROR;
-  rc = lba_solve_attempt(h, p, stop_ref, r);
-  return rc == kRcLdltTimedOut ? ORBG_HIP_ERROR : rc;
+  bool retried = false;
+  const int rc = ldlt_retry(h->ldlt, h->stream, [&] { return lba_solve_attempt(h, p, stop_ref, r); }, &retried);
+  if (retried) h->xcd_timeouts++;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------- one solve
@@ -1573,7 +1546,6 @@ struct LbaRun : LbaStructure {
   double* pointsB[3] = {};
   struct { uint8_t* flags; double* chi2; PoseQ* poses; double* points; } out{};   // k_export's outputs in the results block (dl_h)
   size_t o_rflags = 0, o_rchi = 0, o_rposes = 0, o_rpoints = 0;
-  bool use_mfma = false, use_wide = false, use_xcd = false;
   int n_blocks_u = 0;              // k_update's workgroups: also the number of its scale partials
   bool first2 = false;             // the first iteration went out in two launches (k_errlin_prep or k_csr_sort + k_errlin, k_finish_items)
   bool prof_this_solve = false, prof_pending = false;   // an event pair brackets one LDL^T launch of this call
@@ -1618,20 +1590,15 @@ struct LbaRun : LbaStructure {
       // (more pose pairs than compute units: the two-pass form, three workgroups per compute unit)
       const auto schur_fn = n_pairs_all > 256 ? k_schur<2> : k_schur<1>;
       hipLaunchKernelGGL(schur_fn, dim3(n_pairs_all), dim3(kSchurThreads), 0, st, nP, D.pair_i1, D.pair_i2, D.pair_start, D.items,
-                         L.EB.p, L.Hll.p, L.bl.p, L.Hpp.p, L.bp.p, lam, h->d_S.p, h->d_bs.p, lam_p, item_cap,
-                         dev_items ? h->d_pair_count.p : (const int*)nullptr, use_mfma ? h->d_St.p : (double*)nullptr);
+                         L.EB.p, L.Hll.p, L.bl.p, L.Hpp.p, L.bp.p, lam, h->ldlt.S(), h->d_bs.p, lam_p, item_cap,
+                         dev_items ? h->d_pair_count.p : (const int*)nullptr, h->ldlt.St());
       // (two event records and an elapsed-time query cost the solve ~8 us: one solve in four is enough for an average)
       const bool bracket = h->prof_on && !prof_pending && prof_this_solve;
       if (bracket) ORBG_HIP(hipEventRecord(h->prof_ev[0], st));
-      if (use_xcd) {
-        const bool one_short = h->sw.ldlt_xcd_short_once;
-        h->sw.ldlt_xcd_short_once = false;
-        ORBG_HIP(ldltx::launch(h->ldlt_x, n, h->d_St.p, h->d_x.p, h->d_ok.p, st, ldltx::kMaxP, h->sw.ldlt_xcd == 2, one_short));
-      } else if (use_mfma) {
-        ORBG_HIP(ldltm::launch(n, h->d_St.p, h->d_x.p, h->d_ok.p, h->d_wfac.p, st, &h->ldlt_attr));
-      } else {
-        ORBG_HIP(launch_ldlt_wide(n, h->d_S.p, h->d_bs.p, h->d_x.p, h->d_ok.p, h->d_wide.p, st));
-      }
+      // (ORBG_LDLT_XCD=short, test hook: the handle's first eight-workgroup launch misses a participant)
+      const bool one_short = h->ldlt.use_xcd && h->ldlt.asked_short;
+      if (one_short) h->ldlt.asked_short = false;
+      if (int rc = h->ldlt.launch(h->d_bs.p, h->d_x.p, h->d_ok.p, st, one_short)) return rc;
       if (bracket) { ORBG_HIP(hipEventRecord(h->prof_ev[1], st)); prof_pending = true; }
     } else {
       ORBG_HIP(hipMemsetAsync(h->d_ok.p, 0xFF, sizeof(int), st));   // nothing to solve: ok
@@ -1668,7 +1635,7 @@ struct LbaRun : LbaStructure {
     const LinSet& L = h->lin[set];
     const int n_err = nP + n_blocks_e + errlin_tail_blocks(nL), nsb = (nL + 255) / 256;
     hipLaunchKernelGGL(k_errlin_prep<CamT>, dim3(n_err + nsb + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, n_err, nsb,
-                       D.pf_edges, D.pf_col, D.pf_start, D.lm_mask, n, use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero,
+                       D.pf_edges, D.pf_col, D.pf_start, D.lm_mask, n, h->ldlt.St(), h->d_x.p, n_zero,
                        nP, NE, d_edges, posesB[buf], pointsB[buf], cam, hb, h->d_err.p, h->d_chi2.p, D.pose_col, D.point_col, L.EB.p,
                        D.ps_start, D.ps_edges, L.Hpp.p, L.bp.p, h->d_partial.p, h->d_ticket.p, h->d_scale_partial.p, 0,
                        (const int*)nullptr, h->rec.d, h->rec_seq, n_blocks_e, nL, D.pt_start, D.pt_edges, L.Hll.p, L.bl.p, LmIn{});
@@ -1932,7 +1899,7 @@ struct LbaRun : LbaStructure {
         (rc = h->d_err.reserve(std::max<size_t>(3 * (size_t)NE, 1))) || (rc = h->d_chi2.reserve(std::max(NE, 1))) ||
         (rc = h->d_partial.reserve(std::max(n_blocks_e, 1))) || (rc = h->lin[0].reserve(NE, nL, nP)) ||
         (rc = h->lin[1].reserve(NE, nL, nP)) || (rc = h->d_lambda0.reserve(4)) ||
-        (rc = h->d_S.reserve(std::max<size_t>((size_t)n * n, 1))) || (rc = h->d_bs.reserve(std::max(n, 1))) ||
+        (rc = h->d_bs.reserve(std::max(n, 1))) ||
         (rc = h->d_x.reserve(std::max<size_t>((size_t)n + 3 * (size_t)nL, 1))))
       return rc;
     posesB[0] = D.poses; posesB[1] = h->d_poses[1].p; posesB[2] = h->d_poses[0].p;
@@ -1942,26 +1909,8 @@ struct LbaRun : LbaStructure {
   // ---- the solver of the reduced camera system, the record's scratch, the results block
   int pick_solver() {
     int rc;
-    // FP64 matrix-core LDL^T (ldlt_mfma.hpp): up to 50 free poses (ORBG_LDLT_WIDE=1: k_wide_* at any size)
-    use_mfma = nP >= 1 && ldltm::supports(n) && !h->sw.ldlt_wide;
-    // windows beyond the matrix-core kernels (more than 50 free poses): blocked LDL^T over many workgroups
-    use_wide = nP >= 1 && !use_mfma;
-    if (use_wide && n > kWideMaxUnknowns) return ORBG_CAP_EXCEEDED;      // (k_wide_back's x lives in LDS)
-    if (use_wide && (rc = h->d_wide.reserve(2 * (size_t)n + 32))) return rc;
-    if (use_mfma) {
-      if ((rc = h->d_St.reserve(ldltm::tile_image_doubles(n))) || (rc = h->d_wfac.reserve(ldltm::wglob_doubles(ldltm::make_geo(n))))) return rc;
-    }
-    // 21 .. 50 free poses: the same tile image, factored by eight workgroups of one XCD (ldlt_xcd.hpp)
-    use_xcd = use_mfma && h->sw.ldlt_xcd != 0 && ldltx::pays(n);
-    if (use_xcd && !h->ldlt_x.scr) {
-      if ((rc = h->d_xscr.reserve(ldltx::scratch_doubles())) || (rc = h->d_xflags.reserve(ldltx::kFlagWords))) return rc;
-      ORBG_HIP(hipMemsetAsync(h->d_xflags.p, 0, ldltx::kFlagWords * sizeof(unsigned), st));
-      // (the G / D^-1 pair region: a fresh nonce per bind already makes stale pairs of a recycled allocation fail their test; zero all the same)
-      ORBG_HIP(hipMemsetAsync(h->d_xscr.p + ldltx::kGbOff, 0, (ldltx::kWOff - ldltx::kGbOff) * sizeof(double), st));
-      h->ldlt_x.bind(h->d_xscr.p, h->d_xflags.p);
-      static std::atomic<int> n_users{0};              // users of one process on different XCDs; processes sharing a GPU differ by pid
-      h->ldlt_x.pick = ((int)getpid() + n_users.fetch_add(1)) & 7;
-    }
+    // FP64 matrix-core LDL^T up to 50 free poses, on eight workgroups of one XCD from 21 on; blocked LDL^T over many workgroups beyond
+    if ((rc = h->ldlt.plan(n, st))) return rc;
     n_blocks_u = (NP + NX + kUpdThreads - 1) / kUpdThreads;
     if ((rc = h->d_scale_partial.reserve(std::max(n_blocks_u, 1)))) return rc;
     if (!h->d_ticket.p) {
@@ -1996,7 +1945,7 @@ struct LbaRun : LbaStructure {
           const int n_blocks_l = (nL + 255) / 256;              // (k_csr_sort: one thread per landmark)
           hipLaunchKernelGGL(k_csr_sort, dim3(nP + n_blocks_l + kPrep256Pad + kPrep256Zero), dim3(256), 0, st, nP, nL, D.ps_start,
                              D.ps_edges, D.pt_start, D.pt_edges, D.pf_start, D.pf_edges, D.pf_col, D.lm_mask, d_edges, D.pose_col, n,
-                             use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
+                             h->ldlt.St(), h->d_x.p, n_zero);
           errlin(lm.cur, set, false, LmIn{});
         } else {
           errlin_prep(lm.cur, set);
@@ -2019,11 +1968,11 @@ struct LbaRun : LbaStructure {
       // ... in one launch with the per-landmark lists (k_prep)
       const int nsb = (nL + kSortPfThreads - 1) / kSortPfThreads;
       hipLaunchKernelGGL(k_prep, dim3(nsb + 32 + 8), dim3(kSortPfThreads), 0, st, nsb, nL, D.pf_start, D.pf_edges, D.pf_col, D.lm_mask,
-                         d_edges, D.pose_col, n, use_mfma ? h->d_St.p : (double*)nullptr, h->d_x.p, n_zero);
+                         d_edges, D.pose_col, n, h->ldlt.St(), h->d_x.p, n_zero);
       ORBG_HIP(hipGetLastError());
     } else {
       ORBG_HIP(hipMemsetAsync(h->d_x.p, 0, (size_t)n_zero * sizeof(double), st));
-      if (use_mfma) ORBG_HIP(ldltm::launch_image_pad(n, h->d_St.p, st));
+      if (h->ldlt.St()) ORBG_HIP(ldltm::launch_image_pad(n, h->ldlt.St(), st));
     }
     return ORBG_OK;
   }
@@ -2342,7 +2291,7 @@ extern "C" int lba_get_solver_stats(lba_handle* h, double* sum_ms, int64_t* n_br
   if (!h || !sum_ms || !n_brackets) return ORBG_BAD_ARG;
   *sum_ms = h->prof_sum_ms; *n_brackets = h->prof_n;
   if (n_unknowns) *n_unknowns = h->prof_n_unknowns;
-  if (matrix_core) *matrix_core = h->prof_n_unknowns >= 1 && ldltm::supports(h->prof_n_unknowns) && !h->sw.ldlt_wide;
+  if (matrix_core) *matrix_core = h->prof_n_unknowns >= 1 && ldltm::supports(h->prof_n_unknowns) && !h->ldlt.wide;
   return ORBG_OK;
 }
 

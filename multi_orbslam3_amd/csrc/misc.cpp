@@ -121,6 +121,8 @@ bool is_library_stream(hipStream_t st) {
   return false;
 }
 
+int next_ldlt_xcd_user() { static std::atomic<int> n_users{0}; return n_users.fetch_add(1); }
+
 }  // namespace orbg
 
 extern "C" int orbg_set_wait_policy(int role, int spin) {

@@ -161,6 +161,41 @@ def test_sizes_on_both_sides_of_each_solver_limit(n_free):
     assert not fails, fails
 
 
+@needs_long_double
+@pytest.mark.parametrize("env", [{}, {"ORBG_LDLT_WIDE": "1"}, {"ORBG_LDLT_XCD": "safe"}, {"ORBG_LDLT_XCD": "0"}],
+                         ids=["default", "wide", "xcd_safe", "xcd_off"])
+def test_the_solver_switches_at_the_first_eight_workgroup_size(env, monkeypatch):
+    """18 free keyframes, the first size on the eight-workgroup LDL^T, under each value of the two switches of csrc/ldlt_solver.hpp:
+    the many-workgroup kernels, the eight-workgroup kernel with its same-L2 and with its agent-scope hand-overs, and the one-workgroup
+    kernel in its place.  The work area belongs to the calling thread and reads the variables on that thread's first call: every
+    variant runs in a thread of its own.  Judged as the scenes' other tests judge them."""
+    fam = yardstick()
+    assert solver_limits()[1] == 18
+    scenes = [s for s in fam["scenes"] if s["problem"].n_free == 18]
+    assert len(scenes) >= 2                                  # both scale modes
+    for key in ("ORBG_LDLT_WIDE", "ORBG_LDLT_XCD"):
+        monkeypatch.delenv(key, raising=False)
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    fails, judged, raised = [], [], []
+
+    def work():
+        try:
+            for s in scenes:
+                fails.extend(judge(s["problem"], s["f64"], s["ld"], fam["band_est"][s["band"]], fam["band_pts"][s["band"]],
+                                   "free 18 fix %d %s" % (s["entry"][1], env))[1])
+                judged.append(s)
+        except BaseException as e:                           # (an exception must not end with the thread)
+            raised.append(e)
+
+    th = threading.Thread(target=work)
+    th.start()
+    th.join()
+    if raised:
+        raise raised[0]
+    assert len(judged) == len(scenes) and not fails, fails
+
+
 # ------------------------------------------------------------------ 4. structure
 
 def _chain(n, rng, fix_scale, noise=0.02):

@@ -83,6 +83,27 @@ def test_equals_the_model(opt, name):
         _assert_equals_model(out, fc.model(name))
 
 
+@pytest.mark.parametrize("env", [{}, {"ORBG_LDLT_WIDE": "1"}, {"ORBG_LDLT_XCD": "safe"}, {"ORBG_LDLT_XCD": "0"}],
+                         ids=["default", "wide", "xcd_safe", "xcd_off"])
+def test_the_solver_switches_at_the_first_eight_workgroup_size(env, monkeypatch):
+    """21 free poses, the smallest system on the eight-workgroup LDL^T, under each value of the two switches that ba_create reads
+    (csrc/ldlt_solver.hpp): the many-workgroup kernels, the eight-workgroup kernel with its same-L2 and with its agent-scope
+    hand-overs, and the one-workgroup kernel in its place -- each judged as test_equals_the_model judges the case."""
+    name = "boundary_21"
+    assert name not in fc.NEW_CASES and fc.BOUNDARY_POSES[1] == 21
+    for key in ("ORBG_LDLT_WIDE", "ORBG_LDLT_XCD"):
+        monkeypatch.delenv(key, raising=False)
+    for key, val in env.items():
+        monkeypatch.setenv(key, val)
+    _, its, robust = fc.CASES[name]
+    h = api.FullBA()                                 # (created with the variables as set above)
+    try:
+        out = h.solve(_view(fc.problem(name), its, robust)[0])
+    finally:
+        h.close()
+    _assert_equals_model(out, fc.model(name))
+
+
 @pytest.mark.parametrize("name", sorted(fc.REPLICATED))
 def test_copies_of_a_component_at_and_below_the_cap(opt, name):
     """BA_MAX_FREE_POSES free poses (8190 unknowns on k_wide_*: 64 KB of LDS in k_wide_back, 43 bitmap words per row, the counting
