@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/orbgpu.h"
+#include "stage_layout.hpp"
 
 #define ORBG_HIP(expr)                                                                          \
   do {                                                                                          \
@@ -82,6 +83,40 @@ struct PinnedBuf {
     return ORBG_OK;
   }
   void release() { if (h) { (void)hipHostFree(h); h = nullptr; d = nullptr; cap = 0; } }
+};
+
+// The staging block of an entry point: per-call arrays packed into ONE pinned block at the slots of a StageLayout, read by the kernel
+// in place (mapped) or from the device block after ONE copy; results come back through slots of the same block.  The one place where
+// a byte offset becomes a T*.
+struct StageBlock {
+  PinnedBuf<uint8_t> pin;
+  DevBuf<uint8_t> dev;
+  StageLayout lay;                       // single-pass form (begin .. commit)
+  size_t dirty_lo = 0, dirty_hi = 0;     // part of the block that commit() copies to the device
+  int reserve(size_t bytes) { int rc = pin.reserve(bytes); return rc ? rc : dev.reserve(bytes); }   // (growth as PinnedBuf / DevBuf)
+  template <typename T> T* host(StageSlot<T> s) const { return reinterpret_cast<T*>(pin.h + s.off); }
+  template <typename T> T* mapped(StageSlot<T> s) const { return reinterpret_cast<T*>(pin.d + s.off); }   // the device's address of host(s)
+  template <typename T> T* device(StageSlot<T> s) const { return reinterpret_cast<T*>(dev.p + s.off); }
+  template <typename T> void put(StageSlot<T> s, const T* src) { if (s.count) memcpy(host(s), src, s.bytes()); }
+  template <typename T> void get(StageSlot<T> s, T* dst) const { if (s.count) memcpy(dst, host(s), s.bytes()); }
+  // bytes [lo, hi) of the block, pinned -> device and back: one copy command each
+  int upload(size_t lo, size_t hi, hipStream_t st) { ORBG_HIP(hipMemcpyAsync(dev.p + lo, pin.h + lo, hi - lo, hipMemcpyHostToDevice, st)); return ORBG_OK; }
+  int download(size_t lo, size_t hi, hipStream_t st) { ORBG_HIP(hipMemcpyAsync(pin.h + lo, dev.p + lo, hi - lo, hipMemcpyDeviceToHost, st)); return ORBG_OK; }
+  void release() { pin.release(); dev.release(); }
+  // Single pass, for a site that lays out while it fills: `bound` >= the bytes the slots will take (StageLayout::bound).
+  int begin(size_t bound) { lay = StageLayout(); dirty_lo = dirty_hi = 0; return reserve(bound); }
+  // the next slot; dev_copy: it is part of what commit() uploads (inputs that many threads re-read), else it is read or written in place
+  template <typename T> StageSlot<T> room(size_t count, bool dev_copy = false) {
+    const StageSlot<T> s = lay.add<T>(count);
+    if (dev_copy && count) { if (dirty_hi == dirty_lo) dirty_lo = s.off; dirty_hi = s.end(); }
+    return s;
+  }
+  template <typename T> const T* add(const T* src, size_t count, bool dev_copy = false) {
+    const StageSlot<T> s = room<T>(count, dev_copy);
+    put(s, src);
+    return dev_copy ? device(s) : mapped(s);
+  }
+  int commit(hipStream_t st) { return dirty_hi > dirty_lo ? upload(dirty_lo, dirty_hi, st) : ORBG_OK; }
 };
 
 // Completion signal without the runtime's wake-up path: a one-thread kernel at the tail of a stream writes a sequence number

@@ -276,8 +276,7 @@ __global__ __launch_bounds__(kThreads) void fuse_kernel(FuseArgs A) {
 // ------------------------------------------------------------------------------------------------ host
 
 struct FuseBufs {
-  orbg::PinnedBuf<uint8_t> stage;
-  orbg::DevBuf<uint8_t> d_stage;
+  orbg::StageBlock stage;
   orbg::DevBuf<orbm_fuse_record> d_rec;
   orbg::DevBuf<uint16_t> d_cand;
   orbg::PinnedBuf<orbm_fuse_record> h_rec;
@@ -286,7 +285,7 @@ struct FuseBufs {
   std::vector<hipStream_t> streams;
   hipEvent_t ev = nullptr;
   void release_buffers() {
-    stage.release(); d_stage.release(); d_rec.release(); d_cand.release(); h_rec.release(); h_cand.release();
+    stage.release(); d_rec.release(); d_cand.release(); h_rec.release(); h_cand.release();
     if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
   }
 };
@@ -362,32 +361,23 @@ extern "C" int orbm_fuse(const orbm_fuse_kf* kfs, int K, const orbm_worldpoints_
   if (!W.ev) ORBG_HIP(hipEventCreateWithFlags(&W.ev, hipEventDisableTiming));
   const size_t nrec = (size_t)K * (size_t)P;
   // one pinned block, one H2D copy: FuseKfDev[K], the points, the skip bytes
-  size_t total = 0;
-  auto room = [&](size_t bytes) { const size_t o = total; total += (bytes + 15) & ~(size_t)15; return o; };
   const bool pskip = pts->bad || pts->skip;
-  const size_t o_kf = room((size_t)K * sizeof(FuseKfDev)), o_pos = room((size_t)P * 12), o_nrm = room((size_t)P * 12), o_min = room((size_t)P * 4),
-               o_max = room((size_t)P * 4), o_desc = room((size_t)P * 32), o_ps = pskip ? room((size_t)P) : 0, o_skip = skip ? room(nrec) : 0;
-  if ((rc = W.stage.reserve(total)) || (rc = W.d_stage.reserve(total)) || (rc = W.d_rec.reserve(nrec)) || (rc = W.d_cand.reserve(nrec * kCap)) ||
-      (rc = W.h_rec.reserve(nrec)) || (rc = W.h_cand.reserve(nrec * kCap)))
+  orbg::StageBlock& S = W.stage;
+  if ((rc = S.begin(orbg::StageLayout::bound(8, (size_t)K * sizeof(FuseKfDev) + (size_t)P * 65 + nrec))) || (rc = W.d_rec.reserve(nrec)) ||
+      (rc = W.d_cand.reserve(nrec * kCap)) || (rc = W.h_rec.reserve(nrec)) || (rc = W.h_cand.reserve(nrec * kCap)))
     return rc;
-  uint8_t* hs = W.stage.h;
-  const uint8_t* ds = W.d_stage.p;
-  memcpy(hs + o_kf, W.kf.data(), (size_t)K * sizeof(FuseKfDev));
-  memcpy(hs + o_pos, pts->pos, (size_t)P * 12);
-  memcpy(hs + o_nrm, pts->normal, (size_t)P * 12);
-  memcpy(hs + o_min, pts->min_dist, (size_t)P * 4);
-  memcpy(hs + o_max, pts->max_dist, (size_t)P * 4);
-  memcpy(hs + o_desc, pts->desc, (size_t)P * 32);
-  if (pskip)
-    for (int i = 0; i < P; i++) hs[o_ps + i] = (uint8_t)((pts->bad && pts->bad[i]) || (pts->skip && pts->skip[i]));
-  if (skip) memcpy(hs + o_skip, skip, nrec);
   FuseArgs A;
-  A.kf = (const FuseKfDev*)(ds + o_kf);
-  A.pos = (const float*)(ds + o_pos); A.normal = (const float*)(ds + o_nrm);
-  A.min_dist = (const float*)(ds + o_min); A.max_dist = (const float*)(ds + o_max);
-  A.desc = ds + o_desc;
-  A.pskip = pskip ? ds + o_ps : nullptr;
-  A.skip = skip ? ds + o_skip : nullptr;
+  A.kf = S.add(W.kf.data(), K, true);
+  A.pos = S.add(pts->pos, 3 * (size_t)P, true); A.normal = S.add(pts->normal, 3 * (size_t)P, true);
+  A.min_dist = S.add(pts->min_dist, P, true); A.max_dist = S.add(pts->max_dist, P, true);
+  A.desc = S.add(pts->desc, 32 * (size_t)P, true);
+  A.pskip = nullptr;
+  if (pskip) {
+    const auto s_ps = S.room<uint8_t>(P, true);
+    for (int i = 0; i < P; i++) S.host(s_ps)[i] = (uint8_t)((pts->bad && pts->bad[i]) || (pts->skip && pts->skip[i]));
+    A.pskip = S.device(s_ps);
+  }
+  A.skip = skip ? S.add(skip, nrec, true) : nullptr;
   A.rec = W.d_rec.p; A.cand = W.d_cand.p;
   A.P = P; A.th = params->th;
   // the calling thread's stream; what is pending on the keyframes' streams (an upload, a constructor) is ordered in front
@@ -398,7 +388,7 @@ extern "C" int orbm_fuse(const orbm_fuse_kf* kfs, int K, const orbm_worldpoints_
     ORBG_HIP(hipEventRecord(W.ev, fs));
     ORBG_HIP(hipStreamWaitEvent(st, W.ev, 0));
   }
-  ORBG_HIP(hipMemcpyAsync(W.d_stage.p, hs, total, hipMemcpyHostToDevice, st));
+  if ((rc = S.commit(st))) return rc;
   const dim3 grid((P + kThreads - 1) / kThreads, K);
   if (sim3) hipLaunchKernelGGL(fuse_kernel<true>, grid, dim3(kThreads), 0, st, A);
   else hipLaunchKernelGGL(fuse_kernel<false>, grid, dim3(kThreads), 0, st, A);

@@ -1057,14 +1057,11 @@ struct orbm_frame {
   PinnedBuf<uint8_t> h_vis;
   const orbx_keypoint* hk = nullptr;     // host mirror (octave / angle for the serial commit)
   // per-call inputs are packed into ONE pinned staging block and moved with ONE H2D copy
-  PinnedBuf<uint8_t> stage;
-  DevBuf<uint8_t> d_stage;
-  size_t stage_off = 0;
+  orbg::StageBlock stage;
   const int* d_assigned_mp = nullptr;
   const int* d_assigned_obs = nullptr;
   bool occ_mask = false;                 // occupancy travels in the kernel arguments (frames of <= kOccBits features)
   uint32_t occ[kOccBits / 32];
-  size_t copy_lo = 0, copy_hi = 0;       // part of the staging block that needs a device copy
   unsigned search_seq = 0;               // selects the overflow counter; the kernel clears the other one
   StreamSignal sig;                      // completion word in pinned memory (host spins instead of hipStreamSynchronize)
   // query-side scratch
@@ -1145,7 +1142,7 @@ extern "C" int orbm_frame_destroy(orbm_frame* f) {
   (void)hipStreamSynchronize(f->stream);
   if (f->own_stream != f->stream) (void)hipStreamSynchronize(f->own_stream);
   f->d_kps.release(); f->d_desc.release(); f->d_uright.release(); f->d_depth.release(); f->d_cell_of.release();
-  f->d_cell_start.release(); f->d_cell_items.release(); f->stage.release(); f->d_stage.release();
+  f->d_cell_start.release(); f->d_cell_items.release(); f->stage.release();
   f->d_counter.release(); f->list.release(); f->results.release(); f->sig.release(); f->h_kps_pin.release(); f->d_qflag.release(); f->d_blk_cnt.release(); f->d_slot_pt.release(); f->d_total.release(); f->h_slot_pt.release(); f->h_vis.release();
   if (f->side_cache && f->side_free) f->side_free(f->side_cache);
   for (auto& e : f->ev) if (e) (void)hipEventDestroy(e);
@@ -1320,8 +1317,8 @@ extern "C" int orbk_pack_frame(orbm_frame* f, uint8_t* wire, int wire_on_device)
   const size_t bytes = (size_t)n * (kWireKp + kWireDesc);
   uint8_t* d_wire = wire;
   if (!wire_on_device) {
-    if ((rc = f->d_stage.reserve(bytes))) return rc;
-    d_wire = f->d_stage.p;
+    if ((rc = f->stage.dev.reserve(bytes))) return rc;
+    d_wire = f->stage.dev.p;
   }
   hipLaunchKernelGGL(wire_pack_kernel, dim3((n + 255) / 256), dim3(256), 0, f->stream, f->kps_p, f->desc_p, n, d_wire);
   ORBG_HIP(hipGetLastError());
@@ -1350,9 +1347,9 @@ extern "C" int orbk_frame_from_wire(orbm_frame* f, const orbm_frame_view* v, con
     const size_t bytes = (size_t)n * (kWireKp + kWireDesc);
     const uint8_t* d_wire = wire;
     if (!wire_on_device) {
-      if ((rc = f->d_stage.reserve(bytes))) return rc;
-      ORBG_HIP(hipMemcpyAsync(f->d_stage.p, wire, bytes, hipMemcpyHostToDevice, f->stream));
-      d_wire = f->d_stage.p;
+      if ((rc = f->stage.dev.reserve(bytes))) return rc;
+      ORBG_HIP(hipMemcpyAsync(f->stage.dev.p, wire, bytes, hipMemcpyHostToDevice, f->stream));
+      d_wire = f->stage.dev.p;
     }
     hipLaunchKernelGGL(wire_unpack_kernel, dim3((n + 255) / 256), dim3(256), 0, f->stream, d_wire, n, f->d_kps.p, f->d_desc.p,
                        f->h_kps_pin.d);
@@ -1552,8 +1549,8 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   for (int i = 0; i < nq; i++) { const int o = v->kps_left[v->mono_left + i].octave; if (o < 0 || o >= v->n_levels) return ORBG_BAD_ARG; }
   for (int i = 0; i < nt; i++) { const int o = v->kps_right[v->mono_right + i].octave; if (o < 0 || o >= v->n_levels) return ORBG_BAD_ARG; }
   struct Bufs {
-    PinnedBuf<uint8_t> in, out; DevBuf<uint8_t> din; StreamSignal sig;
-    void release_buffers() { in.release(); out.release(); din.release(); sig.release(); }
+    orbg::StageBlock blk; StreamSignal sig;
+    void release_buffers() { blk.release(); sig.release(); }
   };
   static thread_local orbg::WorkArea<Bufs> S;
   int rc = S.open(device, "misc");                      // the library's M stream (kept: a stream object per call costs a synchronisation)
@@ -1562,31 +1559,29 @@ extern "C" int orbx_fisheye_stereo_matches(int device, const orbx_fisheye_stereo
   for (int i = 0; i < v->n_right; i++) right_to_left[i] = -1;
   if (n_matches) *n_matches = 0;
   if (nq == 0 || nt < 2) return ORBG_OK;
-  // one pinned block in (one copy to the device), results straight into mapped pinned memory (buffers of the calling thread, kept from
-  // frame to frame); mvRightToLeftMatch and nMatches follow from mvLeftToRightMatch on the host (:1144-1145: the last left feature stays)
-  auto up = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  const size_t o_kl = 0, o_kr = up(o_kl + (size_t)nq * sizeof(orbx_keypoint)), o_dl = up(o_kr + (size_t)nt * sizeof(orbx_keypoint)), o_dr = up(o_dl + (size_t)nq * 32),
-               o_sg = up(o_dr + (size_t)nt * 32), in_bytes = up(o_sg + (size_t)v->n_levels * 4);
-  const size_t p_l2r = 0, p_dep = up(p_l2r + (size_t)nq * 4), p_p3d = up(p_dep + (size_t)nq * 4), out_bytes = up(p_p3d + (size_t)nq * 12);
-  if ((rc = S.in.reserve(in_bytes)) || (rc = S.out.reserve(out_bytes)) || (rc = S.din.reserve(in_bytes))) return rc;
-  memcpy(S.in.h + o_kl, v->kps_left + v->mono_left, (size_t)nq * sizeof(orbx_keypoint));
-  memcpy(S.in.h + o_kr, v->kps_right + v->mono_right, (size_t)nt * sizeof(orbx_keypoint));
-  memcpy(S.in.h + o_dl, v->desc_left + (size_t)v->mono_left * 32, (size_t)nq * 32);
-  memcpy(S.in.h + o_dr, v->desc_right + (size_t)v->mono_right * 32, (size_t)nt * 32);
-  memcpy(S.in.h + o_sg, v->level_sigma2, (size_t)v->n_levels * 4);
-  ORBG_HIP(hipMemcpyAsync(S.din.p, S.in.h, in_bytes, hipMemcpyHostToDevice, S.stream));
+  // one staging block (buffers of the calling thread, kept from frame to frame): the inputs go to the device in one copy, the results
+  // come straight into its mapped slots; mvRightToLeftMatch and nMatches follow from mvLeftToRightMatch on the host (:1144-1145: the
+  // last left feature stays)
+  orbg::StageBlock& blk = S.blk;
+  const size_t payload = (size_t)(nq + nt) * (sizeof(orbx_keypoint) + 32) + (size_t)v->n_levels * 4 + (size_t)nq * 20;
+  if ((rc = blk.begin(orbg::StageLayout::bound(8, payload)))) return rc;
   FisheyeDev D;
   D.nq = nq; D.nt = nt; D.mono_left = v->mono_left; D.mono_right = v->mono_right;
-  D.kl = reinterpret_cast<const orbx_keypoint*>(S.din.p + o_kl); D.kr = reinterpret_cast<const orbx_keypoint*>(S.din.p + o_kr);
-  D.dl = S.din.p + o_dl; D.dr = S.din.p + o_dr; D.sigma2 = reinterpret_cast<const float*>(S.din.p + o_sg);
+  D.kl = blk.add(v->kps_left + v->mono_left, nq, true); D.kr = blk.add(v->kps_right + v->mono_right, nt, true);
+  D.dl = blk.add(v->desc_left + (size_t)v->mono_left * 32, (size_t)nq * 32, true);
+  D.dr = blk.add(v->desc_right + (size_t)v->mono_right * 32, (size_t)nt * 32, true);
+  D.sigma2 = blk.add(v->level_sigma2, v->n_levels, true);
+  if ((rc = blk.commit(S.stream))) return rc;
   D.cam1 = rig_cam_of(v->left); D.cam2 = rig_cam_of(v->right);
   memcpy(D.Tlr, v->Tlr, sizeof(D.Tlr));
-  D.l2r = reinterpret_cast<int*>(S.out.d + p_l2r); D.depth = reinterpret_cast<float*>(S.out.d + p_dep); D.p3d = reinterpret_cast<float*>(S.out.d + p_p3d);
+  const auto s_l2r = blk.room<int>(nq);
+  const auto s_dep = blk.room<float>(nq), s_p3d = blk.room<float>(3 * (size_t)nq);
+  D.l2r = blk.mapped(s_l2r); D.depth = blk.mapped(s_dep); D.p3d = blk.mapped(s_p3d);
   hipLaunchKernelGGL(fisheye_stereo_kernel, dim3((nq + 3) / 4), dim3(256), 0, S.stream, D);
   ORBG_HIP(hipGetLastError());
   if ((rc = S.sig.sync(S.stream))) return rc;
-  const int* h_l2r = reinterpret_cast<const int*>(S.out.h + p_l2r); const float* h_dep = reinterpret_cast<const float*>(S.out.h + p_dep);
-  const float* h_p3d = reinterpret_cast<const float*>(S.out.h + p_p3d);
+  const int* h_l2r = blk.host(s_l2r); const float* h_dep = blk.host(s_dep);
+  const float* h_p3d = blk.host(s_p3d);
   int nm = 0;
   for (int q = 0; q < nq; q++) {
     left_to_right[v->mono_left + q] = h_l2r[q]; depth[v->mono_left + q] = h_dep[q];
@@ -1609,12 +1604,14 @@ extern "C" int orbm_hamming_best2(int device, const uint8_t* q, int nq, const ui
 struct orbm_map {
   int device = 0;
   int m = 0;
-  // point fields: ONE device block filled by ONE copy from a pinned staging block (offsets below, all 16-byte aligned)
-  DevBuf<uint8_t> arena;
-  PinnedBuf<uint8_t> stage;
+  // point fields: ONE device block filled by ONE copy from its pinned staging block (slots below, laid out by map_reserve for the
+  // points of the last upload; the blocks themselves only grow)
+  orbg::StageBlock blk;
   hipStream_t stream = nullptr;
   bool ext_stream = false;
-  size_t o_pos = 0, o_normal = 0, o_min = 0, o_max = 0, o_desc = 0, o_bad = 0, o_skip = 0, arena_bytes = 0;
+  orbg::StageSlot<float> s_pos, s_normal, s_min, s_max;
+  orbg::StageSlot<uint8_t> s_desc, s_bad, s_skip;
+  size_t arena_bytes = 0;
   std::vector<int> n_obs;
   std::vector<uint8_t> h_bad;
   // device track fields
@@ -1639,10 +1636,11 @@ static int map_sync_to(orbm_map* m, hipStream_t st) {
 static int map_reserve(orbm_map* m, int n) {
   const size_t c = (size_t)std::max(n, 1);
   int rc;
-  const size_t c16 = (c + 15) & ~(size_t)15;
-  m->o_pos = 0; m->o_normal = m->o_pos + 12 * c16; m->o_min = m->o_normal + 12 * c16; m->o_max = m->o_min + 4 * c16;
-  m->o_desc = m->o_max + 4 * c16; m->o_bad = m->o_desc + 32 * c16; m->o_skip = m->o_bad + c16; m->arena_bytes = m->o_skip + c16;
-  if ((rc = m->arena.reserve(m->arena_bytes)) || (rc = m->stage.reserve(m->arena_bytes)) || (rc = m->t_in_view.reserve(c)) ||
+  orbg::StageLayout lay;
+  m->s_pos = lay.add<float>(3 * c); m->s_normal = lay.add<float>(3 * c); m->s_min = lay.add<float>(c); m->s_max = lay.add<float>(c);
+  m->s_desc = lay.add<uint8_t>(32 * c); m->s_bad = lay.add<uint8_t>(c); m->s_skip = lay.add<uint8_t>(c);
+  m->arena_bytes = lay.bytes();
+  if ((rc = m->blk.reserve(m->arena_bytes)) || (rc = m->t_in_view.reserve(c)) ||
       (rc = m->t_px.reserve(c)) || (rc = m->t_py.reserve(c)) || (rc = m->t_pxr.reserve(c)) || (rc = m->t_depth.reserve(c)) ||
       (rc = m->t_vc.reserve(c)) || (rc = m->t_level.reserve(c)))
     return rc;
@@ -1673,7 +1671,7 @@ extern "C" int orbm_map_destroy(orbm_map* m) {
   if (!m) return ORBG_BAD_ARG;
   (void)hipSetDevice(m->device);
   (void)hipDeviceSynchronize();
-  m->arena.release(); m->stage.release();
+  m->blk.release();
   if (m->up_ev) (void)hipEventDestroy(m->up_ev);
   if (!m->ext_stream) orbg::release_stream(m->stream);
   m->t_in_view.release(); m->t_px.release(); m->t_py.release(); m->t_pxr.release(); m->t_depth.release();
@@ -1702,14 +1700,13 @@ extern "C" int orbm_map_upload(orbm_map* m, const orbm_worldpoints_view* p) {
   m->n_obs.assign(p->n_obs, p->n_obs + n);
   m->h_bad.assign(p->bad, p->bad + n);
   if (n > 0) {
-    uint8_t* S = m->stage.h;
-    memcpy(S + m->o_pos, p->pos, n * 12); memcpy(S + m->o_normal, p->normal, n * 12);
-    memcpy(S + m->o_min, p->min_dist, n * 4); memcpy(S + m->o_max, p->max_dist, n * 4);
-    memcpy(S + m->o_desc, p->desc, n * 32); memcpy(S + m->o_bad, p->bad, n);
-    if (p->skip) memcpy(S + m->o_skip, p->skip, n); else memset(S + m->o_skip, 0, n);
-    const int n16 = (int)((m->arena_bytes + 15) / 16);
-    hipLaunchKernelGGL(lastview_copy_kernel, dim3((n16 + 255) / 256), dim3(256), 0, m->stream, reinterpret_cast<const uint4*>(m->stage.d),
-                       reinterpret_cast<uint4*>(m->arena.p), n16);
+    orbg::StageBlock& S = m->blk;             // (map_reserve laid the slots out for these n points)
+    S.put(m->s_pos, p->pos); S.put(m->s_normal, p->normal); S.put(m->s_min, p->min_dist); S.put(m->s_max, p->max_dist);
+    S.put(m->s_desc, p->desc); S.put(m->s_bad, p->bad);
+    if (p->skip) S.put(m->s_skip, p->skip); else memset(S.host(m->s_skip), 0, n);
+    const int n16 = (int)(m->arena_bytes / 16);
+    hipLaunchKernelGGL(lastview_copy_kernel, dim3((n16 + 255) / 256), dim3(256), 0, m->stream, reinterpret_cast<const uint4*>(S.pin.d),
+                       reinterpret_cast<uint4*>(S.dev.p), n16);
     ORBG_HIP(hipGetLastError());
     ORBG_HIP(hipEventRecord(m->up_ev, m->stream));
     m->up_pending = true;
@@ -1728,10 +1725,9 @@ extern "C" int orbm_map_set_observations(orbm_map* m, const int32_t* n_obs) {
 
 static WorldPtsDev map_dev(const orbm_map* m) {
   WorldPtsDev w;
-  const uint8_t* A = m->arena.p;
-  w.m = m->m; w.pos = reinterpret_cast<const float*>(A + m->o_pos); w.normal = reinterpret_cast<const float*>(A + m->o_normal);
-  w.min_dist = reinterpret_cast<const float*>(A + m->o_min); w.max_dist = reinterpret_cast<const float*>(A + m->o_max);
-  w.desc = A + m->o_desc; w.bad = A + m->o_bad; w.skip = A + m->o_skip;
+  const orbg::StageBlock& A = m->blk;
+  w.m = m->m; w.pos = A.device(m->s_pos); w.normal = A.device(m->s_normal); w.min_dist = A.device(m->s_min); w.max_dist = A.device(m->s_max);
+  w.desc = A.device(m->s_desc); w.bad = A.device(m->s_bad); w.skip = A.device(m->s_skip);
   return w;
 }
 static TrackDev map_track(const orbm_map* m) {
@@ -1783,34 +1779,11 @@ static void cache_keypoint_fields(orbm_frame* f) {
   f->hk_cached_from = f->hk; f->hk_cached_n = n;
 }
 
-static int stage_begin(orbm_frame* f, size_t total_bytes) {
-  int rc;
-  const size_t need = total_bytes + 64 * 16;
-  if ((rc = f->stage.reserve(need)) || (rc = f->d_stage.reserve(need))) return rc;
-  f->stage_off = 0;
-  f->copy_lo = f->copy_hi = 0;
-  return ORBG_OK;
-}
-// Packs a per-call input into the pinned staging block.  Inputs every query reads ONCE (descriptors, projections, flags)
-// are read by the kernel straight from that block (it is mapped into the device address space): no copy command at all.
-// Inputs that are re-read by many queries ask for a device copy (dev_copy): one H2D over their contiguous range.
-template <typename T>
-static const T* stage_add(orbm_frame* f, const T* src, size_t count, bool dev_copy = false) {
-  f->stage_off = (f->stage_off + 15) & ~(size_t)15;
-  if (count) memcpy(f->stage.h + f->stage_off, src, count * sizeof(T));
-  const T* dev = reinterpret_cast<const T*>((dev_copy ? f->d_stage.p : f->stage.d) + f->stage_off);
-  if (dev_copy && count) {
-    if (f->copy_hi == f->copy_lo) f->copy_lo = f->stage_off;
-    f->copy_hi = f->stage_off + count * sizeof(T);
-  }
-  f->stage_off += count * sizeof(T);
-  return dev;
-}
-static int stage_commit(orbm_frame* f) {
-  if (f->copy_hi > f->copy_lo)
-    ORBG_HIP(hipMemcpyAsync(f->d_stage.p + f->copy_lo, f->stage.h + f->copy_lo, f->copy_hi - f->copy_lo, hipMemcpyHostToDevice, f->stream));
-  return ORBG_OK;
-}
+// The frame's staging block in its single-pass form (common.hpp, StageBlock): inputs every query reads ONCE (descriptors, projections,
+// flags) are read by the kernel straight from the mapped block, no copy command at all; inputs that many queries re-read ask for a
+// device copy (add(.., true)), and commit() makes one H2D over their contiguous range.  `payload`: the bytes of the call's arrays.
+static int stage_begin(orbm_frame* f, size_t payload) { return f->stage.begin(orbg::StageLayout::bound(64, payload)); }
+
 static int frustum_zero_copy(orbm_frame* f, const float* Tcw, const orbm_worldpoints_view* pts, float limit, uint8_t* track_in_view,
                              float* proj_x, float* proj_y, float* proj_xr, float* track_depth, int32_t* scale_level, float* view_cos) {
   const size_t n = (size_t)pts->m;
@@ -1818,26 +1791,25 @@ static int frustum_zero_copy(orbm_frame* f, const float* Tcw, const orbm_worldpo
   if ((rc = stage_begin(f, n * (32 + 25) + 16 * 16))) return rc;
   WorldPtsDev w;
   w.m = pts->m;
-  w.pos = stage_add(f, pts->pos, 3 * n); w.normal = stage_add(f, pts->normal, 3 * n);
-  w.min_dist = stage_add(f, pts->min_dist, n); w.max_dist = stage_add(f, pts->max_dist, n);
+  w.pos = f->stage.add(pts->pos, 3 * n); w.normal = f->stage.add(pts->normal, 3 * n);
+  w.min_dist = f->stage.add(pts->min_dist, n); w.max_dist = f->stage.add(pts->max_dist, n);
   w.desc = nullptr; w.bad = nullptr; w.skip = nullptr;
-  // outputs: regions of the same block
-  auto out_region = [&](size_t bytes) { f->stage_off = (f->stage_off + 15) & ~(size_t)15; const size_t o = f->stage_off; f->stage_off += bytes; return o; };
-  const size_t o_iv = out_region(n), o_px = out_region(4 * n), o_py = out_region(4 * n), o_pxr = out_region(4 * n), o_dep = out_region(4 * n),
-               o_lvl = out_region(4 * n), o_vc = out_region(4 * n);
-  uint8_t* D = f->stage.d;
+  // outputs: slots of the same block
+  orbg::StageBlock& S = f->stage;
+  const auto o_iv = S.room<uint8_t>(n);
+  const auto o_px = S.room<float>(n), o_py = S.room<float>(n), o_pxr = S.room<float>(n), o_dep = S.room<float>(n);
+  const auto o_lvl = S.room<int>(n);
+  const auto o_vc = S.room<float>(n);
   TrackDev t;
-  t.in_view = D + o_iv; t.px = reinterpret_cast<float*>(D + o_px); t.py = reinterpret_cast<float*>(D + o_py);
-  t.pxr = reinterpret_cast<float*>(D + o_pxr); t.depth = reinterpret_cast<float*>(D + o_dep); t.level = reinterpret_cast<int*>(D + o_lvl);
-  t.view_cos = reinterpret_cast<float*>(D + o_vc);
+  t.in_view = S.mapped(o_iv); t.px = S.mapped(o_px); t.py = S.mapped(o_py); t.pxr = S.mapped(o_pxr); t.depth = S.mapped(o_dep);
+  t.level = S.mapped(o_lvl); t.view_cos = S.mapped(o_vc);
   PoseF P;
   make_pose(Tcw, &P);
   hipLaunchKernelGGL(frustum_kernel, dim3((pts->m + 255) / 256), dim3(256), 0, f->stream, f->fp, P, w, limit, t);
   ORBG_HIP(hipGetLastError());
   if ((rc = f->sig.sync(f->stream))) return rc;
-  const uint8_t* Hh = f->stage.h;
-  memcpy(track_in_view, Hh + o_iv, n); memcpy(proj_x, Hh + o_px, 4 * n); memcpy(proj_y, Hh + o_py, 4 * n); memcpy(proj_xr, Hh + o_pxr, 4 * n);
-  memcpy(track_depth, Hh + o_dep, 4 * n); memcpy(scale_level, Hh + o_lvl, 4 * n); memcpy(view_cos, Hh + o_vc, 4 * n);
+  S.get(o_iv, track_in_view); S.get(o_px, proj_x); S.get(o_py, proj_y); S.get(o_pxr, proj_xr); S.get(o_dep, track_depth);
+  S.get(o_lvl, scale_level); S.get(o_vc, view_cos);
   return ORBG_OK;
 }
 
@@ -1850,8 +1822,8 @@ static void stage_occupancy(orbm_frame* f, const int32_t* amp, const int32_t* ao
       if (amp[i] >= 0 && (!aob || aob[i] > 0)) f->occ[i >> 5] |= 1u << (i & 31);
     f->d_assigned_mp = nullptr; f->d_assigned_obs = nullptr;
   } else {
-    f->d_assigned_mp = stage_add(f, amp, n, true);
-    f->d_assigned_obs = aob ? stage_add(f, aob, n, true) : nullptr;
+    f->d_assigned_mp = f->stage.add(amp, n, true);
+    f->d_assigned_obs = aob ? f->stage.add(aob, n, true) : nullptr;
   }
 }
 
@@ -2003,12 +1975,12 @@ extern "C" int orbm_search_by_projection_mps(orbm_frame* f, const orbm_mappoints
   stage_occupancy(f, assigned_mp, assigned_obs, n);
   MpsDev mp;
   mp.m = m;
-  mp.in_view = stage_add(f, mps->track_in_view, m); mp.bad = stage_add(f, mps->bad, m);
-  mp.desc = stage_add(f, mps->desc, (size_t)m * 32);
-  mp.px = stage_add(f, mps->proj_x, m); mp.py = stage_add(f, mps->proj_y, m); mp.pxr = stage_add(f, mps->proj_xr, m);
-  mp.depth = stage_add(f, mps->track_depth, m); mp.view_cos = stage_add(f, mps->view_cos, m);
-  mp.level = stage_add(f, mps->scale_level, m);
-  if ((rc = stage_commit(f))) return rc;
+  mp.in_view = f->stage.add(mps->track_in_view, m); mp.bad = f->stage.add(mps->bad, m);
+  mp.desc = f->stage.add(mps->desc, (size_t)m * 32);
+  mp.px = f->stage.add(mps->proj_x, m); mp.py = f->stage.add(mps->proj_y, m); mp.pxr = f->stage.add(mps->proj_xr, m);
+  mp.depth = f->stage.add(mps->track_depth, m); mp.view_cos = f->stage.add(mps->view_cos, m);
+  mp.level = f->stage.add(mps->scale_level, m);
+  if ((rc = f->stage.commit(f->stream))) return rc;
   rc = run_search(f, m, [&](int list_cap, int* cnt, int* cnt_next) {
     hipLaunchKernelGGL(search_mps_kernel, dim3((m + 3) / 4), dim3(256), 0, st, f->fp, frame_dev(f), mp, th, far_points,
                        th_far_points, cnt, cnt_next, f->list.d, list_cap, f->results.d);
@@ -2038,8 +2010,8 @@ extern "C" int orbm_search_local_points_vis(orbm_frame* f, orbm_map* mp, const f
   stage_occupancy(f, assigned_mp, assigned_obs, n);
   PoseF P;
   make_pose(Tcw, &P);
-  const uint8_t* d_skip_call = skip ? stage_add(f, skip, m) : nullptr;
-  if ((rc = stage_commit(f))) return rc;
+  const uint8_t* d_skip_call = skip ? f->stage.add(skip, m) : nullptr;
+  if ((rc = f->stage.commit(f->stream))) return rc;
   if ((rc = map_sync_to(mp, st))) return rc;       // the map's last upload may still be in flight on its own stream
   const WorldPtsDev w = map_dev(mp);
   // large maps: frustum test one thread per point, compaction, window search only for the points that become queries
@@ -2116,19 +2088,17 @@ extern "C" int orbm_is_in_frustum_rig(orbm_frame* f, const float* Tcw, const orb
   if ((rc = stage_begin(f, n * (32 + 2 * 21) + 16 * 24))) return rc;
   WorldPtsDev w;
   w.m = pts->m;
-  w.pos = stage_add(f, pts->pos, 3 * n); w.normal = stage_add(f, pts->normal, 3 * n);
-  w.min_dist = stage_add(f, pts->min_dist, n); w.max_dist = stage_add(f, pts->max_dist, n);
+  w.pos = f->stage.add(pts->pos, 3 * n); w.normal = f->stage.add(pts->normal, 3 * n);
+  w.min_dist = f->stage.add(pts->min_dist, n); w.max_dist = f->stage.add(pts->max_dist, n);
   w.desc = nullptr; w.bad = nullptr; w.skip = nullptr;
-  auto out_region = [&](size_t bytes) { f->stage_off = (f->stage_off + 15) & ~(size_t)15; const size_t o = f->stage_off; f->stage_off += bytes; return o; };
-  size_t off[2][6];
+  orbg::StageBlock& S = f->stage;
+  struct { orbg::StageSlot<uint8_t> iv; orbg::StageSlot<float> px, py, dep, vc; orbg::StageSlot<int> lvl; } o[2];
   TrackDev t[2];
-  uint8_t* D = f->stage.d;
   for (int sd = 0; sd < 2; sd++) {
-    off[sd][0] = out_region(n);
-    for (int k = 1; k < 6; k++) off[sd][k] = out_region(4 * n);
-    t[sd].in_view = D + off[sd][0]; t[sd].px = reinterpret_cast<float*>(D + off[sd][1]); t[sd].py = reinterpret_cast<float*>(D + off[sd][2]);
-    t[sd].depth = reinterpret_cast<float*>(D + off[sd][3]); t[sd].level = reinterpret_cast<int*>(D + off[sd][4]);
-    t[sd].view_cos = reinterpret_cast<float*>(D + off[sd][5]); t[sd].pxr = nullptr;
+    o[sd].iv = S.room<uint8_t>(n); o[sd].px = S.room<float>(n); o[sd].py = S.room<float>(n); o[sd].dep = S.room<float>(n);
+    o[sd].lvl = S.room<int>(n); o[sd].vc = S.room<float>(n);
+    t[sd].in_view = S.mapped(o[sd].iv); t[sd].px = S.mapped(o[sd].px); t[sd].py = S.mapped(o[sd].py); t[sd].depth = S.mapped(o[sd].dep);
+    t[sd].level = S.mapped(o[sd].lvl); t[sd].view_cos = S.mapped(o[sd].vc); t[sd].pxr = nullptr;
   }
   PoseF P;
   make_pose(Tcw, &P);
@@ -2136,11 +2106,12 @@ extern "C" int orbm_is_in_frustum_rig(orbm_frame* f, const float* Tcw, const orb
                      rig_side_of(P, rig, Tlr, two), two ? 1 : 0, w, limit, t[0], t[1]);
   ORBG_HIP(hipGetLastError());
   if ((rc = f->sig.sync(f->stream))) return rc;
-  const uint8_t* Hh = f->stage.h;
-  void* outs[2][6] = {{in_view, proj_x, proj_y, track_depth, scale_level, view_cos},
-                      {in_view_r, proj_x_r, proj_y_r, track_depth_r, scale_level_r, view_cos_r}};
-  for (int sd = 0; sd < (two ? 2 : 1); sd++)
-    for (int k = 0; k < 6; k++) memcpy(outs[sd][k], Hh + off[sd][k], k == 0 ? n : 4 * n);
+  S.get(o[0].iv, in_view); S.get(o[0].px, proj_x); S.get(o[0].py, proj_y); S.get(o[0].dep, track_depth); S.get(o[0].lvl, scale_level);
+  S.get(o[0].vc, view_cos);
+  if (two) {
+    S.get(o[1].iv, in_view_r); S.get(o[1].px, proj_x_r); S.get(o[1].py, proj_y_r); S.get(o[1].dep, track_depth_r);
+    S.get(o[1].lvl, scale_level_r); S.get(o[1].vc, view_cos_r);
+  }
   return ORBG_OK;
 }
 
@@ -2158,12 +2129,12 @@ static int stage_mps_rig_side(orbm_frame* f, const orbm_mappoints_view* pt, cons
   stage_occupancy(f, amp, aob, n);
   MpsDev& mp = out->mp;
   mp.m = m;
-  mp.in_view = stage_add(f, in_view, m); mp.bad = stage_add(f, pt->bad, m);
-  mp.desc = stage_add(f, pt->desc, (size_t)m * 32);
-  mp.px = stage_add(f, px, m); mp.py = stage_add(f, py, m); mp.pxr = mp.px;   // (not read: the frame has no uRight)
-  mp.depth = stage_add(f, pt->track_depth, m); mp.view_cos = stage_add(f, view_cos, m);
-  mp.level = stage_add(f, level, m);
-  if ((rc = stage_commit(f))) return rc;
+  mp.in_view = f->stage.add(in_view, m); mp.bad = f->stage.add(pt->bad, m);
+  mp.desc = f->stage.add(pt->desc, (size_t)m * 32);
+  mp.px = f->stage.add(px, m); mp.py = f->stage.add(py, m); mp.pxr = mp.px;   // (not read: the frame has no uRight)
+  mp.depth = f->stage.add(pt->track_depth, m); mp.view_cos = f->stage.add(view_cos, m);
+  mp.level = f->stage.add(level, m);
+  if ((rc = f->stage.commit(f->stream))) return rc;
   out->F = frame_dev(f);
   out->F.uright = nullptr;                                // S/ORBmatcher.cc:93: the mvuRight test is for Nleft == -1 only
   return ORBG_OK;
@@ -2288,11 +2259,11 @@ extern "C" int orbm_search_by_projection_frame_rig(orbm_frame* FL, orbm_frame* F
     stage_occupancy(f, none.data(), nullptr, n);
     LastDev& L = Ls[side];
     L.n = m;
-    L.mp_valid = stage_add(f, last->mp_valid, m); L.outlier = stage_add(f, last->outlier, m);
-    L.desc = stage_add(f, last->desc, (size_t)m * 32);
-    L.world_pos = stage_add(f, last->world_pos, (size_t)m * 3);
-    L.octave = stage_add(f, last->octave, m);
-    if ((rc = stage_commit(f))) return rc;
+    L.mp_valid = f->stage.add(last->mp_valid, m); L.outlier = f->stage.add(last->outlier, m);
+    L.desc = f->stage.add(last->desc, (size_t)m * 32);
+    L.world_pos = f->stage.add(last->world_pos, (size_t)m * 3);
+    L.octave = f->stage.add(last->octave, m);
+    if ((rc = f->stage.commit(f->stream))) return rc;
     Fs[side] = frame_dev(f);
     Fs[side].uright = nullptr;                             // :2049: the mvuRight test is for Nleft == -1 only
   }
@@ -2401,11 +2372,11 @@ extern "C" int orbm_search_by_projection_frame(orbm_frame* f, const float* Tcw_c
   stage_occupancy(f, assigned_mp, assigned_obs, n);
   LastDev L;
   L.n = m;
-  L.mp_valid = stage_add(f, last->mp_valid, m); L.outlier = stage_add(f, last->outlier, m);
-  L.desc = stage_add(f, last->desc, (size_t)m * 32);
-  L.world_pos = stage_add(f, last->world_pos, (size_t)m * 3);
-  L.octave = stage_add(f, last->octave, m);
-  if ((rc = stage_commit(f))) return rc;
+  L.mp_valid = f->stage.add(last->mp_valid, m); L.outlier = f->stage.add(last->outlier, m);
+  L.desc = f->stage.add(last->desc, (size_t)m * 32);
+  L.world_pos = f->stage.add(last->world_pos, (size_t)m * 3);
+  L.octave = f->stage.add(last->octave, m);
+  if ((rc = f->stage.commit(f->stream))) return rc;
   return search_frame_common(f, Tcw_cur, last->Tcw, m, L, last->n_obs, last->angle, nullptr, th, mono, check_orientation, assigned_mp,
                              assigned_obs, nmatches_out);
 }
@@ -2420,12 +2391,13 @@ struct orbm_lastview {
   int device = 0;
   hipStream_t stream = nullptr;
   bool ext_stream = false;
-  DevBuf<uint8_t> arena;
-  PinnedBuf<uint8_t> stage;
+  orbg::StageBlock blk;                  // pinned staging block + the device block the searches read
   hipEvent_t ev = nullptr;
   bool pending = false;
   int n = 0;
-  size_t o_valid = 0, o_outl = 0, o_desc = 0, o_pos = 0, o_oct = 0, bytes = 0;
+  orbg::StageSlot<uint8_t> s_valid, s_outl, s_desc;
+  orbg::StageSlot<float> s_pos;
+  orbg::StageSlot<int> s_oct;
   std::vector<int32_t> n_obs;
   std::vector<float> angle;
   float Tcw[16] = {0};
@@ -2440,7 +2412,7 @@ extern "C" int orbm_lastview_create(int device, int cap_features, orbm_lastview*
   if (orbg::create_stream(&v->stream, "map") != hipSuccess) { delete v; return ORBG_HIP_ERROR; }
   if (hipEventCreateWithFlags(&v->ev, hipEventDisableTiming) != hipSuccess) { orbg::release_stream(v->stream); delete v; return ORBG_HIP_ERROR; }
   const size_t need = (size_t)std::max(cap_features, 16) * 64 + 256;
-  if ((rc = v->arena.reserve(need)) || (rc = v->stage.reserve(need))) { v->arena.release(); v->stage.release(); (void)hipEventDestroy(v->ev); orbg::release_stream(v->stream); delete v; return rc; }
+  if ((rc = v->blk.reserve(need))) { v->blk.release(); (void)hipEventDestroy(v->ev); orbg::release_stream(v->stream); delete v; return rc; }
   *out = v;
   return ORBG_OK;
 }
@@ -2449,7 +2421,7 @@ extern "C" int orbm_lastview_destroy(orbm_lastview* v) {
   if (!v) return ORBG_BAD_ARG;
   (void)hipSetDevice(v->device);
   (void)hipStreamSynchronize(v->stream);
-  v->arena.release(); v->stage.release();
+  v->blk.release();
   if (v->ev) (void)hipEventDestroy(v->ev);
   if (!v->ext_stream) orbg::release_stream(v->stream);
   delete v;
@@ -2463,21 +2435,21 @@ extern "C" int orbm_lastview_upload(orbm_lastview* v, const orbm_lastframe_view*
   int rc = select_device(v->device);
   if (rc) return rc;
   if (v->pending) { ORBG_HIP(hipEventSynchronize(v->ev)); v->pending = false; }      // the staging block of the previous upload
-  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  v->o_valid = 0; v->o_outl = al(m); v->o_desc = v->o_outl + al(m); v->o_pos = v->o_desc + al(32 * m); v->o_oct = v->o_pos + al(12 * m);
-  v->bytes = v->o_oct + al(4 * m);
-  if ((rc = v->arena.reserve(v->bytes + 64)) || (rc = v->stage.reserve(v->bytes + 64))) return rc;
+  orbg::StageBlock& S = v->blk;
+  orbg::StageLayout lay;
+  v->s_valid = lay.add<uint8_t>(m); v->s_outl = lay.add<uint8_t>(m); v->s_desc = lay.add<uint8_t>(32 * m); v->s_pos = lay.add<float>(3 * m);
+  v->s_oct = lay.add<int>(m);
+  if ((rc = S.reserve(lay.bytes() + 64))) return rc;
   v->n = last->n;
   v->n_obs.assign(last->n_obs, last->n_obs + m);
   v->angle.assign(last->angle, last->angle + m);
   memcpy(v->Tcw, last->Tcw, sizeof(v->Tcw));
   if (m > 0) {
-    uint8_t* S = v->stage.h;
-    memcpy(S + v->o_valid, last->mp_valid, m); memcpy(S + v->o_outl, last->outlier, m); memcpy(S + v->o_desc, last->desc, 32 * m);
-    memcpy(S + v->o_pos, last->world_pos, 12 * m); memcpy(S + v->o_oct, last->octave, 4 * m);
-    const int n16 = (int)((v->bytes + 15) / 16);
-    hipLaunchKernelGGL(lastview_copy_kernel, dim3((n16 + 255) / 256), dim3(256), 0, v->stream, reinterpret_cast<const uint4*>(v->stage.d),
-                       reinterpret_cast<uint4*>(v->arena.p), n16);
+    S.put(v->s_valid, last->mp_valid); S.put(v->s_outl, last->outlier); S.put(v->s_desc, last->desc);
+    S.put(v->s_pos, last->world_pos); S.put(v->s_oct, last->octave);
+    const int n16 = (int)(lay.bytes() / 16);
+    hipLaunchKernelGGL(lastview_copy_kernel, dim3((n16 + 255) / 256), dim3(256), 0, v->stream, reinterpret_cast<const uint4*>(S.pin.d),
+                       reinterpret_cast<uint4*>(S.dev.p), n16);
     ORBG_HIP(hipGetLastError());
     ORBG_HIP(hipEventRecord(v->ev, v->stream));
     v->pending = true;
@@ -2496,12 +2468,12 @@ extern "C" int orbm_search_by_projection_frame_resident(orbm_frame* f, const flo
   const int n = f->fp.n;
   if ((rc = stage_begin(f, (size_t)n * 8))) return rc;
   stage_occupancy(f, assigned_mp, assigned_obs, n);
-  if ((rc = stage_commit(f))) return rc;
-  const uint8_t* A = v->arena.p;
+  if ((rc = f->stage.commit(f->stream))) return rc;
+  const orbg::StageBlock& A = v->blk;
   LastDev L;
   L.n = m;
-  L.mp_valid = A + v->o_valid; L.outlier = A + v->o_outl; L.desc = A + v->o_desc;
-  L.world_pos = reinterpret_cast<const float*>(A + v->o_pos); L.octave = reinterpret_cast<const int*>(A + v->o_oct);
+  L.mp_valid = A.device(v->s_valid); L.outlier = A.device(v->s_outl); L.desc = A.device(v->s_desc);
+  L.world_pos = A.device(v->s_pos); L.octave = A.device(v->s_oct);
   hipEvent_t wait_ev = nullptr;
   if (v->pending) {
     if (hipEventQuery(v->ev) == hipSuccess) v->pending = false;
@@ -2551,11 +2523,11 @@ static int bow_common(orbm_frame* f, const orbm_featvec_view* fvF, const uint8_t
     if ((int)fvF->feat_idx[i] >= n) return ORBG_BAD_ARG;
   if ((rc = stage_begin(f, (size_t)nj * sizeof(BowJob) + (size_t)nfi * 4 + (size_t)nkf * 32 + (size_t)n))) return rc;
   hipStream_t st = f->stream;
-  const uint32_t* d_fidx = stage_add(f, fvF->feat_idx, nfi, true);
-  const uint8_t* d_tvalid = t_valid ? stage_add(f, t_valid, n, true) : nullptr;
-  const BowJob* d_jobs = stage_add(f, jobs.data(), nj);
-  const uint8_t* d_kfdesc = stage_add(f, kf_desc, (size_t)nkf * 32);
-  if ((rc = stage_commit(f))) return rc;
+  const uint32_t* d_fidx = f->stage.add(fvF->feat_idx, nfi, true);
+  const uint8_t* d_tvalid = t_valid ? f->stage.add(t_valid, n, true) : nullptr;
+  const BowJob* d_jobs = f->stage.add(jobs.data(), nj);
+  const uint8_t* d_kfdesc = f->stage.add(kf_desc, (size_t)nkf * 32);
+  if ((rc = f->stage.commit(f->stream))) return rc;
   rc = run_search(f, nj, [&](int list_cap, int* cnt, int* cnt_next) {
     hipLaunchKernelGGL(search_bow_kernel, dim3((nj + 3) / 4), dim3(256), 0, st, f->desc_p, d_fidx, d_tvalid, d_kfdesc,
                        d_jobs, nj, cnt, cnt_next, f->list.d, list_cap, f->results.d, n_left);
@@ -2668,8 +2640,8 @@ static int search_sim3_common(orbm_frame* f, orbm_map* mp, const float* Scw, con
   if ((rc = stage_begin(f, (size_t)n * 4 + (size_t)m))) return rc;
   hipStream_t st = f->stream;
   stage_occupancy(f, matched, nullptr, n);
-  const uint8_t* d_found = already_found ? stage_add(f, already_found, m) : nullptr;
-  if ((rc = stage_commit(f))) return rc;
+  const uint8_t* d_found = already_found ? f->stage.add(already_found, m) : nullptr;
+  if ((rc = f->stage.commit(f->stream))) return rc;
   float T16[16];
   {
     double d = 0;
@@ -2746,8 +2718,8 @@ static int search_reloc_common(orbm_frame* f, orbm_map* mp, const float* Tcw, co
   if ((rc = stage_begin(f, (size_t)n * 4 + (size_t)m))) return rc;
   hipStream_t st = f->stream;
   stage_occupancy(f, assigned_mp, nullptr, n);                   // any map point blocks a feature (:2246-2247)
-  const uint8_t* d_found = already_found ? stage_add(f, already_found, m) : nullptr;
-  if ((rc = stage_commit(f))) return rc;
+  const uint8_t* d_found = already_found ? f->stage.add(already_found, m) : nullptr;
+  if ((rc = f->stage.commit(f->stream))) return rc;
   PoseF P;
   make_pose(Tcw, &P);
   FrameDev F = frame_dev(f);

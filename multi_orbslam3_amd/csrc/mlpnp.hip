@@ -640,10 +640,9 @@ PnpRansac ransac_parameters(int N, double probability, int min_inliers, int max_
 }
 
 struct PnpBufs {
-  orbg::PinnedBuf<unsigned char> h_in, h_out;
-  orbg::DevBuf<unsigned char> d_in, d_out;
+  orbg::StageBlock blk;            // problems and draws up, hypotheses down
   orbg::StreamSignal sig;
-  void release_buffers() { h_in.release(); h_out.release(); d_in.release(); d_out.release(); sig.release(); }
+  void release_buffers() { blk.release(); sig.release(); }
 };
 using PnpWork = orbg::WorkArea<PnpBufs>;
 
@@ -696,16 +695,19 @@ int launch(PnpWork& w, const std::vector<PnpJob>& jobs, PnpOut& out) {
     o_pts += 9LL * D.n; o_draws += 6LL * j.H; o_hyp += j.H; o_mask += (long long)j.H * D.words;
     max_h = std::max(max_h, j.H);
   }
-  const size_t desc_bytes = (size_t)B * sizeof(PnpDesc);                // (a multiple of 8)
-  const size_t in_bytes = desc_bytes + 4 * (size_t)(o_pts + o_draws);
-  const size_t pose_bytes = 96 * (size_t)o_hyp, mask_bytes = 8 * (size_t)o_mask;
-  const size_t out_bytes = pose_bytes + mask_bytes + 8 * (size_t)o_hyp;
+  orbg::StageBlock& S = w.blk;
+  orbg::StageLayout lay;
+  const auto s_desc = lay.add<PnpDesc>(B);                              // in: one upload over the first three slots
+  const auto s_pts = lay.add<float>((size_t)o_pts);
+  const auto s_draws = lay.add<int32_t>((size_t)o_draws);
+  const auto s_pose = lay.add<double>(12 * (size_t)o_hyp);              // out: one download over the last three
+  const auto s_mask = lay.add<unsigned long long>((size_t)o_mask);
+  const auto s_cnt = lay.add<int>(2 * (size_t)o_hyp);
   int rc;
-  if ((rc = w.h_in.reserve(in_bytes)) || (rc = w.d_in.reserve(in_bytes)) || (rc = w.h_out.reserve(out_bytes)) || (rc = w.d_out.reserve(out_bytes)))
-    return rc;
-  memcpy(w.h_in.h, out.desc.data(), desc_bytes);
-  float* hf = (float*)(w.h_in.h + desc_bytes);
-  int32_t* hd = (int32_t*)(hf + o_pts);
+  if ((rc = S.reserve(lay.bytes()))) return rc;
+  S.put(s_desc, out.desc.data());
+  float* hf = S.host(s_pts);
+  int32_t* hd = S.host(s_draws);
   for (int b = 0; b < B; b++) {
     const PnpJob& j = jobs[b];
     const PnpDesc& D = out.desc[b];
@@ -715,20 +717,12 @@ int launch(PnpWork& w, const std::vector<PnpJob>& jobs, PnpOut& out) {
     if (j.probe) memset(hd + D.off_draws, 0, 24 * (size_t)j.H);
     else memcpy(hd + D.off_draws, j.draws, 24 * (size_t)j.H);
   }
-  ORBG_HIP(hipMemcpyAsync(w.d_in.p, w.h_in.h, in_bytes, hipMemcpyHostToDevice, st));
-  const PnpDesc* d_desc = (const PnpDesc*)w.d_in.p;
-  const float* d_pts = (const float*)(w.d_in.p + desc_bytes);
-  const int* d_draws = (const int*)(d_pts + o_pts);
-  double* d_pose = (double*)w.d_out.p;
-  unsigned long long* d_mask = (unsigned long long*)(w.d_out.p + pose_bytes);
-  int* d_cnt = (int*)(w.d_out.p + pose_bytes + mask_bytes);
-  hipLaunchKernelGGL(mlpnp_ransac_kernel, dim3(max_h, B), dim3(kThreads), 0, st, d_desc, d_pts, d_draws, d_pose, d_cnt, d_mask);
+  if ((rc = S.upload(s_desc.off, s_draws.end(), st))) return rc;
+  hipLaunchKernelGGL(mlpnp_ransac_kernel, dim3(max_h, B), dim3(kThreads), 0, st, (const PnpDesc*)S.device(s_desc), (const float*)S.device(s_pts),
+                     (const int*)S.device(s_draws), S.device(s_pose), S.device(s_cnt), S.device(s_mask));
   ORBG_HIP(hipGetLastError());
-  ORBG_HIP(hipMemcpyAsync(w.h_out.h, w.d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
-  if ((rc = w.sig.sync(st))) return rc;
-  out.poses = (const double*)w.h_out.h;
-  out.masks = (const unsigned long long*)(w.h_out.h + pose_bytes);
-  out.counts = (const int*)(w.h_out.h + pose_bytes + mask_bytes);
+  if ((rc = S.download(s_pose.off, s_cnt.end(), st)) || (rc = w.sig.sync(st))) return rc;
+  out.poses = S.host(s_pose); out.masks = S.host(s_mask); out.counts = S.host(s_cnt);
   return ORBG_OK;
 }
 

@@ -335,8 +335,7 @@ void pair_geometry(const orbm_newpoints_kf& k1, const orbm_newpoints_kf& k2, flo
 }
 
 struct NpBufs {
-  orbg::PinnedBuf<uint8_t> stage;
-  orbg::DevBuf<uint8_t> d_stage;
+  orbg::StageBlock stage;
   orbg::DevBuf<orbm_newpoints_record> d_rec;
   orbg::PinnedBuf<orbm_newpoints_record> h_rec;
   std::vector<int2> range;
@@ -344,7 +343,7 @@ struct NpBufs {
   std::vector<uint8_t> claimed;
   std::vector<int32_t> m12;
   std::vector<uint32_t> rot_entries;
-  void release_buffers() { stage.release(); d_stage.release(); d_rec.release(); h_rec.release(); }
+  void release_buffers() { stage.release(); d_rec.release(); h_rec.release(); }
 };
 
 struct KfHost {                     // what the frame object says about a keyframe
@@ -415,42 +414,26 @@ int run_records(orbg::WorkArea<NpBufs>& W, const orbm_newpoints_kf* kf1, const K
     return ORBG_OK;
   }
   // one pinned block, one H2D copy: NbDev[B], ranges, has_mp / mvKeys of KF1, then per neighbour its lists, has_mp and mvKeys
-  size_t total = 0;
-  auto room = [&](size_t bytes) { const size_t o = total; total += (bytes + 15) & ~(size_t)15; return o; };
-  const size_t o_nb = room((size_t)B * sizeof(NbDev)), o_range = room(nrec * sizeof(int2)), o_mp1 = room((size_t)n1);
-  const size_t o_xy1 = kf1->keys_xy ? room((size_t)n1 * 8) : 0;
-  std::vector<size_t> o_cand(B), o_mp2(B), o_xy2(B);
-  for (int b = 0; b < B; b++) {
-    const orbm_featvec_view& f2 = nbs[b].featvec;
-    o_cand[b] = room((size_t)(f2.n_nodes > 0 ? f2.start[f2.n_nodes] : 0) * 4);
-    o_mp2[b] = room((size_t)hn[b].n);
-    o_xy2[b] = nbs[b].keys_xy ? room((size_t)hn[b].n * 8) : 0;
-  }
-  if ((rc = W.stage.reserve(total)) || (rc = W.d_stage.reserve(total)) || (rc = W.d_rec.reserve(nrec))) return rc;
-  uint8_t* hs = W.stage.h;
-  const uint8_t* ds = W.d_stage.p;
+  auto n_cand = [](const orbm_featvec_view& f) { return (size_t)(f.n_nodes > 0 ? f.start[f.n_nodes] : 0); };
+  size_t payload = (size_t)B * sizeof(NbDev) + nrec * sizeof(int2) + 9 * (size_t)n1;
+  for (int b = 0; b < B; b++) payload += 4 * n_cand(nbs[b].featvec) + 9 * (size_t)hn[b].n;
+  orbg::StageBlock& S = W.stage;
+  if ((rc = S.begin(orbg::StageLayout::bound(4 + 3 * (size_t)B, payload))) || (rc = W.d_rec.reserve(nrec))) return rc;
   NpArgs A;
   fill_kf(*kf1, h1, &A.k1);
-  memcpy(hs + o_mp1, kf1->has_mp, (size_t)n1);
-  A.k1.has_mp = ds + o_mp1;
-  if (kf1->keys_xy) { memcpy(hs + o_xy1, kf1->keys_xy, (size_t)n1 * 8); A.k1.keys_xy = (const float*)(ds + o_xy1); }
-  memcpy(hs + o_range, W.range.data(), nrec * sizeof(int2));
+  A.k1.has_mp = S.add(kf1->has_mp, n1, true);
+  if (kf1->keys_xy) A.k1.keys_xy = S.add(kf1->keys_xy, 2 * (size_t)n1, true);
+  A.range = S.add(W.range.data(), nrec, true);
   W.nb.resize(B);
   for (int b = 0; b < B; b++) {
     NbDev& N = W.nb[b];
-    const orbm_featvec_view& f2 = nbs[b].featvec;
-    const size_t nc = f2.n_nodes > 0 ? f2.start[f2.n_nodes] : 0;
     fill_kf(nbs[b], hn[b], &N.kf);
-    if (nc) memcpy(hs + o_cand[b], f2.feat_idx, nc * 4);
-    if (hn[b].n) memcpy(hs + o_mp2[b], nbs[b].has_mp, (size_t)hn[b].n);
-    N.cand = (const uint32_t*)(ds + o_cand[b]);
-    N.kf.has_mp = ds + o_mp2[b];
-    if (nbs[b].keys_xy) { memcpy(hs + o_xy2[b], nbs[b].keys_xy, (size_t)hn[b].n * 8); N.kf.keys_xy = (const float*)(ds + o_xy2[b]); }
+    N.cand = S.add(nbs[b].featvec.feat_idx, n_cand(nbs[b].featvec), true);
+    N.kf.has_mp = S.add(nbs[b].has_mp, hn[b].n, true);
+    if (nbs[b].keys_xy) N.kf.keys_xy = S.add(nbs[b].keys_xy, 2 * (size_t)hn[b].n, true);
     pair_geometry(*kf1, nbs[b], N.F12, N.ep);
   }
-  memcpy(hs + o_nb, W.nb.data(), (size_t)B * sizeof(NbDev));
-  A.nb = (const NbDev*)(ds + o_nb);
-  A.range = (const int2*)(ds + o_range);
+  A.nb = S.add(W.nb.data(), B, true);
   A.rec = W.d_rec.p;
   A.n1 = n1; A.only_stereo = pr->only_stereo != 0; A.coarse = pr->coarse != 0; A.far_points = pr->far_points != 0; A.match_only = match_only;
   A.th_far = pr->th_far_points; A.ratio_factor = 1.5f * kf1->scale_factor;
@@ -459,7 +442,7 @@ int run_records(orbg::WorkArea<NpBufs>& W, const orbm_newpoints_kf* kf1, const K
   orbg::StreamDrain drain{st};
   for (int b = 0; b < B; b++)
     if ((rc = orbm_internal_order_after(nbs[b].frame, st))) return rc;
-  ORBG_HIP(hipMemcpyAsync(W.d_stage.p, hs, total, hipMemcpyHostToDevice, st));
+  if ((rc = S.commit(st))) return rc;
   hipLaunchKernelGGL(newpoints_kernel, dim3((n1 + kThreads / kLanes - 1) / (kThreads / kLanes), B), dim3(kThreads), 0, st, A);
   ORBG_HIP(hipGetLastError());
   ORBG_HIP(hipMemcpyAsync(W.h_rec.h, W.d_rec.p, nrec * sizeof(orbm_newpoints_record), hipMemcpyDeviceToHost, st));

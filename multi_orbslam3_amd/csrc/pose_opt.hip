@@ -853,9 +853,12 @@ extern "C" int pose_opt_debug_prof(long long* out, int reset) {
 // the calling thread's work area (common.hpp; PoseOptimization has no handle: the reference calls a static member)
 namespace {
 struct PoBufs {
-  PinnedBuf<uint8_t> stage; DevBuf<uint8_t> dev;
-  void release_buffers() { stage.release(); dev.release(); }
+  orbg::StageBlock stage;
+  void release_buffers() { stage.release(); }
 };
+// what the kernel leaves in the staging block next to the outlier flags; stats: nBad, the iterations of the four rounds, two unused
+// words, then the sequence number that completes the record
+struct PoOut { PoseQ T; double chi2[4]; int stats[8]; };
 WorkArea<PoBufs>& po_work() { static thread_local WorkArea<PoBufs> w; return w; }
 }  // namespace
 
@@ -882,29 +885,20 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   for (int i = 0; i < 4; i++) { r->iters[i] = 0; r->chi2[i] = 0; }
   for (int i = 0; i < n; i++) r->outlier[i] = 0;
   if (n < 3) return ORBG_OK;                                  // S/Optimizer.cc:1180-1181
-  const size_t in_bytes = ((size_t)n * 7 * 4 + 15) & ~(size_t)15;
-  const size_t out_off = in_bytes;
-  const size_t out_bytes = sizeof(PoseQ) + 8 * sizeof(int) + 4 * sizeof(double) + (size_t)n + 64;
-  if ((rc = sc.stage.reserve(in_bytes + out_bytes + 64)) || (rc = sc.dev.reserve(in_bytes + out_bytes + 64))) return rc;
-  float* hs = reinterpret_cast<float*>(sc.stage.h);
-  memcpy(hs, p->Xw, (size_t)n * 12);
-  memcpy(hs + 3 * (size_t)n, p->u, (size_t)n * 4);
-  memcpy(hs + 4 * (size_t)n, p->v, (size_t)n * 4);
-  memcpy(hs + 5 * (size_t)n, p->ur, (size_t)n * 4);
-  memcpy(hs + 6 * (size_t)n, p->inv_sigma2, (size_t)n * 4);
-  // small problems: the wide kernel reads its inputs straight from this pinned block (once, into registers); large ones are re-read
-  // on every pass and get a device copy.  Results always land in the pinned block, followed by a sequence number the host spins on.
-  const float* dX;
-  if (n <= kPoPinnedN) dX = reinterpret_cast<const float*>(sc.stage.d);
-  else {
-    ORBG_HIP(hipMemcpyAsync(sc.dev.p, sc.stage.h, in_bytes, hipMemcpyHostToDevice, sc.stream));
-    dX = reinterpret_cast<const float*>(sc.dev.p);
-  }
-  uint8_t* dout = sc.stage.d + out_off;
-  PoseQ* dT = reinterpret_cast<PoseQ*>(dout);
-  double* dchi = reinterpret_cast<double*>(dout + sizeof(PoseQ));
-  int* dstats = reinterpret_cast<int*>(dout + sizeof(PoseQ) + 4 * sizeof(double));
-  uint8_t* dflag = dout + sizeof(PoseQ) + 4 * sizeof(double) + 8 * sizeof(int);
+  // small problems: the wide kernel reads its inputs straight from the pinned block (once, into registers); large ones are re-read
+  // on every pass and get a device copy.  Results always land in the pinned block, with a sequence number the host spins on.
+  orbg::StageBlock& S = sc.stage;
+  const bool dev_copy = n > kPoPinnedN;
+  // (+ 32: this block used to be reserved with 128 spare bytes behind the flags; 32 on top of the bound keep its capacity for a given n
+  // at least what it was, so a thread that has seen its largest n still allocates nothing)
+  if ((rc = S.begin(orbg::StageLayout::bound(7, (size_t)n * 29 + sizeof(PoOut)) + 32))) return rc;
+  const float* dX = S.add(p->Xw, 3 * (size_t)n, dev_copy);
+  const float* du = S.add(p->u, n, dev_copy); const float* dv = S.add(p->v, n, dev_copy); const float* dur = S.add(p->ur, n, dev_copy);
+  const float* dom = S.add(p->inv_sigma2, n, dev_copy);
+  if ((rc = S.commit(sc.stream))) return rc;
+  const auto s_out = S.room<PoOut>(1);
+  const auto s_flag = S.room<uint8_t>(n);
+  PoOut* dout = S.mapped(s_out);
   PoseQ T0;
   {
     const float* T = p->Tcw;
@@ -919,12 +913,13 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   static thread_local unsigned po_seq = 0;
   po_seq = (po_seq + 1) & 0x7FFFFFFFu;
   if (po_seq == 0) po_seq = 1;
-  volatile int* seq_word = reinterpret_cast<volatile int*>(sc.stage.h + out_off + sizeof(PoseQ) + 4 * sizeof(double)) + 7;
-  *seq_word = 0;
-  // one launch site for every form: the five input arrays lie one after the other behind dX
+  PoOut* ho = S.host(s_out);
+  volatile const int* seq_word = &ho->stats[7];
+  ho->stats[7] = 0;
+  // one launch site for every form
   auto launch = [&](auto kernel, int threads, const auto& camera) {
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, sc.stream, n, dX, dX + 3 * (size_t)n, dX + 4 * (size_t)n, dX + 5 * (size_t)n,
-                       dX + 6 * (size_t)n, camera, T0, dT, dflag, dstats, dchi, po_seq);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, sc.stream, n, dX, du, dv, dur, dom, camera, T0, &dout->T, S.mapped(s_flag),
+                       dout->stats, dout->chi2, po_seq);
   };
   if (p->rig) {
     // a Frame with camera models / a second camera: the wide kernel over CamRig, up to eight correspondences per thread
@@ -951,15 +946,11 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
     }
     if (!got) ORBG_HIP(hipStreamSynchronize(sc.stream));
   }
-  const uint8_t* ho = sc.stage.h + out_off;
-  PoseQ Tf;
-  memcpy(&Tf, ho, sizeof(PoseQ));
-  memcpy(r->chi2, ho + sizeof(PoseQ), 4 * sizeof(double));
-  int stats[8];
-  memcpy(stats, ho + sizeof(PoseQ) + 4 * sizeof(double), sizeof(stats));
-  memcpy(r->outlier, ho + sizeof(PoseQ) + 4 * sizeof(double) + 8 * sizeof(int), (size_t)n);
-  r->n_bad = stats[0];
-  for (int i = 0; i < 4; i++) r->iters[i] = stats[1 + i];
+  const PoseQ Tf = ho->T;
+  memcpy(r->chi2, ho->chi2, sizeof(ho->chi2));
+  S.get(s_flag, r->outlier);
+  r->n_bad = ho->stats[0];
+  for (int i = 0; i < 4; i++) r->iters[i] = ho->stats[1 + i];
   r->n_inliers = n - r->n_bad;
   double R[9];
   quat_to_R(Tf.q, R);

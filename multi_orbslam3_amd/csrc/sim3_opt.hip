@@ -367,12 +367,11 @@ __global__ __launch_bounds__(kS3oThreads) void sim3_opt_kernel(const S3oDesc* __
 
 // ------------------------------------------------------------------------------------------------ host side
 
-struct S3oBufs {                 // the calling thread's buffers: one pinned block in, one pinned block out, the device copies
-  orbg::PinnedBuf<uint8_t> h_in, h_out;
-  orbg::DevBuf<uint8_t> d_in, d_out;
+struct S3oBufs {                 // the calling thread's buffers: one staging block (inputs up, records down) and the per-edge chi2
+  orbg::StageBlock blk;
   orbg::DevBuf<double> d_chi;
   std::vector<double> h_chi;
-  void release_buffers() { h_in.release(); h_out.release(); d_in.release(); d_out.release(); d_chi.release(); }
+  void release_buffers() { blk.release(); d_chi.release(); }
 };
 using S3oWork = orbg::WorkArea<S3oBufs>;
 S3oWork& s3o_work() { static thread_local S3oWork w; return w; }
@@ -390,8 +389,6 @@ int check_problem(const orbm_sim3opt_problem* p) {
   if (!(p->th2 > 0.0f)) return ORBG_BAD_ARG;
   return ORBG_OK;
 }
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -424,14 +421,14 @@ extern "C" int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* 
   if (J > 0) {
     w = &s3o_work();
     if ((rc = w->open(device, "misc"))) return rc;
-    const size_t desc_bytes = align16((size_t)J * sizeof(S3oDesc));
-    const size_t in_bytes = desc_bytes + n_tot * 12 * sizeof(float);
-    const size_t rec_bytes = align16((size_t)J * sizeof(S3oRec));
-    const size_t out_bytes = rec_bytes + n_tot;
-    if ((rc = w->h_in.reserve(in_bytes)) || (rc = w->d_in.reserve(in_bytes)) || (rc = w->h_out.reserve(out_bytes)) ||
-        (rc = w->d_out.reserve(out_bytes)) || (rc = w->d_chi.reserve(4 * n_tot)))
-      return rc;
-    float* hin = reinterpret_cast<float*>(w->h_in.h + desc_bytes);
+    orbg::StageBlock& S = w->blk;
+    orbg::StageLayout lay;
+    const auto s_desc = lay.add<S3oDesc>(J);               // in: one upload over the first two slots
+    const auto s_in = lay.add<float>(12 * n_tot);
+    const auto s_rec = lay.add<S3oRec>(J);                 // out: one download over the last two
+    const auto s_rem = lay.add<uint8_t>(n_tot);
+    if ((rc = S.reserve(lay.bytes())) || (rc = w->d_chi.reserve(4 * n_tot))) return rc;
+    float* hin = S.host(s_in);
     size_t off = 0;
     for (int j = 0; j < J; j++) {
       const orbm_sim3opt_problem& p = problems[jobs[j]];
@@ -453,21 +450,20 @@ extern "C" int orbm_sim3_optimize_batch(int device, const orbm_sim3opt_problem* 
       memcpy(dst + 10 * n, p.inv_sigma2_1, 4 * n); memcpy(dst + 11 * n, p.inv_sigma2_2, 4 * n);
       off += n;
     }
-    memcpy(w->h_in.h, descs.data(), (size_t)J * sizeof(S3oDesc));
+    S.put(s_desc, descs.data());
     hipStream_t st = w->stream;
-    ORBG_HIP(hipMemcpyAsync(w->d_in.p, w->h_in.h, in_bytes, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(sim3_opt_kernel, dim3(J), dim3(kS3oThreads), 0, st, reinterpret_cast<const S3oDesc*>(w->d_in.p),
-                       reinterpret_cast<const float*>(w->d_in.p + desc_bytes), w->d_chi.p, w->d_out.p + rec_bytes,
-                       reinterpret_cast<S3oRec*>(w->d_out.p));
+    if ((rc = S.upload(s_desc.off, s_in.end(), st))) return rc;
+    hipLaunchKernelGGL(sim3_opt_kernel, dim3(J), dim3(kS3oThreads), 0, st, (const S3oDesc*)S.device(s_desc), (const float*)S.device(s_in),
+                       w->d_chi.p, S.device(s_rem), S.device(s_rec));
     ORBG_HIP(hipGetLastError());
-    ORBG_HIP(hipMemcpyAsync(w->h_out.h, w->d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    if ((rc = S.download(s_rec.off, s_rem.end(), st))) return rc;
     if (want_chi) {
       w->h_chi.resize(4 * n_tot);
       ORBG_HIP(hipMemcpyAsync(w->h_chi.data(), w->d_chi.p, 4 * n_tot * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     ORBG_HIP(hipStreamSynchronize(st));
-    recs = reinterpret_cast<const S3oRec*>(w->h_out.h);
-    rems = w->h_out.h + rec_bytes;
+    recs = S.host(s_rec);
+    rems = S.host(s_rem);
   }
   for (int b = 0; b < B; b++) {
     const orbm_sim3opt_problem& p = problems[b];

@@ -721,10 +721,8 @@ void normalize_keys(const float* keys, int n, float* pn, float* T) {
 }
 
 struct TvBufs {
-  orbg::PinnedBuf<uint32_t> h_in;      // the one upload: 8 N floats, N keypoint indices, 8 H draws
-  orbg::PinnedBuf<unsigned char> h_out;   // the one download: TvRec, vP3D, vbTriangulated
-  orbg::DevBuf<uint32_t> d_in;
-  orbg::DevBuf<unsigned char> d_out, d_flags;
+  orbg::StageBlock blk;                // the one upload: 8 N floats, N keypoint indices, 8 H draws; the one download: TvRec, vP3D, vbTriangulated
+  orbg::DevBuf<unsigned char> d_flags;
   orbg::DevBuf<float> d_hyp, d_scores, d_p3d;
   orbg::DevBuf<u64> d_masks;
   orbg::DevBuf<int> d_sets;
@@ -732,7 +730,7 @@ struct TvBufs {
   bool tickets_ready = false;
   std::vector<float> pn1, pn2, h_hyp;
   void release_buffers() {
-    h_in.release(); h_out.release(); d_in.release(); d_out.release(); d_flags.release(); d_hyp.release(); d_scores.release();
+    blk.release(); d_flags.release(); d_hyp.release(); d_scores.release();
     d_p3d.release(); d_masks.release(); d_sets.release(); d_tickets.release();
     tickets_ready = false;
   }
@@ -792,12 +790,16 @@ extern "C" int orbi_two_view_reconstruct(int device, const orbi_two_view_problem
   normalize_keys(p->keys2, p->n2, w.pn2.data(), P.T2);
   inv3(P.T2, P.T2inv);
 
-  const size_t n_in = 9 * (size_t)N + 8 * (size_t)H;
-  const size_t rec_bytes = (sizeof(TvRec) + 15) & ~(size_t)15;
-  const size_t out_bytes = rec_bytes + 12 * (size_t)p->n1 + (size_t)p->n1;
+  orbg::StageBlock& S = w.blk;
+  orbg::StageLayout lay;
+  const auto s_f = lay.add<float>(8 * (size_t)N);            // in: one upload over the first three slots
+  const auto s_idx1 = lay.add<int>(N);
+  const auto s_draws = lay.add<int32_t>(8 * (size_t)H);
+  const auto s_rec = lay.add<TvRec>(1);                      // out: one download over the last three
+  const auto s_p3d = lay.add<float>(3 * (size_t)p->n1);
+  const auto s_tri = lay.add<uint8_t>(p->n1);
   const size_t n_hyp = 2 * (size_t)H;
-  if ((rc = w.h_in.reserve(n_in)) || (rc = w.h_out.reserve(out_bytes)) || (rc = w.d_in.reserve(n_in)) || (rc = w.d_out.reserve(out_bytes)) ||
-      (rc = w.d_flags.reserve((size_t)kMotions * N)) || (rc = w.d_p3d.reserve(3 * (size_t)kMotions * N)) ||
+  if ((rc = S.reserve(lay.bytes())) || (rc = w.d_flags.reserve((size_t)kMotions * N)) || (rc = w.d_p3d.reserve(3 * (size_t)kMotions * N)) ||
       (rc = w.d_hyp.reserve(n_hyp * kHypFloats)) || (rc = w.d_scores.reserve(n_hyp)) || (rc = w.d_masks.reserve(n_hyp * P.words)) ||
       (rc = w.d_sets.reserve(8 * (size_t)H)))
     return rc;
@@ -807,8 +809,8 @@ extern "C" int orbi_two_view_reconstruct(int device, const orbi_two_view_problem
     w.tickets_ready = true;
   }
   {
-    float* f = (float*)w.h_in.h;
-    int32_t* k1 = (int32_t*)w.h_in.h + 8 * (size_t)N;
+    float* f = S.host(s_f);
+    int* k1 = S.host(s_idx1);
     int m = 0;
     for (int i = 0; i < p->n1; i++) {
       const int j = p->matches12[i];
@@ -818,22 +820,22 @@ extern "C" int orbi_two_view_reconstruct(int device, const orbi_two_view_problem
       k1[m] = i;
       m++;
     }
-    memcpy(k1 + N, draws, 32 * (size_t)H);
+    S.put(s_draws, draws);
   }
-  ORBG_HIP(hipMemcpyAsync(w.d_in.p, w.h_in.h, n_in * 4, hipMemcpyHostToDevice, st));
-  const float* d_f = (const float*)w.d_in.p;
-  const int* d_idx1 = (const int*)w.d_in.p + 8 * (size_t)N;
-  const int* d_draws = d_idx1 + N;
-  TvRec* d_rec = (TvRec*)w.d_out.p;
-  float* d_P3D = (float*)(w.d_out.p + rec_bytes);
-  uint8_t* d_tri = (uint8_t*)(w.d_out.p + rec_bytes + 12 * (size_t)p->n1);
+  if ((rc = S.upload(s_f.off, s_draws.end(), st))) return rc;
+  const float* d_f = S.device(s_f);
+  const int* d_idx1 = S.device(s_idx1);
+  const int* d_draws = S.device(s_draws);
+  TvRec* d_rec = S.device(s_rec);
+  float* d_P3D = S.device(s_p3d);
+  uint8_t* d_tri = S.device(s_tri);
   hipLaunchKernelGGL(tv_ransac_kernel, dim3(2 * P.nG), dim3(kGroup), 0, st, P, d_f, d_draws, w.d_hyp.p, w.d_scores.p, w.d_masks.p,
                      w.d_sets.p, w.d_tickets.p, d_rec);
   ORBG_HIP(hipGetLastError());
   hipLaunchKernelGGL(tv_check_rt_kernel, dim3(kMotions), dim3(kRtThreads), 0, st, P, d_f, d_idx1, (const u64*)w.d_masks.p, d_rec,
                      (uint8_t*)w.d_flags.p, w.d_p3d.p, w.d_tickets.p, d_P3D, d_tri);
   ORBG_HIP(hipGetLastError());
-  ORBG_HIP(hipMemcpyAsync(w.h_out.h, w.d_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+  if ((rc = S.download(s_rec.off, s_tri.end(), st))) return rc;
   if (r->hyp_scores) ORBG_HIP(hipMemcpyAsync(r->hyp_scores, w.d_scores.p, n_hyp * 4, hipMemcpyDeviceToHost, st));
   if (r->hyp_masks) ORBG_HIP(hipMemcpyAsync(r->hyp_masks, w.d_masks.p, n_hyp * P.words * 8, hipMemcpyDeviceToHost, st));
   if (r->hyp_sets) ORBG_HIP(hipMemcpyAsync(r->hyp_sets, w.d_sets.p, 32 * (size_t)H, hipMemcpyDeviceToHost, st));
@@ -845,7 +847,7 @@ extern "C" int orbi_two_view_reconstruct(int device, const orbi_two_view_problem
   if (r->hyp_models)
     for (size_t h = 0; h < n_hyp; h++) memcpy(r->hyp_models + 9 * h, w.h_hyp.data() + h * kHypFloats, 36);
 
-  const TvRec& rec = *(const TvRec*)w.h_out.h;
+  const TvRec& rec = *S.host(s_rec);
   r->success = rec.success; r->model = rec.model; r->best_iteration_H = rec.bestH; r->best_iteration_F = rec.bestF;
   r->n_matches = N; r->n_inliers = rec.n_inliers; r->n_motions = rec.n_motions; r->best_motion = rec.best_motion;
   r->h_degenerate = rec.h_degenerate; r->SH = rec.SH; r->SF = rec.SF;
@@ -853,7 +855,7 @@ extern "C" int orbi_two_view_reconstruct(int device, const orbi_two_view_problem
   memcpy(r->T1, P.T1, 36); memcpy(r->T2, P.T2, 36);
   memcpy(r->motion_nGood, rec.nGood, sizeof(rec.nGood)); memcpy(r->motion_parallax, rec.parallax, sizeof(rec.parallax));
   memcpy(r->motion_R, rec.R, sizeof(rec.R)); memcpy(r->motion_t, rec.t, sizeof(rec.t));
-  if (r->vP3D && p->n1 > 0) memcpy(r->vP3D, w.h_out.h + rec_bytes, 12 * (size_t)p->n1);
-  if (r->vbTriangulated && p->n1 > 0) memcpy(r->vbTriangulated, w.h_out.h + rec_bytes + 12 * (size_t)p->n1, (size_t)p->n1);
+  if (r->vP3D) S.get(s_p3d, r->vP3D);
+  if (r->vbTriangulated) S.get(s_tri, r->vbTriangulated);
   return ORBG_OK;
 }

@@ -62,6 +62,18 @@ def test_ldlt_xcd_plan_and_schedule_for_every_size():
     assert r.returncode == 0 and "176 system sizes checked: ALL OK" in r.stdout, (r.stdout[-2000:], r.stderr[-500:])
 
 
+def test_stage_layout_slots_for_random_sequences():
+    """tests/cpp/stage_layout_check.cpp (host only, plain g++ with AddressSanitizer and UBSan over this program alone): seeded random
+    sequences of typed slots through csrc/stage_layout.hpp -- element sizes 1 to 32 bytes and the record structs, counts 0, 1 and section
+    ends at every residue mod 16, one sequence past 4 GiB -- keep every offset a multiple of 16, no two slots overlapping, the total
+    covering the last slot and the bound never below the total reached."""
+    exe = os.path.join(CPP, "stage_layout_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-o", exe, os.path.join(CPP, "stage_layout_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "4017 slot sequences checked: ALL OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+
+
 def test_lba_glue_alone_is_timed_on_the_host():
     """tests/cpp/glue_cpu_bench: the LocalBundleAdjustment glue over the mocks with an entry-point set that returns at once."""
     import json
