@@ -1427,6 +1427,97 @@ typedef struct pose_opt_result {
  * runs in ONE kernel launch (LM control flow on the device). */
 int pose_optimize(const pose_opt_problem* p, pose_opt_result* r);
 
+/* ---------------------------------------------------------------- pose-inertial optimisation (the per-frame optimiser of an inertial agent)
+ *
+ * Optimizer::PoseInertialOptimizationLastKeyFrame (S/Optimizer.cc:7603-7996) and ...LastFrame (:7998-8424), what
+ * Tracking::TrackLocalMap calls instead of PoseOptimization once the IMU is initialised (S/Tracking.cc:2689-2740). */
+enum { POSE_INERTIAL_LAST_KEYFRAME = 0, POSE_INERTIAL_LAST_FRAME = 1 };
+
+/* What VertexPose / VertexVelocity / VertexGyroBias / VertexAccBias read of a Frame or KeyFrame (S/G2oTypes.cc:73-119, 648-691):
+ * GetImuRotation(), GetImuPosition(), the velocity, mImuBias (bwx.., bax..). */
+typedef struct pose_inertial_state {
+  float Rwb[9];            /* row-major */
+  float twb[3];
+  float vwb[3];
+  float bg[3];
+  float ba[3];
+} pose_inertial_state;
+
+/* What EdgeInertial reads of an IMU::Preintegrated (S/G2oTypes.cc:695-800, S/ImuTypes.cc:404-431). */
+typedef struct pose_inertial_preint {
+  float dT;
+  float dR[9], dV[3], dP[3];
+  float JRg[9], JVg[9], JVa[9], JPg[9], JPa[9];
+  float bg[3], ba[3];      /* Preintegrated::b, the bias the deltas were integrated with */
+} pose_inertial_preint;
+
+/* ConstraintPoseImu as it is stored (I/G2oTypes.h:703-746): H after the constructor's conditioning (orbg_condition_prior). */
+typedef struct pose_inertial_prior {
+  double Rwb[9], twb[3], vwb[3], bg[3], ba[3];
+  double H[225];           /* row-major; rows / columns: rotation, translation, velocity, gyro bias, accelerometer bias */
+} pose_inertial_prior;
+
+typedef struct pose_inertial_problem {
+  uint32_t struct_size;    /* sizeof(pose_inertial_problem) */
+  int32_t form;            /* POSE_INERTIAL_LAST_KEYFRAME / POSE_INERTIAL_LAST_FRAME */
+  int32_t rec_init;        /* bRecInit */
+  int32_t device;
+  int32_t n_left;          /* Frame::Nleft; must be -1 (a two-camera Frame is refused with ORBG_BAD_ARG) */
+  int32_t n;               /* nInitialCorrespondences: one entry per feature that holds a map point */
+  const float* Xw;         /* n x 3, pMP->GetWorldPos() */
+  const float* u;          /* mvKeysUn[i].pt.x */
+  const float* v;          /* mvKeysUn[i].pt.y */
+  const float* ur;         /* mvuRight[i]; < 0 => EdgeMonoOnlyPose, else EdgeStereoOnlyPose */
+  const float* inv_sigma2; /* mvInvLevelSigma2[octave] (Pinhole::uncertainty2 is 1) */
+  const uint8_t* close;    /* mvpMapPoints[i]->mTrackDepth < 10.f */
+  float fx, fy, cx, cy, bf;
+  float Tcb[12];           /* mImuCalib.Tcb, rows 0-2 (row-major 3 x 4) */
+  pose_inertial_state frame;   /* pFrame */
+  pose_inertial_state other;   /* pFrame->mpLastKeyFrame (fixed) / pFrame->mpPrevFrame (optimised with the frame) */
+  pose_inertial_preint preint; /* pFrame->mpImuPreintegrated / mpImuPreintegratedFrame */
+  double info9[81];        /* EdgeInertial's information (orbg_imu_information) */
+  double infoG[9];         /* EdgeGyroRW's */
+  double infoA[9];         /* EdgeAccRW's */
+  const pose_inertial_prior* prior;   /* LAST_FRAME: pFp->mpcpi (required); LAST_KEYFRAME: ignored */
+} pose_inertial_problem;
+
+typedef struct pose_inertial_result {
+  uint32_t struct_size;    /* sizeof(pose_inertial_result) */
+  int32_t  n_inliers;      /* return value: nInitialCorrespondences - nBad */
+  int32_t  n_bad;
+  int32_t  rounds_run;     /* 4, or 1 when the graph has fewer than 10 edges */
+  int32_t  solve_failed;   /* a factorisation met a pivot that is not positive: that round's iterations ended without an update */
+  uint8_t* outlier;        /* n, pFrame->mvbOutlier for the correspondences (caller-allocated) */
+  double   Rwb[9], twb[3], vwb[3], bg[3], ba[3];   /* the frame's estimates (SetImuPoseVelocity, mImuBias) */
+  double   chi2[4];        /* robustified chi2 of the active edges at the last linearisation of each round: the errors the edges are classified with */
+  double   H[225];         /* what the reference passes to the ConstraintPoseImu constructor (before its conditioning) */
+} pose_inertial_result;
+
+/* int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame*, bool) / ...LastFrame(Frame*, bool): 4 rounds x 10 Gauss-Newton
+ * iterations on the frame's pose, velocity and biases (LAST_FRAME: and the previous frame's, 30 unknowns) with EdgeMonoOnlyPose /
+ * EdgeStereoOnlyPose, EdgeInertial, EdgeGyroRW, EdgeAccRW and (LAST_FRAME) EdgePriorPoseImu; outliers re-classified after every
+ * round with the error each edge holds (the one before the round's last update for an active edge), recovery below 30 inliers, the
+ * Hessian for the next frame's prior (LAST_FRAME: marginalised over the previous frame, Optimizer::Marginalize).  ONE kernel launch
+ * and one wait per call.  One deviation: a failed factorisation ends the round's iterations WITHOUT applying an update (the
+ * reference applies an undefined one) and sets solve_failed.  Pinhole mpCamera, mpCamera2 == NULL only.  ORBG_BAD_ARG / ORBG_CAP_EXCEEDED
+ * (n > 4096) are returned before a device is looked for, ORBG_NO_DEVICE where there is none. */
+int pose_inertial_optimize(const pose_inertial_problem* p, pose_inertial_result* r);
+/* TEST AID, not part of the stable interface: the kernel's edge arithmetic, compiled for the host, at the estimates handed in.
+ * J: 30 x 32 row-major, the stacked Jacobian of the non-visual edges (rows: EdgeInertial 9, EdgeGyroRW 3, EdgeAccRW 3, EdgePriorPoseImu
+ * 15; columns: the unknowns, then the error); vis: n x 31, per visual edge the error (3), its chi2, J^T Omega J (21, upper triangle)
+ * and -J^T Omega e (6) without robust weights.  No device needed. */
+int pose_inertial_host_linearize(const pose_inertial_problem* p, double* J, double* vis);
+
+/* The three C.rowRange().colRange().inv(cv::DECOMP_SVD) reads of an IMU::Preintegrated's covariance C (15 x 15, row-major): rows 0-8 with
+ * the symmetrisation and the eigenvalue clamp at 1e-12 of the EdgeInertial constructor (S/G2oTypes.cc:702-714), rows 9-11 and 12-14 as
+ * S/Optimizer.cc:7798-7813 reads them.  The inverses are computed in double and rounded to float where the reference reads .at<float>.
+ * Host code, no device needed. */
+int orbg_imu_information(const float C[225], double info9[81], double infoG[9], double infoA[9]);
+/* The ConstraintPoseImu constructor's conditioning of H, in place (I/G2oTypes.h:712-718): eigenvalues below 1e-12 become 0 ((H + H) / 2
+ * there is H, not a symmetrisation: the lower triangle is what the eigen solver reads).  pose_inertial_result::H of frame t goes through
+ * it into pose_inertial_prior::H of frame t + 1.  Host code, no device needed. */
+int orbg_condition_prior(double H[225]);
+
 /* ---------------------------------------------------------------- streams, hardware queues, host threads
  * Streams.  Every handle enqueues its work on ONE HIP stream.  By default that stream comes from a per-device pool the library
  * creates with its first handle: four hipStreamNonBlocking streams -- L (local BA handles), E0 / E1 (extractor handles,
@@ -1468,6 +1559,7 @@ int lba_set_stream(lba_handle* h, void* hip_stream);
 int orbv_vocab_set_stream(orbv_vocab* v, void* hip_stream);
 int orbd_database_set_stream(orbd_database* d, void* hip_stream);
 int pose_opt_set_stream(int device, void* hip_stream);      /* the calling thread's pose_optimize calls on `device` */
+int pose_inertial_set_stream(int device, void* hip_stream); /* the calling thread's pose_inertial_optimize calls on `device` */
 
 /* ---------------------------------------------------------------- misc */
 const char* orbg_version(void);

@@ -1,0 +1,164 @@
+// Drop-in glue for the per-frame optimiser of an inertial agent: templates over the reference's own types.
+//
+//   int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame *pFrame, bool bRecInit = false)   I/Optimizer.h, S/Optimizer.cc:7603-7996
+//   int Optimizer::PoseInertialOptimizationLastFrame(Frame *pFrame, bool bRecInit = false)      I/Optimizer.h, S/Optimizer.cc:7998-8424
+//
+// Collect what :7659-7815 / :8040-8226 read, call pose_inertial_optimize (include/orbgpu.h), write back what :7949-7993 / :8361-8421
+// write.  Matrices are read through mat_f32(m) (a const float* to row-major data, found by argument-dependent lookup or the cv::Mat
+// overload below) and written through make_mat(m, rows, cols, data).  A ConstraintPoseImu is read through operator() of its members
+// (Eigen) and built by a factory: EigenConstraintFactory calls the reference's constructor, which conditions H itself.
+#ifndef ORBGPU_INERTIAL_HPP_
+#define ORBGPU_INERTIAL_HPP_
+
+#include <cstdint>
+#include <cstring>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "orbgpu.h"
+
+namespace orbgpu {
+namespace inertial {
+
+#ifdef HAVE_OPENCV
+inline const float* mat_f32(const cv::Mat& m) { return m.ptr<float>(0); }
+inline void make_mat(cv::Mat& out, int rows, int cols, const float* data) { out = cv::Mat(rows, cols, CV_32F, const_cast<float*>(data)).clone(); }
+#endif
+
+// the library calls; a test replaces them to look at what the glue hands over
+struct GpuOps {
+  static int optimize(const pose_inertial_problem& p, pose_inertial_result& r) { return pose_inertial_optimize(&p, &r); }
+  static int information(const float* C, double* i9, double* ig, double* ia) { return orbg_imu_information(C, i9, ig, ia); }
+};
+
+#ifdef EIGEN_WORLD_VERSION
+// new ConstraintPoseImu(Rwb, twb, vwb, bg, ba, H) as S/Optimizer.cc:7993, 8419 call it
+struct EigenConstraintFactory {
+  template <class CpiT>
+  static CpiT* make(const pose_inertial_result& r) {
+    Eigen::Matrix3d R; Eigen::Vector3d t, v, bg, ba; Eigen::Matrix<double, 15, 15> H;
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R(i, j) = r.Rwb[3 * i + j]; t(i) = r.twb[i]; v(i) = r.vwb[i]; bg(i) = r.bg[i]; ba(i) = r.ba[i]; }
+    for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) H(i, j) = r.H[15 * i + j];
+    return new CpiT(R, t, v, bg, ba, H);
+  }
+};
+typedef EigenConstraintFactory DefaultConstraintFactory;
+#else
+struct NoConstraintFactory {};
+typedef NoConstraintFactory DefaultConstraintFactory;
+#endif
+
+inline void check(int rc, const char* where) {
+  if (rc != ORBG_OK) throw std::runtime_error(std::string("orbgpu inertial: ") + where + " failed: " + orbg_strerror(rc));
+}
+
+template <class M> inline void read_state_mats(const M& R, const M& t, const M& v, pose_inertial_state* s) {
+  std::memcpy(s->Rwb, mat_f32(R), sizeof(s->Rwb)); std::memcpy(s->twb, mat_f32(t), sizeof(s->twb)); std::memcpy(s->vwb, mat_f32(v), sizeof(s->vwb));
+}
+// VertexPose / Velocity / GyroBias / AccBias of a Frame (S/G2oTypes.cc:73-119, 664-691)
+template <class FrameT> inline void read_frame_state(FrameT* F, pose_inertial_state* s) {
+  read_state_mats(F->GetImuRotation(), F->GetImuPosition(), F->mVw, s);
+  s->bg[0] = F->mImuBias.bwx; s->bg[1] = F->mImuBias.bwy; s->bg[2] = F->mImuBias.bwz;
+  s->ba[0] = F->mImuBias.bax; s->ba[1] = F->mImuBias.bay; s->ba[2] = F->mImuBias.baz;
+}
+// ... of a KeyFrame (S/G2oTypes.cc:27-71, 659-683)
+template <class KeyFrameT> inline void read_keyframe_state(KeyFrameT* K, pose_inertial_state* s) {
+  read_state_mats(K->GetImuRotation(), K->GetImuPosition(), K->GetVelocity(), s);
+  const auto g = K->GetGyroBias(); const auto a = K->GetAccBias();
+  std::memcpy(s->bg, mat_f32(g), sizeof(s->bg)); std::memcpy(s->ba, mat_f32(a), sizeof(s->ba));
+}
+template <class PreT> inline void read_preintegration(const PreT* I, pose_inertial_preint* o) {
+  o->dT = I->dT;
+  std::memcpy(o->dR, mat_f32(I->dR), 36); std::memcpy(o->dV, mat_f32(I->dV), 12); std::memcpy(o->dP, mat_f32(I->dP), 12);
+  std::memcpy(o->JRg, mat_f32(I->JRg), 36); std::memcpy(o->JVg, mat_f32(I->JVg), 36); std::memcpy(o->JVa, mat_f32(I->JVa), 36);
+  std::memcpy(o->JPg, mat_f32(I->JPg), 36); std::memcpy(o->JPa, mat_f32(I->JPa), 36);
+  o->bg[0] = I->b.bwx; o->bg[1] = I->b.bwy; o->bg[2] = I->b.bwz; o->ba[0] = I->b.bax; o->ba[1] = I->b.bay; o->ba[2] = I->b.baz;
+}
+template <class CpiT> inline void read_constraint(const CpiT& c, pose_inertial_prior* o) {
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) o->Rwb[3 * i + j] = c.Rwb(i, j); o->twb[i] = c.twb(i); o->vwb[i] = c.vwb(i); o->bg[i] = c.bg(i); o->ba[i] = c.ba(i); }
+  for (int i = 0; i < 15; i++) for (int j = 0; j < 15; j++) o->H[15 * i + j] = c.H(i, j);
+}
+
+template <class Ops, class Factory, class FrameT>
+int optimize(FrameT* pFrame, bool bRecInit, int form) {
+  if (pFrame->Nleft != -1 || pFrame->mpCamera2) throw std::runtime_error("orbgpu inertial: a two-camera Frame is not supported");
+  const bool last_frame = form == POSE_INERTIAL_LAST_FRAME;
+  typedef typename std::remove_pointer<decltype(pFrame->mpcpi)>::type CpiT;
+  pose_inertial_problem P;
+  std::memset(&P, 0, sizeof(P));
+  P.struct_size = sizeof(P); P.form = form; P.rec_init = bRecInit ? 1 : 0; P.device = 0; P.n_left = -1;
+  // the visual edges (:7659-7764, :8040-8158): one per feature with a map point, mvKeysUn, mvuRight < 0 => monocular
+  const int N = pFrame->N;
+  std::vector<float> Xw, u, v, ur, w; std::vector<uint8_t> close; std::vector<int> featIdx;
+  for (int i = 0; i < N; i++) {
+    auto* pMP = pFrame->mvpMapPoints[i];
+    if (!pMP) continue;
+    pFrame->mvbOutlier[i] = false;
+    const auto& kp = pFrame->mvKeysUn[i];
+    const auto Xm = pMP->GetWorldPos();
+    const float* X = mat_f32(Xm);
+    Xw.insert(Xw.end(), X, X + 3); u.push_back(kp.pt.x); v.push_back(kp.pt.y); ur.push_back(pFrame->mvuRight[i]);
+    w.push_back(pFrame->mvInvLevelSigma2[kp.octave]); close.push_back(pMP->mTrackDepth < 10.f ? 1 : 0); featIdx.push_back(i);
+  }
+  P.n = (int32_t)featIdx.size();
+  P.Xw = Xw.data(); P.u = u.data(); P.v = v.data(); P.ur = ur.data(); P.inv_sigma2 = w.data(); P.close = close.data();
+  P.fx = pFrame->fx; P.fy = pFrame->fy; P.cx = pFrame->cx; P.cy = pFrame->cy; P.bf = pFrame->mbf;
+  std::memcpy(P.Tcb, mat_f32(pFrame->mImuCalib.Tcb), sizeof(P.Tcb));
+  read_frame_state(pFrame, &P.frame);
+  // the other end and its preintegration (:7767-7815, :8163-8212)
+  const auto* pInt = last_frame ? pFrame->mpImuPreintegratedFrame : pFrame->mpImuPreintegrated;
+  if (!pInt) throw std::runtime_error("orbgpu inertial: the Frame has no preintegration");
+  pose_inertial_prior prior;
+  if (last_frame) {
+    auto* pFp = pFrame->mpPrevFrame;
+    if (!pFp) throw std::runtime_error("orbgpu inertial: the Frame has no previous frame");
+    if (!pFp->mpcpi) throw std::runtime_error("orbgpu inertial: pFp->mpcpi does not exist");     // (the reference dereferences NULL at :8217)
+    read_frame_state(pFp, &P.other);
+    read_constraint(*pFp->mpcpi, &prior);
+    P.prior = &prior;
+  } else {
+    if (!pFrame->mpLastKeyFrame) throw std::runtime_error("orbgpu inertial: the Frame has no last keyframe");
+    read_keyframe_state(pFrame->mpLastKeyFrame, &P.other);
+  }
+  read_preintegration(pInt, &P.preint);
+  check(Ops::information(mat_f32(pInt->C), P.info9, P.infoG, P.infoA), "orbg_imu_information");
+  std::vector<uint8_t> outlier(featIdx.size() + 1);
+  pose_inertial_result R;
+  std::memset(&R, 0, sizeof(R));
+  R.struct_size = sizeof(R); R.outlier = outlier.data();
+  check(Ops::optimize(P, R), last_frame ? "PoseInertialOptimizationLastFrame" : "PoseInertialOptimizationLastKeyFrame");
+  // write back (:7949-7993, :8361-8421)
+  for (size_t k = 0; k < featIdx.size(); k++) pFrame->mvbOutlier[featIdx[k]] = outlier[k] != 0;
+  float Rf[9], tf[3], vf[3];
+  for (int i = 0; i < 9; i++) Rf[i] = (float)R.Rwb[i];
+  for (int i = 0; i < 3; i++) { tf[i] = (float)R.twb[i]; vf[i] = (float)R.vwb[i]; }
+  typename std::decay<decltype(pFrame->mVw)>::type mR, mt, mv;
+  make_mat(mR, 3, 3, Rf); make_mat(mt, 3, 1, tf); make_mat(mv, 3, 1, vf);
+  pFrame->SetImuPoseVelocity(mR, mt, mv);
+  typedef typename std::decay<decltype(pFrame->mImuBias)>::type BiasT;
+  pFrame->mImuBias = BiasT((float)R.ba[0], (float)R.ba[1], (float)R.ba[2], (float)R.bg[0], (float)R.bg[1], (float)R.bg[2]);   // IMU::Bias takes (ba, bg)
+  pFrame->mpcpi = Factory::template make<CpiT>(R);
+  if (last_frame) {
+    auto* pFp = pFrame->mpPrevFrame;
+    delete pFp->mpcpi;
+    pFp->mpcpi = nullptr;
+  }
+  return R.n_inliers;
+}
+
+}  // namespace inertial
+
+template <class Ops = inertial::GpuOps, class Factory = inertial::DefaultConstraintFactory, class FrameT>
+int PoseInertialOptimizationLastKeyFrame(FrameT* pFrame, bool bRecInit = false) {
+  return inertial::optimize<Ops, Factory>(pFrame, bRecInit, POSE_INERTIAL_LAST_KEYFRAME);
+}
+template <class Ops = inertial::GpuOps, class Factory = inertial::DefaultConstraintFactory, class FrameT>
+int PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit = false) {
+  return inertial::optimize<Ops, Factory>(pFrame, bRecInit, POSE_INERTIAL_LAST_FRAME);
+}
+
+}  // namespace orbgpu
+
+#endif  // ORBGPU_INERTIAL_HPP_

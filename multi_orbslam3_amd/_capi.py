@@ -194,6 +194,38 @@ class PoseOptProblem(C.Structure):
                 ("bf", C.c_float), ("Tcw", C.c_float * 16), ("device", C.c_int32), ("rig", C.POINTER(CameraRig))]
 
 
+class PoseInertialState(C.Structure):
+    _fields_ = [("Rwb", C.c_float * 9), ("twb", C.c_float * 3), ("vwb", C.c_float * 3), ("bg", C.c_float * 3), ("ba", C.c_float * 3)]
+
+
+class PoseInertialPreint(C.Structure):
+    _fields_ = [("dT", C.c_float), ("dR", C.c_float * 9), ("dV", C.c_float * 3), ("dP", C.c_float * 3), ("JRg", C.c_float * 9),
+                ("JVg", C.c_float * 9), ("JVa", C.c_float * 9), ("JPg", C.c_float * 9), ("JPa", C.c_float * 9), ("bg", C.c_float * 3),
+                ("ba", C.c_float * 3)]
+
+
+class PoseInertialPrior(C.Structure):
+    _fields_ = [("Rwb", C.c_double * 9), ("twb", C.c_double * 3), ("vwb", C.c_double * 3), ("bg", C.c_double * 3), ("ba", C.c_double * 3),
+                ("H", C.c_double * 225)]
+
+
+class PoseInertialProblem(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("form", C.c_int32), ("rec_init", C.c_int32), ("device", C.c_int32), ("n_left", C.c_int32),
+                ("n", C.c_int32), ("Xw", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("ur", C.c_void_p), ("inv_sigma2", C.c_void_p),
+                ("close", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("Tcb", C.c_float * 12), ("frame", PoseInertialState), ("other", PoseInertialState), ("preint", PoseInertialPreint),
+                ("info9", C.c_double * 81), ("infoG", C.c_double * 9), ("infoA", C.c_double * 9), ("prior", C.POINTER(PoseInertialPrior))]
+
+
+class PoseInertialResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_inliers", C.c_int32), ("n_bad", C.c_int32), ("rounds_run", C.c_int32),
+                ("solve_failed", C.c_int32), ("outlier", C.c_void_p), ("Rwb", C.c_double * 9), ("twb", C.c_double * 3),
+                ("vwb", C.c_double * 3), ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("chi2", C.c_double * 4), ("H", C.c_double * 225)]
+
+
+POSE_INERTIAL_LAST_KEYFRAME, POSE_INERTIAL_LAST_FRAME = 0, 1
+
+
 class DatabaseView(C.Structure):
     _fields_ = [("n_kfs", C.c_int32), ("n_words", C.c_int32), ("inv_start", C.c_void_p), ("inv_kf", C.c_void_p),
                 ("bow_start", C.c_void_p), ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("covis_start", C.c_void_p),
@@ -386,6 +418,7 @@ EXPORTED_SYMBOLS = [
     "orbm_create_new_points", "orbm_search_for_triangulation", "orbm_fuse", "orbm_search_for_initialization",
     "orbg_version", "orbg_strerror", "orbg_device_count", "orbx_get_timings", "orbx_event_overhead", "orbx_set_profile_interval", "orbx_set_profile_kernel", "orbx_get_fast_kernel_stats", "orbx_set_profiling",
     "orbx_get_host_redo_count",
+    "pose_inertial_optimize", "pose_inertial_host_linearize", "pose_inertial_set_stream", "orbg_imu_information", "orbg_condition_prior",
 ]
 
 # The initialisers (prefix orbi_): a list of its own, because tests/test_capi_cpu.py holds EXPORTED_SYMBOLS against the header's
@@ -455,6 +488,11 @@ def load():
     lib.orbx_frame_rgbd_wait.argtypes = [C.c_void_p, C.c_void_p]
     lib.orbx_depth_at_points.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+    lib.pose_inertial_optimize.argtypes = [C.c_void_p, C.c_void_p]
+    lib.pose_inertial_host_linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.pose_inertial_set_stream.argtypes = [C.c_int, C.c_void_p]
+    lib.orbg_imu_information.argtypes = [C.c_void_p] * 4
+    lib.orbg_condition_prior.argtypes = [C.c_void_p]
     lib.eg_solve.argtypes = [C.c_void_p, C.c_void_p]
     lib.eg_set_profiling.argtypes = [C.c_int]
     lib.eg_get_phase_ms.argtypes = [C.c_void_p]

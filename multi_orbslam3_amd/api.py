@@ -956,6 +956,28 @@ class Optimizer:
         capi.check(self.lib.pose_optimize(C.byref(problem), C.byref(out.c)), "pose_optimize")
         return out
 
+    def PoseInertialOptimization(self, problem):
+        """int Optimizer::PoseInertialOptimizationLastKeyFrame / LastFrame(Frame*, bool) (S/Optimizer.cc:7603-8424), as problem.form says;
+        problem: views.pose_inertial_problem(...)[0].  Returns a views.PoseInertialOutput."""
+        out = views.PoseInertialOutput(problem.n)
+        capi.check(self.lib.pose_inertial_optimize(C.byref(problem), C.byref(out.c)), "pose_inertial_optimize")
+        return out
+
+    pose_inertial_optimize = PoseInertialOptimization
+
+    def imu_information(self, C15):
+        """info9, infoG, infoA of an IMU::Preintegrated's covariance C (15 x 15 float), as the edges hold them (orbg_imu_information)."""
+        Cf = np.ascontiguousarray(np.asarray(C15, np.float32).reshape(225))
+        i9, ig, ia = np.zeros(81), np.zeros(9), np.zeros(9)
+        capi.check(self.lib.orbg_imu_information(Cf.ctypes.data, i9.ctypes.data, ig.ctypes.data, ia.ctypes.data), "orbg_imu_information")
+        return i9.reshape(9, 9), ig.reshape(3, 3), ia.reshape(3, 3)
+
+    def condition_prior(self, H):
+        """the ConstraintPoseImu constructor's conditioning of a 15 x 15 H (orbg_condition_prior); returns a new array."""
+        Hc = np.ascontiguousarray(np.asarray(H, np.float64).reshape(225)).copy()
+        capi.check(self.lib.orbg_condition_prior(Hc.ctypes.data), "orbg_condition_prior")
+        return Hc.reshape(15, 15)
+
     def LocalBundleAdjustment(self, problem, pbStopFlag=None, trace_cap=64, out=None):
         """problem: views.lba_problem(...)[0]; pbStopFlag: np.bool_[1] (the reference's bool) or np.int32[1], polled between LM
         iterations / trials.

@@ -26,31 +26,10 @@ namespace {
 constexpr int kPoThreads = 256;
 constexpr int kPoMaxPer = 16;      // correspondences per thread (n <= 4096)
 constexpr int kPoPinnedN = 1024;   // up to here the kernel reads its inputs from the pinned staging block, beyond from a device copy
-constexpr int kPoRow = 8 * 33;     // one reduction row: 8 segments of 32 values, padded against LDS bank conflicts
-
-// Block-wide sums of NV per-thread values in a fixed order: transpose through LDS, 8 threads per value add 32
-// entries each, one thread per value adds the 8 partials.  out[0..NV) is valid for every thread afterwards.
+// Block-wide sums of NV per-thread values in a fixed order: lm_block.hpp (shared with pose_inertial.hip)
 template <int NV>
-__device__ inline void po_block_reduce(const double* vals, double* s_acc, double* s_part, double* out) {
-  const int tid = threadIdx.x;
-  const int col = (tid >> 5) * 33 + (tid & 31);
-#pragma unroll
-  for (int v = 0; v < NV; v++) s_acc[v * kPoRow + col] = vals[v];
-  __syncthreads();
-  if (tid < NV * 8) {
-    const double* p = s_acc + (tid >> 3) * kPoRow + (tid & 7) * 33;
-    double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) { a0 += p[4 * j]; a1 += p[4 * j + 1]; a2 += p[4 * j + 2]; a3 += p[4 * j + 3]; }
-    s_part[tid] = (a0 + a1) + (a2 + a3);
-  }
-  __syncthreads();
-  if (tid < NV) {
-    const double* p = s_part + tid * 8;
-    out[tid] = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));
-  }
-  __syncthreads();
-}
+__device__ inline void po_block_reduce(const double* vals, double* s_acc, double* s_part, double* out) { lm_block_reduce<NV>(vals, s_acc, s_part, out); }
+constexpr int kPoRow = kLmRow;
 
 // ---- two correspondences side by side.  A lone wavefront issues a DEPENDENT FP64 instruction every ~9 cycles and an independent
 // one every ~5.4 (tools/micro/fp64_latency; the pipe itself takes one per 4.2), and hipcc keeps the arithmetic of one

@@ -350,6 +350,63 @@ class PoseOptOutput:
         return self.outlier[: self.n].copy()
 
 
+def _fill(dst, src, dtype):
+    a = np.asarray(src, dtype).reshape(-1)
+    assert len(a) == len(dst), (len(a), len(dst))
+    for i, x in enumerate(a):
+        dst[i] = float(x)
+
+
+def pose_inertial_problem(form, Xw, u, v, ur, inv_sigma2, close, cam, Tcb, frame, other, preint, info9, infoG, infoA, prior=None,
+                          rec_init=False, device=0, n_left=-1):
+    """pose_inertial_problem of include/orbgpu.h.  form: capi.POSE_INERTIAL_LAST_KEYFRAME / _LAST_FRAME; cam = (fx, fy, cx, cy, bf); Tcb:
+    mImuCalib.Tcb (3 x 4 or 4 x 4); frame / other: dicts Rwb, twb, vwb, bg, ba; preint: dict dT, dR, dV, dP, JRg, JVg, JVa, JPg, JPa, bg, ba;
+    info9 / infoG / infoA: orbg_imu_information(C); prior (LAST_FRAME): dict Rwb, twb, vwb, bg, ba, H (15 x 15, conditioned).
+    Returns (problem, keep-alive list)."""
+    arrs = [_c(np.asarray(Xw, np.float32).reshape(-1, 3), np.float32), _c(u, np.float32), _c(v, np.float32), _c(ur, np.float32),
+            _c(inv_sigma2, np.float32), _c(close, np.uint8)]
+    p = capi.PoseInertialProblem()
+    p.struct_size = C.sizeof(capi.PoseInertialProblem)
+    p.form, p.rec_init, p.device, p.n_left = int(form), int(bool(rec_init)), int(device), int(n_left)
+    p.n = len(arrs[1])
+    p.Xw, p.u, p.v, p.ur, p.inv_sigma2, p.close = [capi.ptr(a) for a in arrs]
+    p.fx, p.fy, p.cx, p.cy, p.bf = [float(c) for c in cam]
+    _fill(p.Tcb, np.asarray(Tcb, np.float32)[:3, :4], np.float32)
+    for dst, src in ((p.frame, frame), (p.other, other)):
+        for k in ("Rwb", "twb", "vwb", "bg", "ba"):
+            _fill(getattr(dst, k), src[k], np.float32)
+    p.preint.dT = float(preint["dT"])
+    for k in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "bg", "ba"):
+        _fill(getattr(p.preint, k), preint[k], np.float32)
+    _fill(p.info9, info9, np.float64)
+    _fill(p.infoG, infoG, np.float64)
+    _fill(p.infoA, infoA, np.float64)
+    if prior is not None:
+        c = capi.PoseInertialPrior()
+        for k in ("Rwb", "twb", "vwb", "bg", "ba", "H"):
+            _fill(getattr(c, k), prior[k], np.float64)
+        p.prior = C.pointer(c)
+        arrs.append(c)
+    return p, arrs
+
+
+class PoseInertialOutput:
+    def __init__(self, n):
+        self.outlier = np.zeros(max(n, 1), np.uint8)
+        self.c = capi.PoseInertialResult()
+        self.c.struct_size = C.sizeof(capi.PoseInertialResult)
+        self.c.outlier = capi.ptr(self.outlier)
+        self.n = n
+
+    def as_dict(self):
+        """the result in the layout of the numpy model (tests/pose_inertial_model.py)"""
+        c = self.c
+        return {"Rwb": np.array(list(c.Rwb)).reshape(3, 3), "twb": np.array(list(c.twb)), "vwb": np.array(list(c.vwb)),
+                "bg": np.array(list(c.bg)), "ba": np.array(list(c.ba)), "outlier": self.outlier[: self.n].copy(),
+                "n_inliers": c.n_inliers, "n_bad": c.n_bad, "rounds_run": c.rounds_run, "solve_failed": c.solve_failed,
+                "chi2": list(c.chi2), "H": np.array(list(c.H)).reshape(15, 15)}
+
+
 def database_view(inverted_file, bow_vectors, covisible, map_id, bad, map_bad, n_words):
     """orbd_database_view (KeyFrameDatabase flattened, S/KeyFrameDatabase.cc:594-761): inverted_file = {word: [kf, ...]} in
     insertion order, bow_vectors[kf] = (words ascending, values), covisible[kf] = GetBestCovisibilityKeyFrames(10) as indices."""
