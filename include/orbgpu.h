@@ -1518,6 +1518,82 @@ int orbg_imu_information(const float C[225], double info9[81], double infoG[9], 
  * it into pose_inertial_prior::H of frame t + 1.  Host code, no device needed. */
 int orbg_condition_prior(double H[225]);
 
+/* ---------------------------------------------------------------- local inertial BA (the per-keyframe optimiser of an inertial agent)
+ *
+ * Optimizer::LocalInertialBA (S/Optimizer.cc:4556-5226), what LocalMapping::Run calls instead of LocalBundleAdjustment once the IMU is
+ * initialised (S/LocalMapping.cc:213-248).  The caller flattens the graph the reference builds: the window's keyframes (free), the
+ * keyframe in front of it (fixed, with its velocity and biases) and the fixed keyframes that observe the local points, all in one list. */
+#define INERTIAL_BA_MAX_FREE_KEYFRAMES 32      /* the reference's window holds at most 25 */
+#define INERTIAL_BA_MAX_EDGES (1 << 22)
+
+typedef struct inertial_ba_keyframe {
+  pose_inertial_state state;   /* VertexPose / VertexVelocity / VertexGyroBias / VertexAccBias of pKFi (velocity and biases unread when !imu) */
+  int32_t fixed;               /* setFixed(true): the keyframe in front of the window, the other observers of the local points */
+  int32_t imu;                 /* pKFi->bImu: velocity and bias vertices exist (15 unknowns when free, else 6) */
+  int32_t link;                /* EdgeInertial + EdgeGyroRW + EdgeAccRW from keyframe `prev` to this one exist (:4791: both bImu, a preintegration) */
+  int32_t prev;                /* index of pKFi->mPrevKF in the list (read when link) */
+  int32_t last_in_window;      /* i == N - 1: the edge to the fixed keyframe, information * 1e-2 and a Huber kernel (:4826-4837) */
+  pose_inertial_preint preint; /* pKFi->mpImuPreintegrated (read when link) */
+  double info9[81];            /* orbg_imu_information(pKFi->mpImuPreintegrated->C): EdgeInertial's, EdgeGyroRW's, EdgeAccRW's */
+  double infoG[9];
+  double infoA[9];
+} inertial_ba_keyframe;
+
+typedef struct inertial_ba_problem {
+  uint32_t struct_size;        /* sizeof(inertial_ba_problem) */
+  int32_t n_keyframes, n_points, n_edges;
+  const inertial_ba_keyframe* keyframes;
+  const float* points;         /* n_points x 3, pMP->GetWorldPos() */
+  const lba_edge* edges;       /* EdgeMono / EdgeStereo in creation order (per point, its observations: `point` never decreases);
+                                  pose = index into keyframes[]; inv_sigma2 = mvInvLevelSigma2[octave] (Pinhole::uncertainty2 is 1) */
+  const uint8_t* close;        /* n_points, pMP->mTrackDepth < 10.f */
+  int32_t rec_init;            /* bRecInit: a Huber kernel on every EdgeInertial */
+  int32_t large;               /* bLarge: lambda 1e-2 and 4 iterations instead of 1e0 and 10; never `failed` */
+  float fx, fy, cx, cy, bf;    /* the pinhole mpCamera; mpCamera2 == NULL */
+  float Tcb[12];               /* mImuCalib.Tcb, rows 0-2 (row-major 3 x 4) */
+  int32_t device;
+} inertial_ba_problem;
+
+typedef struct inertial_ba_state { double Rwb[9], twb[3], vwb[3], bg[3], ba[3]; } inertial_ba_state;
+
+typedef struct inertial_ba_result {
+  uint32_t struct_size;        /* sizeof(inertial_ba_result) */
+  inertial_ba_state* states;   /* n_keyframes (caller-allocated), the final estimates; fixed keyframes unchanged */
+  float*   points;             /* n_points x 3 (caller-allocated) */
+  double*  edge_chi2;          /* n_edges or NULL: e->chi2() after optimize() -- of the LAST evaluation, a rejected trial's if the run ended on one */
+  uint8_t* edge_depth_pos;     /* n_edges or NULL: e->isDepthPositive() at the final estimate */
+  uint8_t* edge_outlier;       /* n_edges or NULL: the erase predicates of :5097 / :5114 */
+  int32_t  n_outliers;
+  int32_t  failed;             /* (2 * err < err_end || isnan(err) || isnan(err_end)) && !bLarge on the FLOAT err / err_end (:5128) */
+  int32_t  iters;              /* LM iterations run */
+  double   chi2_initial;       /* err: activeRobustChi2() in front of optimize() */
+  double   chi2_final;         /* err_end: activeRobustChi2() after it (the errors of the last evaluation) */
+  double*  trace;              /* optional, trace_cap x 3 as ba_result's: lambda, chi2 and the trials of every iteration */
+  int32_t  trace_cap, trace_len;
+} inertial_ba_result;
+
+typedef struct inertial_ba_handle inertial_ba_handle;
+
+/* The numerical core of Optimizer::LocalInertialBA: computeActiveErrors(), ONE optimize(bLarge ? 4 : 10) of g2o's Levenberg-Marquardt
+ * (user lambda 1e0 / 1e-2) with the map points marginalised, the verdicts.  No abort flag: the reference sets it after optimize().
+ * Refused before a device is looked for: ORBG_BAD_ARG (a NULL array, struct_size, an index out of range, an edge list that is not
+ * grouped per point, two edges of one keyframe and point, ur == LBA_UR_RIGHT_CAMERA, a link on a fixed keyframe or between keyframes
+ * without imu, no free keyframe), ORBG_CAP_EXCEEDED (more than INERTIAL_BA_MAX_FREE_KEYFRAMES free keyframes or INERTIAL_BA_MAX_EDGES
+ * edges).  Two solves of the same problem return the same bits. */
+int inertial_ba_solve(const inertial_ba_problem* p, inertial_ba_result* r);
+/* ... with a handle that keeps the device buffers, the solver object and the stream between calls (one solve at a time per handle). */
+int inertial_ba_create(int device, inertial_ba_handle** out);
+int inertial_ba_destroy(inertial_ba_handle* h);
+int inertial_ba_solve_h(inertial_ba_handle* h, const inertial_ba_problem* p, inertial_ba_result* r);
+int inertial_ba_set_stream(inertial_ba_handle* h, void* hip_stream);   /* as lba_set_stream */
+int inertial_ba_set_profiling(inertial_ba_handle* h, int on);          /* as ba_set_profiling */
+int inertial_ba_get_phase_ms(inertial_ba_handle* h, double* ms /*5: structure, linearise, Schur, LDL^T, update*/);
+/* TEST AID, not part of the stable interface: the kernels' edge arithmetic, compiled for the host, at the estimates handed in.
+ * vis: n_edges x 31, per visual edge the error (3, third 0 for EdgeMono), its chi2, the point Jacobian (3 x 3) and the pose Jacobian
+ * (3 x 6), row-major; inertial: per keyframe with link, in list order, the stacked 15 x 32 Jacobian of EdgeInertial (rows 0-8), EdgeGyroRW
+ * (9-11) and EdgeAccRW (12-14) -- columns: keyframe prev's 15, this keyframe's 15, the error in column 30.  No device needed. */
+int inertial_ba_host_linearize(const inertial_ba_problem* p, double* vis, double* inertial);
+
 /* ---------------------------------------------------------------- streams, hardware queues, host threads
  * Streams.  Every handle enqueues its work on ONE HIP stream.  By default that stream comes from a per-device pool the library
  * creates with its first handle: four hipStreamNonBlocking streams -- L (local BA handles), E0 / E1 (extractor handles,

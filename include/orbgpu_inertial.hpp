@@ -1,7 +1,8 @@
-// Drop-in glue for the per-frame optimiser of an inertial agent: templates over the reference's own types.
+// Drop-in glue for the optimisers of an inertial agent (INTEGRATION.md sections 3n, 3o): templates over the reference's own types.
 //
 //   int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame *pFrame, bool bRecInit = false)   I/Optimizer.h, S/Optimizer.cc:7603-7996
 //   int Optimizer::PoseInertialOptimizationLastFrame(Frame *pFrame, bool bRecInit = false)      I/Optimizer.h, S/Optimizer.cc:7998-8424
+//   void Optimizer::LocalInertialBA(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, bool bLarge, bool bRecInit)   S/Optimizer.cc:4556-5226
 //
 // Collect what :7659-7815 / :8040-8226 read, call pose_inertial_optimize (include/orbgpu.h), write back what :7949-7993 / :8361-8421
 // write.  Matrices are read through mat_f32(m) (a const float* to row-major data, found by argument-dependent lookup or the cv::Mat
@@ -12,9 +13,15 @@
 
 #include <cstdint>
 #include <cstring>
+#include <algorithm>
+#include <list>
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "orbgpu.h"
@@ -157,6 +164,193 @@ int PoseInertialOptimizationLastKeyFrame(FrameT* pFrame, bool bRecInit = false) 
 template <class Ops = inertial::GpuOps, class Factory = inertial::DefaultConstraintFactory, class FrameT>
 int PoseInertialOptimizationLastFrame(FrameT* pFrame, bool bRecInit = false) {
   return inertial::optimize<Ops, Factory>(pFrame, bRecInit, POSE_INERTIAL_LAST_FRAME);
+}
+
+// ---------------------------------------------------------------------------------------------- LocalInertialBA
+namespace inertial {
+
+// the library calls of the local inertial BA; a test replaces them to look at what the glue hands over and to force the fail return
+struct LibaGpuOps {
+  static int solve(const inertial_ba_problem& p, inertial_ba_result& r) { return inertial_ba_solve(&p, &r); }
+  static int information(const float* C, double* i9, double* ig, double* ia) { return orbg_imu_information(C, i9, ig, ia); }
+};
+
+// VertexPose of a KeyFrame (S/G2oTypes.cc:27-71), and with bImu its velocity and biases (:659-683)
+template <class KeyFrameT> inline void read_liba_state(KeyFrameT* K, pose_inertial_state* s) {
+  std::memset(s, 0, sizeof(*s));
+  const auto R = K->GetImuRotation(); const auto t = K->GetImuPosition();
+  std::memcpy(s->Rwb, mat_f32(R), sizeof(s->Rwb)); std::memcpy(s->twb, mat_f32(t), sizeof(s->twb));
+  if (!K->bImu) return;
+  const auto v = K->GetVelocity(); const auto g = K->GetGyroBias(); const auto a = K->GetAccBias();
+  std::memcpy(s->vwb, mat_f32(v), sizeof(s->vwb)); std::memcpy(s->bg, mat_f32(g), sizeof(s->bg)); std::memcpy(s->ba, mat_f32(a), sizeof(s->ba));
+}
+
+}  // namespace inertial
+
+// The window, the stamps, the point list and the fixed list in the reference's order, the SetNewBias side effect, inertial_ba_solve,
+// the erase list (mono edges first, then stereo), the lock, the fail return with its un-reset stamps, the write-back in the
+// reference's order.  pbStopFlag is accepted and not read: the reference hands it to the optimizer after optimize() has returned
+// (:5077).  A keyframe with mpCamera2 throws (EdgeMono(1) is not part of inertial_ba_solve).
+template <class Ops = inertial::LibaGpuOps, class KeyFrameT, class MapT>
+void LocalInertialBA(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, bool bLarge = false, bool bRecInit = false) {
+  using namespace inertial;
+  (void)pbStopFlag;
+  auto* pCurrentMap = pKF->GetMap();
+  const int maxOpt = bLarge ? 25 : 10;
+  const int Nd = std::min((int)pCurrentMap->KeyFramesInMap() - 2, maxOpt);
+  typedef typename std::remove_pointer<typename std::decay<decltype(pKF->GetMapPointMatches())>::type::value_type>::type MapPointT;
+  // the window (:4571-4587)
+  std::vector<KeyFrameT*> vpOptimizableKFs;
+  vpOptimizableKFs.push_back(pKF);
+  pKF->mnBALocalForKF = pKF->mnId;
+  for (int i = 1; i < Nd; i++) {
+    if (!vpOptimizableKFs.back()->mPrevKF) break;
+    vpOptimizableKFs.push_back(vpOptimizableKFs.back()->mPrevKF);
+    vpOptimizableKFs.back()->mnBALocalForKF = pKF->mnId;
+  }
+  int N = (int)vpOptimizableKFs.size();
+  // the points its keyframes see (:4592-4607)
+  std::vector<MapPointT*> lLocalMapPoints;
+  for (int i = 0; i < N; i++) {
+    const auto vpMPs = vpOptimizableKFs[i]->GetMapPointMatches();
+    for (MapPointT* pMP : vpMPs)
+      if (pMP && !pMP->isBad() && pMP->mnBALocalForKF != pKF->mnId) { lLocalMapPoints.push_back(pMP); pMP->mnBALocalForKF = pKF->mnId; }
+  }
+  // the fixed keyframe in front of the window -- or the oldest one itself, popped (:4610-4622)
+  std::list<KeyFrameT*> lFixedKeyFrames;
+  if (vpOptimizableKFs.back()->mPrevKF) {
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back()->mPrevKF);
+    vpOptimizableKFs.back()->mPrevKF->mnBAFixedForKF = pKF->mnId;
+  } else {
+    vpOptimizableKFs.back()->mnBALocalForKF = 0;
+    vpOptimizableKFs.back()->mnBAFixedForKF = pKF->mnId;
+    lFixedKeyFrames.push_back(vpOptimizableKFs.back());
+    vpOptimizableKFs.pop_back();
+  }
+  // (maxCovKF = 0: the loop of :4626-4654 leaves at its first test)
+  // the other observers of the local points, one per point at most, up to 200 keyframes in all (:4657-4678)
+  const size_t maxFixKF = 200;
+  for (MapPointT* pMP : lLocalMapPoints) {
+    const auto observations = pMP->GetObservations();
+    for (const auto& ob : observations) {
+      KeyFrameT* pKFi = ob.first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+        pKFi->mnBAFixedForKF = pKF->mnId;
+        if (!pKFi->isBad()) { lFixedKeyFrames.push_back(pKFi); break; }
+      }
+    }
+    if (lFixedKeyFrames.size() >= maxFixKF) break;
+  }
+  // the vertices (:4704-4775): the window first, then the fixed list
+  N = (int)vpOptimizableKFs.size();
+  std::vector<KeyFrameT*> all(vpOptimizableKFs.begin(), vpOptimizableKFs.end());
+  all.insert(all.end(), lFixedKeyFrames.begin(), lFixedKeyFrames.end());
+  std::map<KeyFrameT*, int> index;
+  std::vector<inertial_ba_keyframe> kfs(all.size());
+  for (size_t i = 0; i < all.size(); i++) {
+    std::memset(&kfs[i], 0, sizeof(kfs[i]));
+    read_liba_state(all[i], &kfs[i].state);
+    kfs[i].fixed = (int)i >= N ? 1 : 0; kfs[i].imu = all[i]->bImu ? 1 : 0; kfs[i].prev = -1;
+    index[all[i]] = (int)i;
+  }
+  // the inertial edges (:4782-4867)
+  for (int i = 0; i < N; i++) {
+    KeyFrameT* pKFi = vpOptimizableKFs[i];
+    if (!pKFi->mPrevKF) continue;
+    if (!(pKFi->bImu && pKFi->mPrevKF->bImu && pKFi->mpImuPreintegrated)) continue;
+    pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());
+    const auto it = index.find(pKFi->mPrevKF);
+    if (it == index.end()) continue;                              // (:4811: a vertex is missing)
+    inertial_ba_keyframe& k = kfs[i];
+    k.link = 1; k.prev = it->second; k.last_in_window = i == N - 1 ? 1 : 0;
+    read_preintegration(pKFi->mpImuPreintegrated, &k.preint);
+    check(Ops::information(mat_f32(pKFi->mpImuPreintegrated->C), k.info9, k.infoG, k.infoA), "orbg_imu_information");
+  }
+  // the points and their edges (:4914-5059)
+  std::vector<float> points; std::vector<uint8_t> close; std::vector<lba_edge> edges;
+  std::vector<KeyFrameT*> vpEdgeKF; std::vector<MapPointT*> vpMapPointEdge;
+  for (MapPointT* pMP : lLocalMapPoints) {
+    const auto Xm = pMP->GetWorldPos();
+    const float* X = mat_f32(Xm);
+    const int l = (int)close.size();
+    points.insert(points.end(), X, X + 3);
+    close.push_back(pMP->mTrackDepth < 10.f ? 1 : 0);
+    const auto observations = pMP->GetObservations();
+    for (const auto& ob : observations) {
+      KeyFrameT* pKFi = ob.first;
+      if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) continue;
+      if (pKFi->isBad() || pKFi->GetMap() != pCurrentMap) continue;
+      if (pKFi->mpCamera2) throw std::runtime_error("orbgpu inertial: a two-camera KeyFrame is not supported");
+      const int leftIndex = std::get<0>(ob.second);
+      if (leftIndex == -1) continue;
+      const auto& kpUn = pKFi->mvKeysUn[leftIndex];
+      lba_edge e;
+      e.pose = index.at(pKFi); e.point = l; e.u = kpUn.pt.x; e.v = kpUn.pt.y;
+      e.ur = pKFi->mvuRight[leftIndex] < 0 ? -1.f : pKFi->mvuRight[leftIndex];
+      e.inv_sigma2 = pKFi->mvInvLevelSigma2[kpUn.octave];          // (Pinhole::uncertainty2 is 1)
+      edges.push_back(e); vpEdgeKF.push_back(pKFi); vpMapPointEdge.push_back(pMP);
+    }
+  }
+  inertial_ba_problem P;
+  std::memset(&P, 0, sizeof(P));
+  P.struct_size = sizeof(P); P.n_keyframes = (int32_t)kfs.size(); P.n_points = (int32_t)close.size(); P.n_edges = (int32_t)edges.size();
+  P.keyframes = kfs.data(); P.points = points.data(); P.edges = edges.data(); P.close = close.data();
+  P.rec_init = bRecInit ? 1 : 0; P.large = bLarge ? 1 : 0; P.device = 0;
+  P.fx = pKF->fx; P.fy = pKF->fy; P.cx = pKF->cx; P.cy = pKF->cy; P.bf = pKF->mbf;
+  std::memcpy(P.Tcb, mat_f32(pKF->mImuCalib.Tcb), sizeof(P.Tcb));
+  std::vector<inertial_ba_state> states(kfs.size());
+  std::vector<float> new_points(points.size() + 1);
+  std::vector<uint8_t> outlier(edges.size() + 1);
+  inertial_ba_result R;
+  std::memset(&R, 0, sizeof(R));
+  R.struct_size = sizeof(R); R.states = states.data(); R.points = new_points.data(); R.edge_outlier = outlier.data();
+  check(Ops::solve(P, R), "LocalInertialBA");
+  // the erase list (:5083-5119): the mono edges in their order, then the stereo edges
+  std::vector<std::pair<KeyFrameT*, MapPointT*> > vToErase;
+  for (int stereo = 0; stereo < 2; stereo++)
+    for (size_t k = 0; k < edges.size(); k++) {
+      if ((edges[k].ur < 0) == (stereo == 1) || vpMapPointEdge[k]->isBad()) continue;
+      if (outlier[k]) vToErase.push_back(std::make_pair(vpEdgeKF[k], vpMapPointEdge[k]));
+    }
+  std::unique_lock<typename std::decay<decltype(pMap->mMutexMapUpdate)>::type> lock(pMap->mMutexMapUpdate);
+  if (R.failed) return;                                           // (:5128-5132: the stamps stay as they are, nothing is written)
+  for (auto& er : vToErase) { er.first->EraseMapPointMatch(er.second); er.second->EraseObservation(er.first); }
+  for (KeyFrameT* pKFi : lFixedKeyFrames) pKFi->mnBAFixedForKF = 0;
+  // write-back (:5157-5213)
+  typedef typename std::decay<decltype(pKF->GetImuBias())>::type BiasT;
+  typedef typename std::decay<decltype(pKF->GetVelocity())>::type MatT;
+  const float* Tcb = P.Tcb;
+  for (int i = 0; i < N; i++) {
+    KeyFrameT* pKFi = vpOptimizableKFs[i];
+    const inertial_ba_state& s = states[i];
+    if (pKFi->bImu) {
+      const float vf[3] = {(float)s.vwb[0], (float)s.vwb[1], (float)s.vwb[2]};
+      MatT mv;
+      make_mat(mv, 3, 1, vf);
+      pKFi->SetVelocity(mv);
+      pKFi->SetNewBias(BiasT((float)s.ba[0], (float)s.ba[1], (float)s.ba[2], (float)s.bg[0], (float)s.bg[1], (float)s.bg[2]));   // IMU::Bias takes (ba, bg)
+    }
+    // Rcw = Rcb Rwb^T, tcw = Rcb (-Rwb^T twb) + tcb in double (ImuCamPose), then Converter::toCvSE3: floats
+    double Rcb[9], tcb[3], tbw[3];
+    for (int a = 0; a < 3; a++) { for (int c = 0; c < 3; c++) Rcb[3 * a + c] = Tcb[4 * a + c]; tcb[a] = Tcb[4 * a + 3]; }
+    for (int a = 0; a < 3; a++) tbw[a] = -(s.Rwb[a] * s.twb[0] + s.Rwb[3 + a] * s.twb[1] + s.Rwb[6 + a] * s.twb[2]);
+    float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+    for (int a = 0; a < 3; a++) {
+      for (int c = 0; c < 3; c++) T[4 * a + c] = (float)(Rcb[3 * a] * s.Rwb[3 * c] + Rcb[3 * a + 1] * s.Rwb[3 * c + 1] + Rcb[3 * a + 2] * s.Rwb[3 * c + 2]);
+      T[4 * a + 3] = (float)(Rcb[3 * a] * tbw[0] + Rcb[3 * a + 1] * tbw[1] + Rcb[3 * a + 2] * tbw[2] + tcb[a]);
+    }
+    MatT mT;
+    make_mat(mT, 4, 4, T);
+    pKFi->SetPose(mT, false);
+    pKFi->mnBALocalForKF = 0;
+  }
+  for (size_t l = 0; l < lLocalMapPoints.size(); l++) {
+    MatT mX;
+    make_mat(mX, 3, 1, &new_points[3 * l]);
+    lLocalMapPoints[l]->SetWorldPos(mX, false, false);
+    lLocalMapPoints[l]->UpdateNormalAndDepth();
+  }
+  pMap->IncreaseChangeIndex();
 }
 
 }  // namespace orbgpu

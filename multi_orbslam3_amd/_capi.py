@@ -226,6 +226,34 @@ class PoseInertialResult(C.Structure):
 POSE_INERTIAL_LAST_KEYFRAME, POSE_INERTIAL_LAST_FRAME = 0, 1
 
 
+class InertialBaKeyframe(C.Structure):
+    _fields_ = [("state", PoseInertialState), ("fixed", C.c_int32), ("imu", C.c_int32), ("link", C.c_int32), ("prev", C.c_int32),
+                ("last_in_window", C.c_int32), ("preint", PoseInertialPreint), ("info9", C.c_double * 81), ("infoG", C.c_double * 9),
+                ("infoA", C.c_double * 9)]
+
+
+class InertialBaProblem(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_keyframes", C.c_int32), ("n_points", C.c_int32), ("n_edges", C.c_int32),
+                ("keyframes", C.c_void_p), ("points", C.c_void_p), ("edges", C.c_void_p), ("close", C.c_void_p), ("rec_init", C.c_int32),
+                ("large", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float),
+                ("Tcb", C.c_float * 12), ("device", C.c_int32)]
+
+
+# inertial_ba_state: Rwb (9), twb, vwb, bg, ba (3 each), double
+INERTIAL_BA_STATE_DOUBLES = 21
+
+
+class InertialBaResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("states", C.c_void_p), ("points", C.c_void_p), ("edge_chi2", C.c_void_p),
+                ("edge_depth_pos", C.c_void_p), ("edge_outlier", C.c_void_p), ("n_outliers", C.c_int32), ("failed", C.c_int32),
+                ("iters", C.c_int32), ("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("trace", C.c_void_p),
+                ("trace_cap", C.c_int32), ("trace_len", C.c_int32)]
+
+
+INERTIAL_BA_MAX_FREE_KEYFRAMES = 32
+INERTIAL_BA_MAX_EDGES = 1 << 22
+
+
 class DatabaseView(C.Structure):
     _fields_ = [("n_kfs", C.c_int32), ("n_words", C.c_int32), ("inv_start", C.c_void_p), ("inv_kf", C.c_void_p),
                 ("bow_start", C.c_void_p), ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("covis_start", C.c_void_p),
@@ -430,6 +458,10 @@ FULL_BA_SYMBOLS = ["ba_solve", "ba_solve_b", "ba_create", "ba_destroy", "ba_solv
 # The essential graph (prefix eg_), likewise; tests/test_essential_graph_cpu.py holds it against the header.
 ESSENTIAL_GRAPH_SYMBOLS = ["eg_solve", "eg_set_profiling", "eg_get_phase_ms"]
 
+# The local inertial BA (prefix inertial_ba_), likewise; tests/test_inertial_ba_cpu.py holds it against the header.
+INERTIAL_BA_SYMBOLS = ["inertial_ba_solve", "inertial_ba_create", "inertial_ba_destroy", "inertial_ba_solve_h", "inertial_ba_set_stream",
+                       "inertial_ba_set_profiling", "inertial_ba_get_phase_ms", "inertial_ba_host_linearize"]
+
 # MLPnPsolver (prefix orbp_), likewise; tests/test_mlpnp_cpu.py holds it against the header.
 MLPNP_SYMBOLS = ["orbp_mlpnp_create", "orbp_mlpnp_destroy", "orbp_mlpnp_set_stream", "orbp_mlpnp_set_problem",
                  "orbp_mlpnp_set_ransac_parameters", "orbp_mlpnp_ransac_iterations", "orbp_mlpnp_iterations_of_call",
@@ -493,13 +525,21 @@ def load():
     lib.pose_inertial_set_stream.argtypes = [C.c_int, C.c_void_p]
     lib.orbg_imu_information.argtypes = [C.c_void_p] * 4
     lib.orbg_condition_prior.argtypes = [C.c_void_p]
+    lib.inertial_ba_solve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.inertial_ba_create.argtypes = [C.c_int, C.c_void_p]
+    lib.inertial_ba_destroy.argtypes = [C.c_void_p]
+    lib.inertial_ba_solve_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.inertial_ba_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    lib.inertial_ba_set_profiling.argtypes = [C.c_void_p, C.c_int]
+    lib.inertial_ba_get_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
+    lib.inertial_ba_host_linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.eg_solve.argtypes = [C.c_void_p, C.c_void_p]
     lib.eg_set_profiling.argtypes = [C.c_int]
     lib.eg_get_phase_ms.argtypes = [C.c_void_p]
     lib.orbp_mlpnp_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
     lib.orbp_mlpnp_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
     lib.orbp_mlpnp_gn.argtypes = [C.c_int] + [C.c_void_p] * 6
-    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS + MLPNP_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS + MLPNP_SYMBOLS + INERTIAL_BA_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

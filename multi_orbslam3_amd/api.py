@@ -965,6 +965,19 @@ class Optimizer:
 
     pose_inertial_optimize = PoseInertialOptimization
 
+    def LocalInertialBA(self, problem, handle=None, trace_cap=16):
+        """The numerical core of void Optimizer::LocalInertialBA(KeyFrame*, bool*, Map*, bool bLarge, bool bRecInit)
+        (S/Optimizer.cc:4556-5226); problem: views.inertial_ba_problem(...)[0]; handle: an InertialBA (device buffers, solver and stream
+        kept between calls) or None.  Returns a views.InertialBaOutput: states and points, the verdicts, `failed`."""
+        out = views.InertialBaOutput(problem, trace_cap)
+        if handle is None:
+            capi.check(self.lib.inertial_ba_solve(C.byref(problem), C.byref(out.c)), "inertial_ba_solve")
+        else:
+            capi.check(self.lib.inertial_ba_solve_h(handle.h, C.byref(problem), C.byref(out.c)), "inertial_ba_solve_h")
+        return out
+
+    inertial_ba_solve = LocalInertialBA
+
     def imu_information(self, C15):
         """info9, infoG, infoA of an IMU::Preintegrated's covariance C (15 x 15 float), as the edges hold them (orbg_imu_information)."""
         Cf = np.ascontiguousarray(np.asarray(C15, np.float32).reshape(225))
@@ -1934,3 +1947,35 @@ def Fuse(kfs, points, th=3.0, sim3_form=False, skip=None):
     capi.check(lib.orbm_fuse(C.byref(arr), K, C.byref(view), capi.ptr(skip) if skip is not None and skip.size else None, C.byref(p),
                              capi.ptr(rec) if rec.size else None, capi.ptr(cand) if cand.size else None), "orbm_fuse")
     return rec, cand
+
+
+class InertialBA:
+    """inertial_ba_create / _destroy: the device buffers, the LDL^T solver object and the stream of Optimizer.LocalInertialBA calls."""
+
+    def __init__(self, device=0):
+        self.lib = capi.load()
+        self.h = C.c_void_p()
+        capi.check(self.lib.inertial_ba_create(int(device), C.byref(self.h)), "inertial_ba_create")
+
+    def set_stream(self, hip_stream):
+        capi.check(self.lib.inertial_ba_set_stream(self.h, C.c_void_p(hip_stream) if hip_stream else None), "inertial_ba_set_stream")
+
+    def set_profiling(self, on):
+        capi.check(self.lib.inertial_ba_set_profiling(self.h, int(bool(on))), "inertial_ba_set_profiling")
+
+    def phase_ms(self):
+        """structure, linearise, Schur, LDL^T, update of the last solve (set_profiling(True) first)"""
+        ms = (C.c_double * 5)()
+        capi.check(self.lib.inertial_ba_get_phase_ms(self.h, ms), "inertial_ba_get_phase_ms")
+        return list(ms)
+
+    def close(self):
+        if self.h:
+            self.lib.inertial_ba_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

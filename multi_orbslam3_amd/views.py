@@ -407,6 +407,89 @@ class PoseInertialOutput:
                 "chi2": list(c.chi2), "H": np.array(list(c.H)).reshape(15, 15)}
 
 
+def inertial_ba_problem(keyframes, points, edges, close, cam, Tcb, rec_init=False, large=False, device=0):
+    """inertial_ba_problem of include/orbgpu.h.  keyframes: a list of dicts -- state (dict Rwb, twb, vwb, bg, ba), fixed, imu, and for a
+    keyframe with an inertial edge to its predecessor: prev (index into the list), preint (dict as for pose_inertial_problem), info9 /
+    infoG / infoA (orbg_imu_information(C)), last_in_window; points: (n, 3) float32; edges: structured EDGE_DTYPE in creation order (pose =
+    keyframe index); close: per point; cam = (fx, fy, cx, cy, bf); Tcb: mImuCalib.Tcb.  Returns (problem, keep-alive list)."""
+    K = (capi.InertialBaKeyframe * max(len(keyframes), 1))()
+    for i, kf in enumerate(keyframes):
+        c = K[i]
+        for k in ("Rwb", "twb", "vwb", "bg", "ba"):
+            _fill(getattr(c.state, k), kf["state"][k], np.float32)
+        c.fixed, c.imu = int(bool(kf["fixed"])), int(bool(kf["imu"]))
+        c.link = int(kf.get("prev") is not None)
+        c.prev = int(kf["prev"]) if c.link else -1
+        c.last_in_window = int(bool(kf.get("last_in_window", False)))
+        if c.link:
+            c.preint.dT = float(kf["preint"]["dT"])
+            for k in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "bg", "ba"):
+                _fill(getattr(c.preint, k), kf["preint"][k], np.float32)
+            _fill(c.info9, kf["info9"], np.float64)
+            _fill(c.infoG, kf["infoG"], np.float64)
+            _fill(c.infoA, kf["infoA"], np.float64)
+    pts = _c(np.asarray(points, np.float32).reshape(-1, 3), np.float32)
+    E = np.ascontiguousarray(edges, capi.EDGE_DTYPE)
+    cl = _c(close, np.uint8)
+    assert len(cl) == len(pts)
+    p = capi.InertialBaProblem()
+    p.struct_size = C.sizeof(capi.InertialBaProblem)
+    p.n_keyframes, p.n_points, p.n_edges = len(keyframes), len(pts), len(E)
+    p.keyframes = C.addressof(K)
+    p.points = capi.ptr(pts) if len(pts) else None
+    p.edges = capi.ptr(E) if len(E) else None
+    p.close = capi.ptr(cl) if len(cl) else None
+    p.rec_init, p.large, p.device = int(bool(rec_init)), int(bool(large)), int(device)
+    p.fx, p.fy, p.cx, p.cy, p.bf = [float(c) for c in cam]
+    _fill(p.Tcb, np.asarray(Tcb, np.float32)[:3, :4], np.float32)
+    return p, [K, pts, E, cl]
+
+
+class InertialBaOutput:
+    """inertial_ba_result with its arrays.  states: (n_keyframes, 21) double = Rwb (9), twb, vwb, bg, ba."""
+
+    def __init__(self, problem, trace_cap=16):
+        nk, nx, ne = problem.n_keyframes, problem.n_points, problem.n_edges
+        self.states = np.zeros((max(nk, 1), capi.INERTIAL_BA_STATE_DOUBLES))
+        self.points = np.zeros((max(nx, 1), 3), np.float32)
+        self.edge_chi2 = np.zeros(max(ne, 1))
+        self.edge_depth_pos = np.zeros(max(ne, 1), np.uint8)
+        self.edge_outlier = np.zeros(max(ne, 1), np.uint8)
+        self.trace = np.zeros((max(trace_cap, 1), 3))
+        self.nk, self.nx, self.ne = nk, nx, ne
+        c = self.c = capi.InertialBaResult()
+        c.struct_size = C.sizeof(capi.InertialBaResult)
+        c.states, c.points = capi.ptr(self.states), capi.ptr(self.points)
+        c.edge_chi2, c.edge_depth_pos, c.edge_outlier = capi.ptr(self.edge_chi2), capi.ptr(self.edge_depth_pos), capi.ptr(self.edge_outlier)
+        c.trace, c.trace_cap = capi.ptr(self.trace), trace_cap
+
+    def as_dict(self):
+        """the result in the layout of the numpy model (tests/inertial_ba_model.py)"""
+        c = self.c
+        st = self.states[: self.nk]
+        return {"states": [{"R": s[0:9].reshape(3, 3).copy(), "t": s[9:12].copy(), "v": s[12:15].copy(), "bg": s[15:18].copy(),
+                            "ba": s[18:21].copy()} for s in st],
+                "points": self.points[: self.nx].copy(), "edge_chi2": self.edge_chi2[: self.ne].copy(),
+                "edge_depth_pos": self.edge_depth_pos[: self.ne].copy(), "edge_outlier": self.edge_outlier[: self.ne].copy(),
+                "n_outliers": c.n_outliers, "failed": c.failed, "iters": c.iters, "chi2_initial": c.chi2_initial, "chi2_final": c.chi2_final,
+                "trace": self.trace[: c.trace_len].copy()}
+
+    def write_back(self, Tcb):
+        """What the glue hands to SetVelocity / SetNewBias / SetPose / SetWorldPos (S/Optimizer.cc:5154-5213), in float: per keyframe
+        (vwb, bias as IMU::Bias(b[3], b[4], b[5], b[0], b[1], b[2]) = (ba, bg), Tcw 4 x 4 from Rcw[0], tcw[0]), and the points."""
+        Tcb = np.asarray(Tcb, np.float32).astype(np.float64)[:3, :4]
+        Rcb, tcb = Tcb[:, :3], Tcb[:, 3]
+        out = []
+        for s in self.states[: self.nk]:
+            Rwb, twb = s[0:9].reshape(3, 3), s[9:12]
+            Tcw = np.eye(4)
+            Tcw[:3, :3] = Rcb @ Rwb.T
+            Tcw[:3, 3] = Rcb @ (-(Rwb.T @ twb)) + tcb
+            out.append({"vwb": s[12:15].astype(np.float32), "bias": np.concatenate([s[18:21], s[15:18]]).astype(np.float32),
+                        "Tcw": Tcw.astype(np.float32)})
+        return out, self.points[: self.nx].copy()
+
+
 def database_view(inverted_file, bow_vectors, covisible, map_id, bad, map_bad, n_words):
     """orbd_database_view (KeyFrameDatabase flattened, S/KeyFrameDatabase.cc:594-761): inverted_file = {word: [kf, ...]} in
     insertion order, bow_vectors[kf] = (words ascending, values), covisible[kf] = GetBestCovisibilityKeyFrames(10) as indices."""
