@@ -40,6 +40,7 @@
 #include "se3.hpp"
 #include "sim3_math.hpp"
 #include "lm_driver.hpp"
+#include "lm_record.hpp"
 
 using namespace orbg;
 using namespace orbg_s3;
@@ -56,15 +57,6 @@ constexpr int kEJ = 105;                 // per edge: Ji (7 x 7 row-major: error
 constexpr int kLinEdges = 8;             // edges per workgroup of k_eg_lin (32 lanes each)
 
 struct EgEdge { int vi, vj; S3 C; };
-struct EgRec { double chi2, scale, maxdiag; int ok, pad; };
-
-__device__ __forceinline__ double eg_block_sum_256(double v, double* red /* 4 */) {
-  const double w = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 // EdgeSim3::computeError, G/types/types_seven_dof_expmap.h:106-114: (C * v1) * v2^-1, then log()
 __host__ __device__ inline void eg_error(const S3& C, const S3& Si, const S3& Sj, double* e) {
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(256) void k_eg_lin(int NE, const EgEdge* __restrict
     if (slot == 0)
       for (int a = 0; a < 7; a++) chi += se[le][0][a] * se[le][0][a];
   }
-  const double s = eg_block_sum_256(chi, red);
+  const double s = block_sum_256(chi, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(256) void k_eg_errors(int NE, const EgEdge* __restr
       for (int a = 0; a < 7; a++) err_out[7 * (size_t)k + a] = r[a];
     }
   }
-  const double s = eg_block_sum_256(chi, red);
+  const double s = block_sum_256(chi, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -243,24 +235,14 @@ __global__ __launch_bounds__(256) void k_eg_update(int NV, const int* __restrict
   scale_v[v] = sc;
 }
 
+// one workgroup: the largest diagonal entry of a linearisation (Hd given), then lm_finish_record
 __global__ __launch_bounds__(256) void k_eg_finish(int n_partial, const double* __restrict__ partial, int n_scale, const double* __restrict__ scale_v,
-                                                   int F, const double* __restrict__ Hd, const int* __restrict__ ok_flag, EgRec* __restrict__ rec) {
-  __shared__ double red[4];
-  __shared__ double mx[256];
+                                                   int F, const double* __restrict__ Hd, const int* __restrict__ ok_flag, LmRec* __restrict__ rec) {
   const int tid = threadIdx.x;
-  double s = 0;
-  { const int ch = (n_partial + 255) / 256; const int b = min(n_partial, tid * ch), e = min(n_partial, b + ch); for (int i = b; i < e; i++) s += partial[i]; }
-  const double chi = eg_block_sum_256(s, red);
-  s = 0;
-  { const int ch = (n_scale + 255) / 256; const int b = min(n_scale, tid * ch), e = min(n_scale, b + ch); for (int i = b; i < e; i++) s += scale_v[i]; }
-  const double scale = eg_block_sum_256(s, red);
   double m = 0;
   if (Hd)
     for (int i = tid; i < 7 * F; i += 256) m = fmax(m, fabs(Hd[49 * (size_t)(i / 7) + 8 * (i % 7)]));
-  mx[tid] = m;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) { if (tid < s2) mx[tid] = fmax(mx[tid], mx[tid + s2]); __syncthreads(); }
-  if (tid == 0) { rec->chi2 = chi; rec->scale = scale; rec->maxdiag = mx[0]; rec->ok = ok_flag ? *ok_flag : 1; }
+  lm_finish_record(n_partial, partial, n_scale, scale_v, m, ok_flag, rec);
 }
 
 // S/Optimizer.cc:2710-2743: correctedSwr.map(Srw.map(P)), Srw the vertex's INITIAL estimate, correctedSwr the inverse of its final one
@@ -289,8 +271,8 @@ struct EgBufs {
   DevBuf<double> d_EJ, d_partial, d_Hd, d_bv, d_Hp, d_x, d_scale_v, d_err0;
   DevBuf<eg_point> d_pts;
   DevBuf<float> d_pts_out;
-  DevBuf<EgRec> d_rec;
-  PinnedBuf<EgRec> rec;
+  DevBuf<LmRec> d_rec;
+  PinnedBuf<LmRec> rec;
   PhaseTimer<4> timer;
   void release_buffers() {
     ldlt.release();
@@ -482,13 +464,7 @@ struct EgRun {
     return ORBG_OK;
   }
 
-  int fetch_record() {
-    ORBG_HIP(hipGetLastError());
-    ORBG_HIP(hipMemcpyAsync(h->rec.h, h->d_rec.p, sizeof(EgRec), hipMemcpyDeviceToHost, st));
-    ORBG_HIP(hipStreamSynchronize(st));
-    h->timer.flush(st);
-    return ORBG_OK;
-  }
+  int fetch_record() { return lm_fetch_record(h->rec.h, h->d_rec.p, st, h->timer); }
 
   // computeActiveErrors + buildSystem of state `buf`; the record brings chi2 and the largest diagonal entry
   int linearise(int buf) {
@@ -528,8 +504,8 @@ struct EgRun {
 
   // ---- what lm_optimize (lm_driver.hpp) asks of a solve; no stop flag here
   int linearise() { return linearise(cur); }
-  const EgRec& record() const { return *h->rec.h; }
-  int timed_out() const { return LdltSolver::timed_out(h->rec.h->ok) ? kRcLdltTimedOut : ORBG_OK; }
+  const LmRec& record() const { return *h->rec.h; }
+  int timed_out() const { return ldlt_timed_out_rc(h->rec.h->ok); }
   void accept() { cur ^= 1; }
   int first_linearisation(double* user_lambda) {
     *user_lambda = p->lambda_init;

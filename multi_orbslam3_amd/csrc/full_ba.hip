@@ -4,7 +4,8 @@
 // map point of a map, Huber kernels on or off, every edge with the camera of its own keyframe.
 //
 // The edges, the Huber kernel, the LM decisions and the LDL^T solvers are the local BA's (ba_edge.hpp, lm_driver.hpp, ldlt_mfma.hpp,
-// ldlt_xcd.hpp, ldlt_wide.hpp).  What is new is everything whose size goes with the MAP instead of a window (DESIGN.md,
+// ldlt_xcd.hpp, ldlt_wide.hpp); the landmark-Schur arithmetic between them (landmark_schur.hpp) and the record of an evaluation
+// (lm_record.hpp) are shared with inertial_ba.hip.  What is new is everything whose size goes with the MAP instead of a window (DESIGN.md,
 // "BundleAdjustment"): hundreds of free poses, 10^5 .. 10^6 edges, a reduced camera system most of whose blocks are empty.
 //   structure, once per call, all on the device, no sort and no floating-point atomic:
 //     k_ba_ranges                 the run of edges of every point (a point's edges are consecutive)
@@ -14,9 +15,9 @@
 //                                 pose i's edge list (ordered compaction)
 //   per LM iteration:
 //     k_ba_lin      thread/edge  residual, chi2, rho, Jacobians -> Hpl | Hll | bl blocks
-//     k_ba_points   thread/point Hll, bl in edge order;  k_ba_poses  workgroup/free pose  Hpp, bp (fixed tree)
+//     k_schur_points thread/point Hll, bl in edge order;  k_ba_poses  workgroup/free pose  Hpp, bp (fixed tree)
 //   per trial:
-//     k_ba_dinv     thread/point (Hll + lambda I)^-1 and its product with bl
+//     k_schur_dinv  thread/point (Hll + lambda I)^-1 and its product with bl
 //     one fill of the dense reduced system, then k_ba_schur: workgroup per NON-EMPTY pair, items in fixed order
 //     LDL^T by size (<= 20 free poses: one workgroup on the matrix cores, <= 50: eight workgroups, beyond: k_wide_*)
 //     k_ba_update   thread/vertex  back-substitution, trial state, computeScale terms
@@ -46,6 +47,7 @@
 
 #include "se3.hpp"
 #include "lm_driver.hpp"
+#include "lm_record.hpp"
 
 using namespace orbg;
 using namespace orbg_se3;
@@ -60,14 +62,13 @@ namespace {
 #include "ba_edge.hpp"
 #include "ldlt_wide.hpp"
 #include "ldlt_solver.hpp"
+#include "landmark_schur.hpp"
 
 constexpr int kEB = 27;                 // per-edge blocks: Hpl (6x3, 18) | Hll upper (6) | bl (3), as in lba.hip
+static_assert(kEB == kSchurHead, "an edge's block is exactly what landmark_schur.hpp reads: Hpl | Hll | bl");
 constexpr int kMaxCols = BA_MAX_FREE_POSES;
 constexpr int kTileEdges = 256;         // edges per workgroup pass of the counting sort
 constexpr int kMaxTiles = 2048;
-
-struct BaItem { int ea, eb; };          // edges (pose i / pose j) of one landmark both poses observe
-struct BaRec { double chi2, scale, maxdiag; int ok, pad; };
 
 // ------------------------------------------------------------------------------------------ structure
 
@@ -220,14 +221,14 @@ __global__ __launch_bounds__(256) void k_ba_items_fill(int n_pairs, const int* _
                                                        const int* __restrict__ row_start, const int* __restrict__ row_edges,
                                                        const lba_edge* __restrict__ edges, const int* __restrict__ pt_start,
                                                        const int* __restrict__ pt_end, const int* __restrict__ pose_col,
-                                                       const int* __restrict__ item_start, BaItem* __restrict__ items) {
+                                                       const int* __restrict__ item_start, SchurItem* __restrict__ items) {
   __shared__ int flag[256];
   const int p = blockIdx.x, tid = threadIdx.x;
   const int i = pair_i[p], j = pair_j[p];
   const int b = row_start[i], e = row_start[i + 1];
   int base = item_start[p];
   if (i == j) {
-    for (int q = b + tid; q < e; q += 256) { const int k = row_edges[q]; items[base + (q - b)] = BaItem{k, k}; }
+    for (int q = b + tid; q < e; q += 256) { const int k = row_edges[q]; items[base + (q - b)] = SchurItem{k, k}; }
     return;
   }
   for (int q0 = b; q0 < e; q0 += 256) {
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(256) void k_ba_items_fill(int n_pairs, const int* _
     __syncthreads();
     int rank = 0, tot = 0;
     for (int t = 0; t < 256; t++) { const int f = flag[t]; tot += f; if (t < tid) rank += f; }
-    if (eb >= 0) items[base + rank] = BaItem{ea, eb};
+    if (eb >= 0) items[base + rank] = SchurItem{ea, eb};
     base += tot;
   }
 }
@@ -253,15 +254,6 @@ __global__ __launch_bounds__(256) void k_ba_items_fill(int n_pairs, const int* _
 __device__ __forceinline__ void edge_rho(double chi, bool mono, int robust, const Huber& hb, double* rho0, double* rho1) {
   if (robust) huber(chi, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, rho0, rho1);
   else { *rho0 = chi; *rho1 = 1.0; }
-}
-
-// sum of v over the workgroup (256 threads) in a fixed order, valid in thread 0
-__device__ __forceinline__ double block_sum_256(double v, double* red /* 4 */) {
-  const double w = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 // residuals of state (poses, points): chi2 per edge, the workgroup's robust partial
@@ -351,32 +343,12 @@ __global__ __launch_bounds__(256) void k_ba_lin(int NE, const lba_edge* __restri
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// Hll, bl of every point: its edges in order
-__global__ __launch_bounds__(256) void k_ba_points(int NX, const int* __restrict__ pt_start, const int* __restrict__ pt_end,
-                                                   const double* __restrict__ EB, double* __restrict__ Hll, double* __restrict__ bl) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= NX) return;
-  double acc[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) acc[i] = 0;
-  for (int k = pt_start[l]; k < pt_end[l]; k++) {
-    const double* eb = EB + (size_t)k * kEB + 18;
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc[i] += eb[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) Hll[6 * (size_t)l + i] = acc[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++) bl[3 * (size_t)l + i] = acc[6 + i];
-}
-
 // Hpp (21 upper entries), bp of one free pose: rebuilt from its edges, thread t takes edges t, t + 256, ... in order
 __global__ __launch_bounds__(256) void k_ba_poses(const int* __restrict__ row_start, const int* __restrict__ row_edges,
                                                   const lba_edge* __restrict__ edges, const PoseQ* __restrict__ poses,
                                                   const double* __restrict__ points, const int* __restrict__ pose_cam,
                                                   const CamRig* __restrict__ cams, int robust, Huber hb, const double* __restrict__ chi2,
                                                   double* __restrict__ Hpp, double* __restrict__ bp) {
-  __shared__ double wpart[4][27];
   const int p = blockIdx.x;
   const int b = row_start[p], e_end = row_start[p + 1];
   double acc[27];
@@ -420,47 +392,15 @@ __global__ __launch_bounds__(256) void k_ba_poses(const int* __restrict__ row_st
       acc[o++] += s;
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 27; i++) {
-    const double v = wave_sum_f64(acc[i]);
-    if (lane == 0) wpart[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 27) {
-    const double v = ((wpart[0][threadIdx.x] + wpart[1][threadIdx.x]) + wpart[2][threadIdx.x]) + wpart[3][threadIdx.x];
-    if (threadIdx.x < 21) Hpp[21 * (size_t)p + threadIdx.x] = v;
-    else bp[6 * (size_t)p + threadIdx.x - 21] = v;
-  }
+  schur_pose_tail(acc, p, Hpp, bp);
 }
 
 // ------------------------------------------------------------------------------------------ per trial
 
-// Eigen-style cofactor inverse of (Hll + lambda I), upper six entries, and its product with bl
-__global__ __launch_bounds__(256) void k_ba_dinv(int NX, const double* __restrict__ Hll, const double* __restrict__ bl, double lambda,
-                                                 double* __restrict__ Dinv, double* __restrict__ Db) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= NX) return;
-  const double* h6 = Hll + 6 * (size_t)l;
-  const double m0 = h6[0] + lambda, m1 = h6[1], m2 = h6[2], m4 = h6[3] + lambda, m5 = h6[4], m8 = h6[5] + lambda;
-  const double c00 = m4 * m8 - m5 * m5, c01 = m5 * m2 - m1 * m8, c02 = m1 * m5 - m4 * m2;
-  const double det = m0 * c00 + m1 * c01 + m2 * c02;
-  const double id = 1.0 / det;
-  const double d0 = c00 * id, d1 = c01 * id, d2 = c02 * id, d3 = (m0 * m8 - m2 * m2) * id, d4 = (m2 * m1 - m0 * m5) * id,
-               d5 = (m0 * m4 - m1 * m1) * id;
-  double* o = Dinv + 6 * (size_t)l;
-  o[0] = d0; o[1] = d1; o[2] = d2; o[3] = d3; o[4] = d4; o[5] = d5;
-  const double* b = bl + 3 * (size_t)l;
-  double* ob = Db + 3 * (size_t)l;
-  ob[0] = d0 * b[0] + d1 * b[1] + d2 * b[2];
-  ob[1] = d1 * b[0] + d3 * b[1] + d4 * b[2];
-  ob[2] = d2 * b[0] + d4 * b[1] + d5 * b[2];
-}
-
 // S_ij = [i == j](Hpp_i + lambda I) - sum_l Hpl_il Dinv_l Hpl_jl^T over the pair's items; diagonal pairs also
 // bs_i = bp_i - sum_l Hpl_il (Dinv_l bl_l).  One workgroup per NON-EMPTY pair; blocks of absent pairs keep the zeros of the fill.
 __global__ __launch_bounds__(256) void k_ba_schur(int nP, const int* __restrict__ pair_i, const int* __restrict__ pair_j,
-                                                  const int* __restrict__ item_start, const BaItem* __restrict__ items,
+                                                  const int* __restrict__ item_start, const SchurItem* __restrict__ items,
                                                   const lba_edge* __restrict__ edges, const double* __restrict__ EB,
                                                   const double* __restrict__ Dinv, const double* __restrict__ Db,
                                                   const double* __restrict__ Hpp, const double* __restrict__ bp, double lambda,
@@ -470,44 +410,7 @@ __global__ __launch_bounds__(256) void k_ba_schur(int nP, const int* __restrict_
   const int i1 = pair_i[p], i2 = pair_j[p];
   const bool diag = i1 == i2;
   const int b = item_start[p], e = item_start[p + 1];
-  double acc[42];
-#pragma unroll
-  for (int i = 0; i < 42; i++) acc[i] = 0;
-  for (int q = b + threadIdx.x; q < e; q += 256) {
-    const BaItem it = items[q];
-    const int l = edges[it.ea].point;
-    const double* Ha = EB + (size_t)it.ea * kEB;
-    const double* Hb = EB + (size_t)it.eb * kEB;
-    const double* d = Dinv + 6 * (size_t)l;
-    const double d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5];
-    double Wm[18];                                 // Hpl_a Dinv  (6 x 3)
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      const double h0 = Ha[3 * a], h1 = Ha[3 * a + 1], h2 = Ha[3 * a + 2];
-      Wm[3 * a] = h0 * d0 + h1 * d1 + h2 * d2;
-      Wm[3 * a + 1] = h0 * d1 + h1 * d3 + h2 * d4;
-      Wm[3 * a + 2] = h0 * d2 + h1 * d4 + h2 * d5;
-    }
-    double hb[18];
-#pragma unroll
-    for (int i = 0; i < 18; i++) hb[i] = Hb[i];
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int c = 0; c < 6; c++) acc[6 * a + c] += Wm[3 * a] * hb[3 * c] + Wm[3 * a + 1] * hb[3 * c + 1] + Wm[3 * a + 2] * hb[3 * c + 2];
-    if (diag) {
-      const double* db = Db + 3 * (size_t)l;
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[36 + a] += Ha[3 * a] * db[0] + Ha[3 * a + 1] * db[1] + Ha[3 * a + 2] * db[2];
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 42; i++) {
-    const double v = wave_sum_f64(acc[i]);
-    if (lane == 0) wpart[wave][i] = v;
-  }
-  __syncthreads();
+  schur_pair_items<kEB>(diag, b, e, items, edges, EB, Dinv, Db, wpart);
   const int tid = threadIdx.x;
   const int n = 6 * nP;
   // every entry of the system and its mirror image are written by ONE thread, with one value: on a diagonal pair the thread of
@@ -522,14 +425,7 @@ __global__ __launch_bounds__(256) void k_ba_schur(int nP, const int* __restrict_
       v += Hpp[21 * (size_t)i1 + u] + (a == c ? lambda : 0.0);
     }
     const int r = 6 * i1 + a, cc = 6 * i2 + c;
-    if (St) {
-      const int p0 = ldltm::tile_image_pos(r, cc), p1 = ldltm::tile_image_pos(cc, r);
-      if (p0 >= 0) St[p0] = v;
-      if (p1 >= 0 && r != cc) St[p1] = v;
-    } else {
-      S[(size_t)r * n + cc] = v;
-      if (r != cc) S[(size_t)cc * n + r] = v;
-    }
+    schur_store_entry(r, cc, n, v, S, St);
   } else if (diag && tid < 42) {
     const int a = tid - 36;
     const double s = ((wpart[0][tid] + wpart[1][tid]) + wpart[2][tid]) + wpart[3][tid];
@@ -565,50 +461,16 @@ __global__ __launch_bounds__(256) void k_ba_update(int NP, int NX, const int* __
     scale_v[v] = sc;
     return;
   }
-  const int l = v - NP;
-  const int b = pt_start[l], e = pt_end[l];
-  double sc = 0;
-  double X[3] = {points[3 * (size_t)l], points[3 * (size_t)l + 1], points[3 * (size_t)l + 2]};
-  if (e > b && ok) {
-    double rr[3] = {bl[3 * (size_t)l], bl[3 * (size_t)l + 1], bl[3 * (size_t)l + 2]};
-    for (int k = b; k < e; k++) {
-      const int c = pose_col[edges[k].pose];
-      if (c < 0) continue;
-      const double* H = EB + (size_t)k * kEB;
-      const double* xi = x + 6 * c;
-#pragma unroll
-      for (int cc = 0; cc < 3; cc++) {
-        double s = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++) s += H[3 * a + cc] * xi[a];
-        rr[cc] -= s;
-      }
-    }
-    const double* d = Dinv + 6 * (size_t)l;
-    const double xl[3] = {d[0] * rr[0] + d[1] * rr[1] + d[2] * rr[2], d[1] * rr[0] + d[3] * rr[1] + d[4] * rr[2],
-                          d[2] * rr[0] + d[4] * rr[1] + d[5] * rr[2]};
-#pragma unroll
-    for (int a = 0; a < 3; a++) { sc += xl[a] * (lambda * xl[a] + bl[3 * (size_t)l + a]); X[a] += xl[a]; }
-  }
-  points_out[3 * (size_t)l] = X[0]; points_out[3 * (size_t)l + 1] = X[1]; points_out[3 * (size_t)l + 2] = X[2];
-  scale_v[v] = sc;
+  schur_update_point<kEB>(v - NP, ok, pose_col, [](int c) { return 6 * c; }, points, x, pt_start, pt_end, edges, EB, Dinv, bl, lambda, points_out,
+                          scale_v + v);
 }
 
-// one workgroup: the sums of the partials in index order, the largest diagonal entry, the solver's flag -> the record
+// one workgroup: the largest diagonal entry of a linearisation (Hpp given), then lm_finish_record
 __global__ __launch_bounds__(256) void k_ba_finish(int n_partial, const double* __restrict__ partial, int n_scale, const double* __restrict__ scale_v,
                                                    int nP, const double* __restrict__ Hpp, int NX, const double* __restrict__ Hll,
                                                    const int* __restrict__ pt_start, const int* __restrict__ pt_end,
-                                                   const int* __restrict__ ok_flag, BaRec* __restrict__ rec) {
-  __shared__ double red[4];
-  __shared__ double mx[256];
+                                                   const int* __restrict__ ok_flag, LmRec* __restrict__ rec) {
   const int tid = threadIdx.x;
-  // thread t sums a contiguous chunk in order, the 256 chunk sums go through the fixed tree
-  double s = 0;
-  { const int ch = (n_partial + 255) / 256; const int b = min(n_partial, tid * ch), e = min(n_partial, b + ch); for (int i = b; i < e; i++) s += partial[i]; }
-  const double chi = block_sum_256(s, red);
-  s = 0;
-  { const int ch = (n_scale + 255) / 256; const int b = min(n_scale, tid * ch), e = min(n_scale, b + ch); for (int i = b; i < e; i++) s += scale_v[i]; }
-  const double scale = block_sum_256(s, red);
   double m = 0;
   if (Hpp) {
     for (int i = tid; i < nP; i += 256) {
@@ -621,10 +483,7 @@ __global__ __launch_bounds__(256) void k_ba_finish(int n_partial, const double* 
       m = fmax(m, fmax(fabs(h[0]), fmax(fabs(h[3]), fabs(h[5]))));
     }
   }
-  mx[tid] = m;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) { if (tid < s2) mx[tid] = fmax(mx[tid], mx[tid + s2]); __syncthreads(); }
-  if (tid == 0) { rec->chi2 = chi; rec->scale = scale; rec->maxdiag = mx[0]; rec->ok = ok_flag ? *ok_flag : 1; }
+  lm_finish_record(n_partial, partial, n_scale, scale_v, m, ok_flag, rec);
 }
 
 __global__ __launch_bounds__(256) void k_ba_depth(int NE, const lba_edge* __restrict__ edges, const PoseQ* __restrict__ poses,
@@ -689,7 +548,7 @@ struct ba_handle {
       d_pair_i, d_pair_j, d_item_cnt, d_item_start, d_ok;
   DevBuf<unsigned> d_bitmap;
   DevBuf<long long> d_total;
-  DevBuf<BaItem> d_items;
+  DevBuf<SchurItem> d_items;
   DevBuf<CamRig> d_cams;
   DevBuf<double> d_chi2, d_partial, d_EB, d_Hll, d_bl, d_Hpp, d_bp, d_Dinv, d_Db, d_bs, d_x, d_scale_v;
   DevBuf<uint8_t> d_depth;
@@ -698,8 +557,8 @@ struct ba_handle {
   DevBuf<double> d_chi2_kept;
   DevBuf<uint8_t> d_level;
   DevBuf<int> d_keep, d_keep_off, d_origin;
-  DevBuf<BaRec> d_rec;
-  PinnedBuf<BaRec> rec;
+  DevBuf<LmRec> d_rec;
+  PinnedBuf<LmRec> rec;
   PinnedBuf<long long> total_h;
   std::vector<PoseQ> s_poses;
   std::vector<double> s_points;
@@ -731,19 +590,8 @@ int ba_validate(const ba_problem* p, const ba_result* r, int* n_free) {
     if (p->cameras[c].model.model != ORBG_CAM_PINHOLE && p->cameras[c].model.model != ORBG_CAM_KANNALA_BRANDT8) return ORBG_BAD_ARG;
   if (nP > BA_MAX_FREE_POSES) return ORBG_CAP_EXCEEDED;
   *n_free = nP;
-  // the host's one pass over the edges: ranges, the right camera's edges, the order rule
-  std::vector<int> stamp((size_t)std::max(p->n_poses, 1), -1);
-  int prev = -1;
-  for (int k = 0; k < p->n_edges; k++) {
-    const lba_edge& e = p->edges[k];
-    if (e.pose < 0 || e.pose >= p->n_poses || e.point < 0 || e.point >= p->n_points) return ORBG_BAD_ARG;
-    if (ur_is_right(e.ur)) return ORBG_BAD_ARG;                 // EdgeSE3ProjectXYZToBody: not part of this entry point
-    if (e.point < prev) return ORBG_BAD_ARG;                    // per point, its observations
-    if (stamp[e.pose] == e.point) return ORBG_BAD_ARG;          // one observation per keyframe and point
-    stamp[e.pose] = e.point;
-    prev = e.point;
-  }
-  return ORBG_OK;
+  // the host's one pass over the edges: ranges, the order rule, the right camera's edges (EdgeSE3ProjectXYZToBody: not part of this entry point)
+  return schur_check_edges(p->edges, p->n_edges, p->n_poses, p->n_points, [](float ur) { return ur_is_right(ur); });
 }
 
 struct BaRun {
@@ -929,13 +777,7 @@ struct BaRun {
   }
 
   // the record of the last launches, on the host
-  int fetch_record() {
-    ORBG_HIP(hipGetLastError());
-    ORBG_HIP(hipMemcpyAsync(h->rec.h, h->d_rec.p, sizeof(BaRec), hipMemcpyDeviceToHost, st));
-    ORBG_HIP(hipStreamSynchronize(st));
-    h->timer.flush(st);
-    return ORBG_OK;
-  }
+  int fetch_record() { return lm_fetch_record(h->rec.h, h->d_rec.p, st, h->timer); }
 
   // computeActiveErrors + buildSystem of state `buf`; the record brings chi2 and the largest diagonal entry
   int linearise(int buf) {
@@ -945,7 +787,7 @@ struct BaRun {
                          h->d_cams.p, robust, hb, h->d_chi2.p, h->d_partial.p, h->d_EB.p);
     }
     if (NX > 0)
-      hipLaunchKernelGGL(k_ba_points, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_pt_start.p, h->d_pt_end.p, h->d_EB.p, h->d_Hll.p, h->d_bl.p);
+      hipLaunchKernelGGL(k_schur_points<kEB>, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_pt_start.p, h->d_pt_end.p, h->d_EB.p, h->d_Hll.p, h->d_bl.p);
     if (nP > 0)
       hipLaunchKernelGGL(k_ba_poses, dim3(nP), dim3(256), 0, st, h->d_row_start.p, h->d_row_edges.p, h->d_edges.p, h->d_poses[buf].p,
                          h->d_points[buf].p, h->d_pose_cam.p, h->d_cams.p, robust, hb, h->d_chi2.p, h->d_Hpp.p, h->d_bp.p);
@@ -961,7 +803,7 @@ struct BaRun {
     int rc;
     h->timer.begin(kPhSchur, st);
     if (NX > 0)
-      hipLaunchKernelGGL(k_ba_dinv, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_Hll.p, h->d_bl.p, lambda, h->d_Dinv.p, h->d_Db.p);
+      hipLaunchKernelGGL(k_schur_dinv, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_Hll.p, h->d_bl.p, lambda, h->d_Dinv.p, h->d_Db.p);
     if (nP > 0) {
       if ((rc = h->ldlt.clear(h->d_x.p, st))) return rc;
       hipLaunchKernelGGL(k_ba_schur, dim3(n_pairs), dim3(256), 0, st, nP, h->d_pair_i.p, h->d_pair_j.p, h->d_item_start.p, h->d_items.p,
@@ -992,8 +834,8 @@ struct BaRun {
 
   // ---- what lm_optimize (lm_driver.hpp) asks of a solve
   int linearise() { return linearise(cur); }
-  const BaRec& record() const { return *h->rec.h; }
-  int timed_out() const { return LdltSolver::timed_out(h->rec.h->ok) ? kRcLdltTimedOut : ORBG_OK; }
+  const LmRec& record() const { return *h->rec.h; }
+  int timed_out() const { return ldlt_timed_out_rc(h->rec.h->ok); }
   void accept() { cur ^= 1; }
   int first_linearisation(double* user_lambda) {
     *user_lambda = 0.0;
@@ -1002,10 +844,7 @@ struct BaRun {
   }
   void iteration_done(int qmax, bool) {
     r->chi2_final = lm.currentChi;
-    if (r->trace && r->trace_len < r->trace_cap) {
-      r->trace[3 * r->trace_len] = lm.lambda; r->trace[3 * r->trace_len + 1] = lm.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
-      r->trace_len++;
-    }
+    lm_trace_row(lm, qmax, r->trace, r->trace_cap, &r->trace_len);
   }
   int optimize(int iterations, int* done) { return lm_optimize(*this, iterations, stop, done); }
 

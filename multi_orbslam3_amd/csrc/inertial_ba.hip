@@ -5,7 +5,7 @@
 // observe them.
 //
 // The vertices and the inertial edges are the per-frame optimiser's (pose_inertial_edges.hpp), the LM decisions and the LDL^T solvers
-// the bundle adjustments' (lm_driver.hpp, ldlt_solver.hpp); full_ba.hip is the pattern of the landmark-Schur pipeline.  What is new:
+// the bundle adjustments' (lm_driver.hpp, lm_record.hpp, ldlt_solver.hpp), the landmark-Schur arithmetic full_ba.hip's (landmark_schur.hpp).  What is new:
 // the visual edges in the ImuCamPose parametrisation (update on the body, right-multiplied rotation), keyframe blocks of 15 (6 without
 // an IMU) at the offsets of a table, and the inertial blocks in the reduced system.
 //   structure, once per call, on the host (a window holds at most 32 free keyframes): the run of edges of every point, the edges of
@@ -15,10 +15,10 @@
 //     k_iba_edges   blocks [0, nbe): thread/visual edge  error, chi2, rho, Jacobians -> Hpl | Hll | bl | Hpp | bp
 //                   blocks [nbe, nbe + nIE): workgroup/inertial edge  the stacked 15 x 30 Jacobian (EdgeInertial's rows on thread 0,
 //                   the random walks' on thread 64), then across the workgroup W J, rho, J^T (rho W) J | b
-//     k_iba_points  thread/point Hll, bl in edge order;  k_iba_poses  workgroup/free keyframe  Hpp, bp (fixed tree)
+//     k_schur_points thread/point Hll, bl in edge order;  k_iba_poses  workgroup/free keyframe  Hpp, bp (fixed tree)
 //     k_iba_finish  the robust chi2 of the evaluation -> the record the host reads
 //   per trial:
-//     k_iba_dinv    thread/point (Hll + lambda I)^-1 and its product with bl
+//     k_schur_dinv  thread/point (Hll + lambda I)^-1 and its product with bl
 //     one fill of the dense reduced system, then k_iba_schur: workgroup per NON-EMPTY pair, the visual items in fixed order, then the
 //       pair's inertial blocks in edge order, one thread per entry
 //     LDL^T by size (LdltSolver::plan)
@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "lm_driver.hpp"
+#include "lm_record.hpp"
 
 using namespace orbg;
 using namespace orbg_lm;
@@ -54,18 +55,19 @@ namespace {
 #include "ldlt_wide.hpp"
 #include "ldlt_solver.hpp"
 #include "pose_inertial_edges.hpp"
+#include "landmark_schur.hpp"
 
 constexpr int kIbaMaxFree = INERTIAL_BA_MAX_FREE_KEYFRAMES;
 constexpr int kIbaEB = 54;               // per visual edge: Hpl (6 x 3, 18) | Hll upper (6) | bl (3) | Hpp upper (21) | bp (6)
 constexpr int kIbaIW = 31;               // row stride of an inertial edge's block: [keyframe 1's 15 | keyframe 2's 15 | b]
 constexpr int kIbaIB = 30 * kIbaIW;      // J^T (rho W) J (30 x 30) with -J^T (rho W) e in the last column
 constexpr int kIbaThreads = 256;
+static_assert(kIbaEB == kSchurHead + 21 + 6, "an edge's block is what landmark_schur.hpp reads (Hpl | Hll | bl), then the edge's Hpp | bp");
+static_assert(kIbaThreads == kSchurThreads, "k_iba_edges reduces with block_sum_256, and the shared loops advance by this workgroup size");
 
 struct IbaCam { double fx, fy, cx, cy, bf, Rcb[9], tcb[3], tbc[3]; };
 struct IbaInertial { int k1, k2, robust, pad; };          // EdgeInertial + EdgeGyroRW + EdgeAccRW between keyframes k1 (the earlier) and k2
 struct IbaPairInertial { int e, ro, co; };                // block (ro.., co..) of inertial edge e adds to the pair's block
-struct IbaItem { int ea, eb; };
-struct IbaRec { double chi2, scale, maxdiag; int ok, pad; };
 
 // ---------------------------------------------------------------------------------------------- the visual edges (host and device)
 
@@ -144,15 +146,6 @@ PI_HD __forceinline__ double iba_info(const PiParams& P, int r, int k) {
 
 // ---------------------------------------------------------------------------------------------- kernels
 
-// sum of v over the workgroup (256 threads) in a fixed order, valid in thread 0
-__device__ __forceinline__ double iba_block_sum(double v, double* red /* 4 */) {
-  const double w = wave_sum_f64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // One inertial edge, the whole workgroup: thread 0 EdgeInertial's rows, thread 64 the random walks' (the transcendental part), then
 // W J, the three chi2 and -- with IB -- J^T (rho W) J | -J^T (rho W) e, one entry per thread and pass.  Returns in thread 0 the sum
 // of the three robustified chi2 (only EdgeInertial may have a kernel: delta sqrt(16.92), S/Optimizer.cc:4826-4837).
@@ -230,76 +223,24 @@ __global__ __launch_bounds__(kIbaThreads) void k_iba_edges(int NE, int nbe, cons
       iba_visual_blocks(o, Jl, Jp, rho1 * om, EB + (size_t)k * kIbaEB);
     }
   }
-  const double s = iba_block_sum(rho0, red);
+  const double s = block_sum_256(rho0, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
-}
-
-// Hll, bl of every point: its edges in order
-__global__ __launch_bounds__(256) void k_iba_points(int NX, const int* __restrict__ pt_start, const int* __restrict__ pt_end,
-                                                    const double* __restrict__ EB, double* __restrict__ Hll, double* __restrict__ bl) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= NX) return;
-  double acc[9];
-#pragma unroll
-  for (int i = 0; i < 9; i++) acc[i] = 0;
-  for (int k = pt_start[l]; k < pt_end[l]; k++) {
-    const double* eb = EB + (size_t)k * kIbaEB + 18;
-#pragma unroll
-    for (int i = 0; i < 9; i++) acc[i] += eb[i];
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) Hll[6 * (size_t)l + i] = acc[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++) bl[3 * (size_t)l + i] = acc[6 + i];
 }
 
 // Hpp (21 upper entries), bp of the visual edges of one free keyframe: thread t takes edges t, t + 256, ... of its list in order
 __global__ __launch_bounds__(256) void k_iba_poses(const int* __restrict__ row_start, const int* __restrict__ row_edges,
                                                    const double* __restrict__ EB, double* __restrict__ Hpp, double* __restrict__ bp) {
-  __shared__ double wpart[4][27];
   const int p = blockIdx.x;
   const int b = row_start[p], e_end = row_start[p + 1];
   double acc[27];
 #pragma unroll
   for (int i = 0; i < 27; i++) acc[i] = 0;
   for (int q = b + threadIdx.x; q < e_end; q += 256) {
-    const double* eb = EB + (size_t)row_edges[q] * kIbaEB + 27;
+    const double* eb = EB + (size_t)row_edges[q] * kIbaEB + kSchurHead;
 #pragma unroll
     for (int i = 0; i < 27; i++) acc[i] += eb[i];
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 27; i++) {
-    const double v = wave_sum_f64(acc[i]);
-    if (lane == 0) wpart[wave][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 27) {
-    const double v = ((wpart[0][threadIdx.x] + wpart[1][threadIdx.x]) + wpart[2][threadIdx.x]) + wpart[3][threadIdx.x];
-    if (threadIdx.x < 21) Hpp[21 * (size_t)p + threadIdx.x] = v;
-    else bp[6 * (size_t)p + threadIdx.x - 21] = v;
-  }
-}
-
-// Eigen-style cofactor inverse of (Hll + lambda I), upper six entries, and its product with bl
-__global__ __launch_bounds__(256) void k_iba_dinv(int NX, const double* __restrict__ Hll, const double* __restrict__ bl, double lambda,
-                                                  double* __restrict__ Dinv, double* __restrict__ Db) {
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  if (l >= NX) return;
-  const double* h6 = Hll + 6 * (size_t)l;
-  const double m0 = h6[0] + lambda, m1 = h6[1], m2 = h6[2], m4 = h6[3] + lambda, m5 = h6[4], m8 = h6[5] + lambda;
-  const double c00 = m4 * m8 - m5 * m5, c01 = m5 * m2 - m1 * m8, c02 = m1 * m5 - m4 * m2;
-  const double det = m0 * c00 + m1 * c01 + m2 * c02;
-  const double id = 1.0 / det;
-  const double d0 = c00 * id, d1 = c01 * id, d2 = c02 * id, d3 = (m0 * m8 - m2 * m2) * id, d4 = (m2 * m1 - m0 * m5) * id,
-               d5 = (m0 * m4 - m1 * m1) * id;
-  double* o = Dinv + 6 * (size_t)l;
-  o[0] = d0; o[1] = d1; o[2] = d2; o[3] = d3; o[4] = d4; o[5] = d5;
-  const double* b = bl + 3 * (size_t)l;
-  double* ob = Db + 3 * (size_t)l;
-  ob[0] = d0 * b[0] + d1 * b[1] + d2 * b[2];
-  ob[1] = d1 * b[0] + d3 * b[1] + d4 * b[2];
-  ob[2] = d2 * b[0] + d4 * b[1] + d5 * b[2];
+  schur_pose_tail(acc, p, Hpp, bp);
 }
 
 // The block of the reduced system of one NON-EMPTY pair of free keyframes (i1 <= i2, widths d1, d2 of 6 or 15, columns from the
@@ -308,7 +249,7 @@ __global__ __launch_bounds__(256) void k_iba_dinv(int NX, const double* __restri
 // before the landmarks are eliminated (computeScale reads it).  Blocks of absent pairs keep the zeros of the fill.
 __global__ __launch_bounds__(256) void k_iba_schur(int n, const int* __restrict__ pair_i, const int* __restrict__ pair_j,
                                                    const int* __restrict__ col_off, const int* __restrict__ col_dim,
-                                                   const int* __restrict__ item_start, const IbaItem* __restrict__ items,
+                                                   const int* __restrict__ item_start, const SchurItem* __restrict__ items,
                                                    const int* __restrict__ pie_start, const IbaPairInertial* __restrict__ pies,
                                                    const lba_edge* __restrict__ edges, const double* __restrict__ EB, const double* __restrict__ IEB,
                                                    const double* __restrict__ Dinv, const double* __restrict__ Db,
@@ -319,44 +260,7 @@ __global__ __launch_bounds__(256) void k_iba_schur(int n, const int* __restrict_
   const int i1 = pair_i[p], i2 = pair_j[p];
   const bool diag = i1 == i2;
   const int b = item_start[p], e = item_start[p + 1];
-  double acc[42];
-#pragma unroll
-  for (int i = 0; i < 42; i++) acc[i] = 0;
-  for (int q = b + threadIdx.x; q < e; q += 256) {
-    const IbaItem it = items[q];
-    const int l = edges[it.ea].point;
-    const double* Ha = EB + (size_t)it.ea * kIbaEB;
-    const double* Hb = EB + (size_t)it.eb * kIbaEB;
-    const double* d = Dinv + 6 * (size_t)l;
-    const double d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4], d5 = d[5];
-    double Wm[18];                                 // Hpl_a Dinv  (6 x 3)
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      const double h0 = Ha[3 * a], h1 = Ha[3 * a + 1], h2 = Ha[3 * a + 2];
-      Wm[3 * a] = h0 * d0 + h1 * d1 + h2 * d2;
-      Wm[3 * a + 1] = h0 * d1 + h1 * d3 + h2 * d4;
-      Wm[3 * a + 2] = h0 * d2 + h1 * d4 + h2 * d5;
-    }
-    double hb[18];
-#pragma unroll
-    for (int i = 0; i < 18; i++) hb[i] = Hb[i];
-#pragma unroll
-    for (int a = 0; a < 6; a++)
-#pragma unroll
-      for (int c = 0; c < 6; c++) acc[6 * a + c] += Wm[3 * a] * hb[3 * c] + Wm[3 * a + 1] * hb[3 * c + 1] + Wm[3 * a + 2] * hb[3 * c + 2];
-    if (diag) {
-      const double* db = Db + 3 * (size_t)l;
-#pragma unroll
-      for (int a = 0; a < 6; a++) acc[36 + a] += Ha[3 * a] * db[0] + Ha[3 * a + 1] * db[1] + Ha[3 * a + 2] * db[2];
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 42; i++) {
-    const double v = wave_sum_f64(acc[i]);
-    if (lane == 0) wpart[wave][i] = v;
-  }
-  __syncthreads();
+  schur_pair_items<kIbaEB>(diag, b, e, items, edges, EB, Dinv, Db, wpart);
   const int tid = threadIdx.x;
   const int d1 = col_dim[i1], d2 = col_dim[i2], c1 = col_off[i1], c2 = col_off[i2];
   const int pb = pie_start[p], pe = pie_start[p + 1];
@@ -374,14 +278,7 @@ __global__ __launch_bounds__(256) void k_iba_schur(int n, const int* __restrict_
     if (diag && a == c) v += lambda;
     for (int q = pb; q < pe; q++) { const IbaPairInertial pi = pies[q]; v += IEB[(size_t)pi.e * kIbaIB + (pi.ro + a) * kIbaIW + pi.co + c]; }
     const int r = c1 + a, cc = c2 + c;
-    if (St) {
-      const int p0 = ldltm::tile_image_pos(r, cc), p1 = ldltm::tile_image_pos(cc, r);
-      if (p0 >= 0) St[p0] = v;
-      if (p1 >= 0 && r != cc) St[p1] = v;
-    } else {
-      S[(size_t)r * n + cc] = v;
-      if (r != cc) S[(size_t)cc * n + r] = v;
-    }
+    schur_store_entry(r, cc, n, v, S, St);
   } else if (diag && tid < 240) {
     const int a = tid - 225;
     if (a >= d1) return;
@@ -429,47 +326,14 @@ __global__ __launch_bounds__(256) void k_iba_update(int NK, int NX, const int* _
     scale_v[v] = sc;
     return;
   }
-  const int l = v - NK;
-  const int b = pt_start[l], e = pt_end[l];
-  double sc = 0;
-  double X[3] = {points[3 * (size_t)l], points[3 * (size_t)l + 1], points[3 * (size_t)l + 2]};
-  if (e > b && ok) {
-    double rr[3] = {bl[3 * (size_t)l], bl[3 * (size_t)l + 1], bl[3 * (size_t)l + 2]};
-    for (int k = b; k < e; k++) {
-      const int c = kf_col[edges[k].pose];
-      if (c < 0) continue;
-      const double* H = EB + (size_t)k * kIbaEB;
-      const double* xi = x + col_off[c];
-#pragma unroll
-      for (int cc = 0; cc < 3; cc++) {
-        double s = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++) s += H[3 * a + cc] * xi[a];
-        rr[cc] -= s;
-      }
-    }
-    const double* d = Dinv + 6 * (size_t)l;
-    const double xl[3] = {d[0] * rr[0] + d[1] * rr[1] + d[2] * rr[2], d[1] * rr[0] + d[3] * rr[1] + d[4] * rr[2],
-                          d[2] * rr[0] + d[4] * rr[1] + d[5] * rr[2]};
-#pragma unroll
-    for (int a = 0; a < 3; a++) { sc += xl[a] * (lambda * xl[a] + bl[3 * (size_t)l + a]); X[a] += xl[a]; }
-  }
-  points_out[3 * (size_t)l] = X[0]; points_out[3 * (size_t)l + 1] = X[1]; points_out[3 * (size_t)l + 2] = X[2];
-  scale_v[v] = sc;
+  schur_update_point<kIbaEB>(v - NK, ok, kf_col, [col_off](int c) { return col_off[c]; }, points, x, pt_start, pt_end, edges, EB, Dinv, bl, lambda,
+                             points_out, scale_v + v);
 }
 
 // one workgroup: the sums of the partials and of the scale terms in index order, the solver's flag -> the record
 __global__ __launch_bounds__(256) void k_iba_finish(int n_partial, const double* __restrict__ partial, int n_scale, const double* __restrict__ scale_v,
-                                                    const int* __restrict__ ok_flag, IbaRec* __restrict__ rec) {
-  __shared__ double red[4];
-  const int tid = threadIdx.x;
-  double s = 0;
-  { const int ch = (n_partial + 255) / 256; const int b = min(n_partial, tid * ch), e = min(n_partial, b + ch); for (int i = b; i < e; i++) s += partial[i]; }
-  const double chi = iba_block_sum(s, red);
-  s = 0;
-  { const int ch = (n_scale + 255) / 256; const int b = min(n_scale, tid * ch), e = min(n_scale, b + ch); for (int i = b; i < e; i++) s += scale_v[i]; }
-  const double scale = iba_block_sum(s, red);
-  if (tid == 0) { rec->chi2 = chi; rec->scale = scale; rec->maxdiag = 0; rec->ok = ok_flag ? *ok_flag : 1; }
+                                                    const int* __restrict__ ok_flag, LmRec* __restrict__ rec) {
+  lm_finish_record<false>(n_partial, partial, n_scale, scale_v, 0.0, ok_flag, rec);   // (the user's lambda is always positive: nobody reads maxdiag)
 }
 
 // ImuCamPose::isDepthPositive (S/G2oTypes.cc:187-190) of every visual edge
@@ -535,18 +399,8 @@ int iba_validate(const inertial_ba_problem* p, const inertial_ba_result* r, int*
   if (nF == 0) return ORBG_BAD_ARG;
   if (nF > kIbaMaxFree) return ORBG_CAP_EXCEEDED;
   *n_free = nF; *n_unknowns = n;
-  std::vector<int> stamp((size_t)p->n_keyframes, -1);
-  int prev = -1;
-  for (int k = 0; k < p->n_edges; k++) {
-    const lba_edge& e = p->edges[k];
-    if (e.pose < 0 || e.pose >= p->n_keyframes || e.point < 0 || e.point >= p->n_points) return ORBG_BAD_ARG;
-    if (iba_edge_is_right(e.ur)) return ORBG_BAD_ARG;             // EdgeMono(1), the right camera of a rig: not part of this entry point
-    if (e.point < prev) return ORBG_BAD_ARG;                      // per point, its observations
-    if (stamp[e.pose] == e.point) return ORBG_BAD_ARG;            // one observation per keyframe and point
-    stamp[e.pose] = e.point;
-    prev = e.point;
-  }
-  return ORBG_OK;
+  // (EdgeMono(1), the right camera of a rig: not part of this entry point)
+  return schur_check_edges(p->edges, p->n_edges, p->n_keyframes, p->n_points, iba_edge_is_right);
 }
 
 }  // namespace
@@ -560,18 +414,18 @@ struct inertial_ba_handle {
   DevBuf<PiState> d_kfs[2];
   DevBuf<double> d_points[2];
   DevBuf<int> d_ints, d_ok;               // the structure's integer tables, one upload
-  DevBuf<IbaItem> d_items;
+  DevBuf<SchurItem> d_items;
   DevBuf<IbaPairInertial> d_pies;
   DevBuf<IbaInertial> d_ies;
   DevBuf<PiParams> d_ieP;
   DevBuf<double> d_chi2, d_partial, d_EB, d_IEB, d_Hll, d_bl, d_Hpp, d_bp, d_Dinv, d_Db, d_bs, d_bk, d_x, d_scale_v;
   DevBuf<uint8_t> d_depth;
-  DevBuf<IbaRec> d_rec;
-  PinnedBuf<IbaRec> rec;
+  DevBuf<LmRec> d_rec;
+  PinnedBuf<LmRec> rec;
   std::vector<PiState> s_kfs;
   std::vector<double> s_points;
   std::vector<int> s_ints;
-  std::vector<IbaItem> s_items;
+  std::vector<SchurItem> s_items;
   std::vector<IbaPairInertial> s_pies;
   std::vector<IbaInertial> s_ies;
   std::vector<PiParams> s_ieP;
@@ -683,10 +537,10 @@ struct IbaRun {
         T[o_item_start + q] = (int)h->s_items.size(); T[o_pie_start + q] = (int)h->s_pies.size();
         for (int s = T[o_row_start + i]; s < T[o_row_start + i + 1]; s++) {
           const int ea = T[o_row_edges + s];
-          if (i == j) { h->s_items.push_back(IbaItem{ea, ea}); continue; }
+          if (i == j) { h->s_items.push_back(SchurItem{ea, ea}); continue; }
           const int l = p->edges[ea].point;
           for (int k = T[o_pt_start + l]; k < T[o_pt_end + l]; k++)
-            if (T[o_kf_col + p->edges[k].pose] == j) { h->s_items.push_back(IbaItem{ea, k}); break; }
+            if (T[o_kf_col + p->edges[k].pose] == j) { h->s_items.push_back(SchurItem{ea, k}); break; }
         }
         for (int e = 0; e < nIE; e++) {
           const int ca = T[o_kf_col + h->s_ies[e].k1], cb = T[o_kf_col + h->s_ies[e].k2];
@@ -724,7 +578,7 @@ struct IbaRun {
     ORBG_HIP(hipMemcpyAsync(h->d_ints.p, h->s_ints.data(), sizeof(int) * h->s_ints.size(), hipMemcpyHostToDevice, st));
     if (NX > 0) ORBG_HIP(hipMemcpyAsync(h->d_points[0].p, h->s_points.data(), sizeof(double) * 3 * (size_t)NX, hipMemcpyHostToDevice, st));
     if (NE > 0) ORBG_HIP(hipMemcpyAsync(h->d_edges.p, p->edges, sizeof(lba_edge) * (size_t)NE, hipMemcpyHostToDevice, st));
-    if (!h->s_items.empty()) ORBG_HIP(hipMemcpyAsync(h->d_items.p, h->s_items.data(), sizeof(IbaItem) * h->s_items.size(), hipMemcpyHostToDevice, st));
+    if (!h->s_items.empty()) ORBG_HIP(hipMemcpyAsync(h->d_items.p, h->s_items.data(), sizeof(SchurItem) * h->s_items.size(), hipMemcpyHostToDevice, st));
     if (!h->s_pies.empty()) ORBG_HIP(hipMemcpyAsync(h->d_pies.p, h->s_pies.data(), sizeof(IbaPairInertial) * h->s_pies.size(), hipMemcpyHostToDevice, st));
     if (nIE > 0) {
       ORBG_HIP(hipMemcpyAsync(h->d_ies.p, h->s_ies.data(), sizeof(IbaInertial) * (size_t)nIE, hipMemcpyHostToDevice, st));
@@ -736,12 +590,9 @@ struct IbaRun {
 
   // the record of the last launches, on the host
   int fetch_record() {
-    ORBG_HIP(hipGetLastError());
-    ORBG_HIP(hipMemcpyAsync(h->rec.h, h->d_rec.p, sizeof(IbaRec), hipMemcpyDeviceToHost, st));
-    ORBG_HIP(hipStreamSynchronize(st));
-    h->timer.flush(st);
-    last_chi2 = h->rec.h->chi2;
-    return ORBG_OK;
+    const int rc = lm_fetch_record(h->rec.h, h->d_rec.p, st, h->timer);
+    if (!rc) last_chi2 = h->rec.h->chi2;
+    return rc;
   }
 
   void launch_edges(int buf, bool lin) {
@@ -755,7 +606,7 @@ struct IbaRun {
     h->timer.begin(kPhLin, st);
     launch_edges(cur, true);
     if (NX > 0)
-      hipLaunchKernelGGL(k_iba_points, dim3((NX + 255) / 256), dim3(256), 0, st, NX, tab(o_pt_start), tab(o_pt_end), h->d_EB.p, h->d_Hll.p, h->d_bl.p);
+      hipLaunchKernelGGL(k_schur_points<kIbaEB>, dim3((NX + 255) / 256), dim3(256), 0, st, NX, tab(o_pt_start), tab(o_pt_end), h->d_EB.p, h->d_Hll.p, h->d_bl.p);
     hipLaunchKernelGGL(k_iba_poses, dim3(nF), dim3(256), 0, st, tab(o_row_start), tab(o_row_edges), h->d_EB.p, h->d_Hpp.p, h->d_bp.p);
     hipLaunchKernelGGL(k_iba_finish, dim3(1), dim3(256), 0, st, nbe + nIE, h->d_partial.p, 0, h->d_scale_v.p, (const int*)nullptr, h->d_rec.p);
     h->timer.end(st);
@@ -768,7 +619,7 @@ struct IbaRun {
     int rc;
     h->timer.begin(kPhSchur, st);
     if (NX > 0)
-      hipLaunchKernelGGL(k_iba_dinv, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_Hll.p, h->d_bl.p, lambda, h->d_Dinv.p, h->d_Db.p);
+      hipLaunchKernelGGL(k_schur_dinv, dim3((NX + 255) / 256), dim3(256), 0, st, NX, h->d_Hll.p, h->d_bl.p, lambda, h->d_Dinv.p, h->d_Db.p);
     if ((rc = h->ldlt.clear(h->d_x.p, st))) return rc;
     hipLaunchKernelGGL(k_iba_schur, dim3(n_pairs), dim3(256), 0, st, n, tab(o_pair_i), tab(o_pair_j), tab(o_col_off), tab(o_col_dim), tab(o_item_start),
                        h->d_items.p, tab(o_pie_start), h->d_pies.p, h->d_edges.p, h->d_EB.p, h->d_IEB.p, h->d_Dinv.p, h->d_Db.p, h->d_Hpp.p, h->d_bp.p,
@@ -788,20 +639,15 @@ struct IbaRun {
   }
 
   // ---- what lm_optimize (lm_driver.hpp) asks of a solve
-  const IbaRec& record() const { return *h->rec.h; }
-  int timed_out() const { return LdltSolver::timed_out(h->rec.h->ok) ? kRcLdltTimedOut : ORBG_OK; }
+  const LmRec& record() const { return *h->rec.h; }
+  int timed_out() const { return ldlt_timed_out_rc(h->rec.h->ok); }
   void accept() { cur ^= 1; }
   int first_linearisation(double* user_lambda) {
     *user_lambda = p->large ? 1e-2 : 1e0;          // setUserLambdaInit (S/Optimizer.cc:4690-4701)
     r->chi2_initial = lm.currentChi;               // computeActiveErrors(); err = activeRobustChi2() in front of optimize()
     return ORBG_OK;
   }
-  void iteration_done(int qmax, bool) {
-    if (r->trace && r->trace_len < r->trace_cap) {
-      r->trace[3 * r->trace_len] = lm.lambda; r->trace[3 * r->trace_len + 1] = lm.currentChi; r->trace[3 * r->trace_len + 2] = qmax;
-      r->trace_len++;
-    }
-  }
+  void iteration_done(int qmax, bool) { lm_trace_row(lm, qmax, r->trace, r->trace_cap, &r->trace_len); }
 
   // ---- results: chi2 of the LAST error evaluation, depth test and states of the final estimate, the verdicts
   int download() {

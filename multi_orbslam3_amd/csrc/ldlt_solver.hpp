@@ -92,6 +92,9 @@ struct LdltSolver {
   }
 };
 
+// what a solve's timed_out() (lm_optimize, lm_driver.hpp) answers from the flag of its last record
+inline int ldlt_timed_out_rc(int ok_value) { return LdltSolver::timed_out(ok_value) ? kRcLdltTimedOut : ORBG_OK; }
+
 // Runs `attempt` (a whole solve from the caller's untouched input).  A time-out is not a verdict on the system: the owner of `s`
 // stops using the eight-workgroup kernel -- the ORBG_LDLT_XCD=0 path, parity-tested like the default -- and the attempt runs once more.
 template <class Attempt>

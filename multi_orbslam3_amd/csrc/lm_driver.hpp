@@ -81,6 +81,14 @@ inline bool lm_iteration_continues(LmScalars& m, bool trials_exhausted, double r
   return m.nBad < 3;
 }
 
+// the trace row of an iteration as the bundle adjustments report it: lambda, the chi2 reached, the trials it took
+inline void lm_trace_row(const LmScalars& m, int qmax, double* trace, int cap, int* len) {
+  if (!trace || *len >= cap) return;
+  double* t = trace + 3 * (size_t)*len;
+  t[0] = m.lambda; t[1] = m.currentChi; t[2] = qmax;
+  ++*len;
+}
+
 // SparseOptimizer::optimize with OptimizationAlgorithmLevenberg::solve as its iteration, for the solves that wait for every record
 // (full_ba.hip, essential_graph.hip; the local BA launches ahead of its verdicts and keeps a loop of its own).  Run supplies:
 //   LmScalars lm

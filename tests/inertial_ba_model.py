@@ -675,8 +675,8 @@ def kernel_constant(name):
     return int(re.search(r"constexpr int %s = (\d+);" % name, src).group(1))
 
 
-# The one lap size of the new kernels: kIbaThreads visual edges per workgroup of k_iba_edges, points per workgroup of k_iba_points /
-# k_iba_dinv / k_iba_update, edges of a keyframe per pass of k_iba_poses, items of a pair per pass of k_iba_schur.  With every point seen
+# The one lap size of the new kernels: kIbaThreads visual edges per workgroup of k_iba_edges, points per workgroup of k_schur_points /
+# k_schur_dinv / k_iba_update, edges of a keyframe per pass of k_iba_poses, items of a pair per pass of k_iba_schur.  With every point seen
 # by all three keyframes, n_points is at once the points, the edges of each keyframe and the items of each pair; the edge list has
 # three times as many entries (one below, at and one above three full workgroups).
 LAP = kernel_constant("kIbaThreads")
