@@ -1594,6 +1594,78 @@ int inertial_ba_get_phase_ms(inertial_ba_handle* h, double* ms /*5: structure, l
  * (9-11) and EdgeAccRW (12-14) -- columns: keyframe prev's 15, this keyframe's 15, the error in column 30.  No device needed. */
 int inertial_ba_host_linearize(const inertial_ba_problem* p, double* vis, double* inertial);
 
+/* ---------------------------------------------------------------- inertial initialisation (what makes the two optimisers above reachable)
+ *
+ * Optimizer::InertialOptimization, four overloads (S/Optimizer.cc:5344, :5534, :5696, :5858): what LocalMapping::InitializeIMU calls
+ * three times per session (S/LocalMapping.cc:1492), LocalMapping::ScaleRefinement every 10 s (:1618) and LoopClosing after a merge
+ * (S/LoopClosing.cc:2170).  Every pose is fixed; each keyframe with an mPrevKF adds one EdgeInertialGS (S/G2oTypes.cc:802-927) over the two
+ * velocities, ONE gyro bias, ONE accelerometer bias, the gravity direction (VertexGDir, 2 unknowns) and the scale (VertexScale, 1).  The
+ * overloads differ only in what is free, the algorithm and the iteration count:
+ *   (Map, Rwg, scale, bg, ba, bMono, cov, bFixedVel, bGauss, priorG, priorA): LM, 200 iterations, lambda_init = priorG != 0 ? 1e3 : auto;
+ *       free_velocity = free_bias = !bFixedVel, free_gdir = 1, free_scale = bMono, with_priors = 1
+ *   (Map, bg, ba, priorG, priorA) and (vector<KeyFrame*>, bg, ba, priorG, priorA): LM, 200, lambda_init = 1e3; free_velocity = free_bias
+ *       = 1, free_gdir = free_scale = 0 with Rwg = I and scale = 1, with_priors = 1
+ *   (Map, Rwg, scale): Gauss-Newton, 10 iterations; free_gdir = free_scale = 1 only, with_priors = 0 */
+#define INERTIAL_INIT_MAX_KEYFRAMES 4096       /* above ba_solve's 1365 and eg_solve's 1170: no map the other solvers accept is refused here */
+enum { INERTIAL_INIT_LM = 0, INERTIAL_INIT_GN = 1 };
+
+typedef struct inertial_init_edge {
+  int32_t k1, k2;              /* index of pKFi->mPrevKF and of pKFi in keyframes[] */
+  pose_inertial_preint preint; /* pKFi->mpImuPreintegrated after SetNewBias(mPrevKF->GetImuBias()) */
+  double info9[81];            /* orbg_imu_information(pKFi->mpImuPreintegrated->C): the EdgeInertialGS constructor (S/G2oTypes.cc:809-821)
+                                  conditions its information exactly as EdgeInertial's (:702-714) */
+} inertial_init_edge;
+
+typedef struct inertial_init_problem {
+  uint32_t struct_size;        /* sizeof(inertial_init_problem) */
+  int32_t device;
+  int32_t algorithm;           /* INERTIAL_INIT_LM / INERTIAL_INIT_GN */
+  int32_t iterations;          /* its */
+  double lambda_init;          /* setUserLambdaInit; <= 0 = auto (tau * the largest diagonal entry) */
+  int32_t free_velocity;       /* !VV->fixed(): the velocity of every keyframe that has an edge */
+  int32_t free_bias;           /* !VG->fixed() && !VA->fixed() */
+  int32_t free_gdir;           /* !VGDir->fixed() */
+  int32_t free_scale;          /* !VS->fixed() */
+  int32_t with_priors;         /* EdgePriorAcc / EdgePriorGyro toward 0 exist; they are active only while the biases are free */
+  double prior_g, prior_a;     /* infoPriorG, infoPriorA (>= 0) */
+  float bg[3], ba[3];          /* vpKFs.front()'s bias: EVERY bias vertex is constructed from it */
+  double Rwg[9], scale;        /* VertexGDir's and VertexScale's estimates, row-major */
+  int32_t n_keyframes;
+  const pose_inertial_state* keyframes;   /* Rwb, twb, vwb; bg and ba are not read */
+  int32_t n_edges;
+  const inertial_init_edge* edges;        /* in creation order */
+} inertial_init_problem;
+
+typedef struct inertial_init_result {
+  uint32_t struct_size;        /* sizeof(inertial_init_result) */
+  int32_t  iters;              /* iterations run (a Gauss-Newton iteration whose solve failed included) */
+  int32_t  n_unknowns;         /* 3 per free velocity in the system + 6 / 2 / 1 for the free biases / direction / scale */
+  int32_t  solve_failed;       /* Gauss-Newton met a pivot that is not positive: no update was applied, the run ended */
+  double*  vwb;                /* n_keyframes x 3 (caller-allocated); a keyframe without an edge, and every keyframe when the
+                                  velocities are fixed, comes back as it went in */
+  double   bg[3], ba[3], Rwg[9], scale;
+  double   chi2_first;         /* chi2 of the first linearisation */
+  double   chi2_final;         /* chi2 of the estimates returned */
+  double*  trace;              /* optional, trace_cap x 3 as inertial_ba_result's: lambda, chi2 and the trials of every iteration
+                                  (Gauss-Newton: 0, the chi2 the iteration linearised at, 1) */
+  int32_t  trace_cap, trace_len;
+} inertial_init_result;
+
+/* optimizer.optimize(its) of Optimizer::InertialOptimization: g2o's Levenberg-Marquardt as the bundle adjustments run it (ten trials per
+ * iteration, _nBad >= 3, rho == 0) or Gauss-Newton (one update per iteration).  ONE kernel launch and one wait per call: the system
+ * (3 x 3 velocity blocks along the mPrevKF forest, a border of up to 9 columns) is eliminated in an order without fill and never formed
+ * densely.  One deviation: a pivot that is not positive and finite refuses the solve -- under LM the trial counts as failed, under
+ * Gauss-Newton no update is applied, solve_failed is set and the run ends (the reference applies an undefined update there; the same
+ * deviation pose_inertial_optimize documents).  Refused before a device is looked for: ORBG_BAD_ARG (a NULL array, struct_size, an
+ * index out of range, a keyframe that is k2 of two edges, a cycle, no free unknown, no edge), ORBG_CAP_EXCEEDED (more than
+ * INERTIAL_INIT_MAX_KEYFRAMES keyframes).  A keyframe that is k1 of several edges is accepted.  Two solves of the same problem return the
+ * same bits. */
+int inertial_init_solve(const inertial_init_problem* p, inertial_init_result* r);
+/* TEST AID, not part of the stable interface: the kernel's edge arithmetic, compiled for the host, at the estimates handed in.
+ * J: n_edges x 9 x 16 row-major, per edge the columns [v1 3 | v2 3 | bg 3 | ba 3 | gdir 2 | s 1 | e 1] of EdgeInertialGS, every vertex taken
+ * as free.  No device needed. */
+int inertial_init_host_linearize(const inertial_init_problem* p, double* J);
+
 /* ---------------------------------------------------------------- streams, hardware queues, host threads
  * Streams.  Every handle enqueues its work on ONE HIP stream.  By default that stream comes from a per-device pool the library
  * creates with its first handle: four hipStreamNonBlocking streams -- L (local BA handles), E0 / E1 (extractor handles,
@@ -1636,6 +1708,7 @@ int orbv_vocab_set_stream(orbv_vocab* v, void* hip_stream);
 int orbd_database_set_stream(orbd_database* d, void* hip_stream);
 int pose_opt_set_stream(int device, void* hip_stream);      /* the calling thread's pose_optimize calls on `device` */
 int pose_inertial_set_stream(int device, void* hip_stream); /* the calling thread's pose_inertial_optimize calls on `device` */
+int inertial_init_set_stream(int device, void* hip_stream); /* the calling thread's inertial_init_solve calls on `device` */
 
 /* ---------------------------------------------------------------- misc */
 const char* orbg_version(void);

@@ -3,6 +3,7 @@
 //   int Optimizer::PoseInertialOptimizationLastKeyFrame(Frame *pFrame, bool bRecInit = false)   I/Optimizer.h, S/Optimizer.cc:7603-7996
 //   int Optimizer::PoseInertialOptimizationLastFrame(Frame *pFrame, bool bRecInit = false)      I/Optimizer.h, S/Optimizer.cc:7998-8424
 //   void Optimizer::LocalInertialBA(KeyFrame *pKF, bool *pbStopFlag, Map *pMap, bool bLarge, bool bRecInit)   S/Optimizer.cc:4556-5226
+//   void Optimizer::InertialOptimization(...), four overloads                                               S/Optimizer.cc:5344-5958
 //
 // Collect what :7659-7815 / :8040-8226 read, call pose_inertial_optimize (include/orbgpu.h), write back what :7949-7993 / :8361-8421
 // write.  Matrices are read through mat_f32(m) (a const float* to row-major data, found by argument-dependent lookup or the cv::Mat
@@ -14,6 +15,7 @@
 #include <cstdint>
 #include <cstring>
 #include <algorithm>
+#include <cmath>
 #include <list>
 #include <map>
 #include <mutex>
@@ -351,6 +353,166 @@ void LocalInertialBA(KeyFrameT* pKF, bool* pbStopFlag, MapT* pMap, bool bLarge =
     lLocalMapPoints[l]->UpdateNormalAndDepth();
   }
   pMap->IncreaseChangeIndex();
+}
+
+// ---------------------------------------------------------------------------------------------- InertialOptimization
+//   void Optimizer::InertialOptimization(Map*, Eigen::Matrix3d &Rwg, double &scale, Eigen::Vector3d &bg, Eigen::Vector3d &ba, bool bMono,
+//                                        Eigen::MatrixXd &covInertial, bool bFixedVel, bool bGauss, float priorG, float priorA)   S/Optimizer.cc:5344
+//   void Optimizer::InertialOptimization(Map*, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG, float priorA)              :5534
+//   void Optimizer::InertialOptimization(vector<KeyFrame*>, Eigen::Vector3d &bg, Eigen::Vector3d &ba, float priorG, float priorA) :5696
+//   void Optimizer::InertialOptimization(Map*, Eigen::Matrix3d &Rwg, double &scale)                                               :5858
+namespace inertial {
+
+// the library calls of the inertial initialisation; a test replaces them to look at what the glue hands over
+struct InitGpuOps {
+  static int solve(const inertial_init_problem& p, inertial_init_result& r) { return inertial_init_solve(&p, &r); }
+  static int information(const float* C, double* i9, double* ig, double* ia) { return orbg_imu_information(C, i9, ig, ia); }
+};
+
+// What the four overloads share.  P comes in with its switches set.  Vertices: every keyframe of the list (map_filter: those with mnId <=
+// maxKFid), found again by mnId as g2o finds them.  Edges: a keyframe with an mPrevKF and mnId <= maxKFid, neither bad nor behind a
+// predecessor beyond maxKFid; set_bias: the SetNewBias(mPrevKF->GetImuBias()) side effect of the first three overloads, applied BEFORE
+// the vertices are looked up, so also to an edge that is then skipped because its predecessor is not in the list (:5782-5796).  Every
+// bias vertex is constructed from vpKFs.front().  Returns the velocities per listed keyframe (index as in `listed`).
+template <class Ops, class KeyFrameT>
+struct InitSolve {
+  std::vector<KeyFrameT*> listed;
+  std::vector<double> vwb;
+  inertial_init_result R;
+  void run(const std::vector<KeyFrameT*>& vpKFs, unsigned long maxKFid, bool map_filter, bool set_bias, inertial_init_problem& P) {
+    if (vpKFs.empty()) throw std::runtime_error("orbgpu inertial: InertialOptimization without keyframes");
+    std::map<unsigned long, int> index;
+    std::vector<pose_inertial_state> kfs;
+    for (KeyFrameT* pKFi : vpKFs) {
+      if (map_filter && pKFi->mnId > maxKFid) continue;
+      pose_inertial_state s;
+      read_keyframe_state(pKFi, &s);
+      index[pKFi->mnId] = (int)kfs.size();
+      kfs.push_back(s); listed.push_back(pKFi);
+    }
+    std::vector<inertial_init_edge> edges;
+    for (KeyFrameT* pKFi : vpKFs) {
+      if (!(pKFi->mPrevKF && pKFi->mnId <= maxKFid)) continue;
+      if (pKFi->isBad() || pKFi->mPrevKF->mnId > maxKFid) continue;
+      if (!pKFi->mpImuPreintegrated) throw std::runtime_error("orbgpu inertial: a keyframe has no preintegration");   // (the reference dereferences NULL)
+      if (set_bias) pKFi->mpImuPreintegrated->SetNewBias(pKFi->mPrevKF->GetImuBias());
+      const auto i1 = index.find(pKFi->mPrevKF->mnId), i2 = index.find(pKFi->mnId);
+      if (i1 == index.end() || i2 == index.end()) continue;                        // a vertex is missing
+      inertial_init_edge e;
+      std::memset(&e, 0, sizeof(e));
+      e.k1 = i1->second; e.k2 = i2->second;
+      read_preintegration(pKFi->mpImuPreintegrated, &e.preint);
+      double ig[9], ia[9];
+      check(Ops::information(mat_f32(pKFi->mpImuPreintegrated->C), e.info9, ig, ia), "orbg_imu_information");
+      edges.push_back(e);
+    }
+    const auto g = vpKFs.front()->GetGyroBias(); const auto a = vpKFs.front()->GetAccBias();
+    std::memcpy(P.bg, mat_f32(g), sizeof(P.bg)); std::memcpy(P.ba, mat_f32(a), sizeof(P.ba));
+    P.struct_size = sizeof(P); P.device = 0;
+    P.n_keyframes = (int32_t)kfs.size(); P.keyframes = kfs.data(); P.n_edges = (int32_t)edges.size(); P.edges = edges.data();
+    vwb.assign(3 * kfs.size() + 3, 0.0);
+    std::memset(&R, 0, sizeof(R));
+    R.struct_size = sizeof(R); R.vwb = vwb.data();
+    check(Ops::solve(P, R), "InertialOptimization");
+    R.vwb = nullptr;
+  }
+  // :5506-5530: SetVelocity, then SetNewBias -- behind a Reintegrate() when the gyro bias moved by more than 0.01 (cv::norm of a float
+  // difference, summed in double)
+  void write_back(unsigned long maxKFid) {
+    typedef typename std::decay<decltype(listed[0]->GetImuBias())>::type BiasT;
+    typedef typename std::decay<decltype(listed[0]->GetVelocity())>::type MatT;
+    const BiasT b((float)R.ba[0], (float)R.ba[1], (float)R.ba[2], (float)R.bg[0], (float)R.bg[1], (float)R.bg[2]);   // IMU::Bias takes (ba, bg)
+    for (size_t i = 0; i < listed.size(); i++) {
+      KeyFrameT* pKFi = listed[i];
+      if (pKFi->mnId > maxKFid) continue;
+      const float vf[3] = {(float)vwb[3 * i], (float)vwb[3 * i + 1], (float)vwb[3 * i + 2]};
+      MatT mv;
+      make_mat(mv, 3, 1, vf);
+      pKFi->SetVelocity(mv);
+      const auto og = pKFi->GetGyroBias();
+      const float* o = mat_f32(og);
+      double n2 = 0;
+      for (int k = 0; k < 3; k++) { const float d = o[k] - (float)R.bg[k]; n2 += (double)d * (double)d; }
+      pKFi->SetNewBias(b);
+      if (std::sqrt(n2) > 0.01 && pKFi->mpImuPreintegrated) pKFi->mpImuPreintegrated->Reintegrate();
+    }
+  }
+};
+
+inline void init_switches(inertial_init_problem* P, int algorithm, int its, double lambda, bool v, bool b, bool g, bool s, bool priors, float priorG, float priorA) {
+  std::memset(P, 0, sizeof(*P));
+  P->algorithm = algorithm; P->iterations = its; P->lambda_init = lambda;
+  P->free_velocity = v; P->free_bias = b; P->free_gdir = g; P->free_scale = s;
+  P->with_priors = priors; P->prior_g = (double)priorG; P->prior_a = (double)priorA;
+  P->Rwg[0] = P->Rwg[4] = P->Rwg[8] = 1.0; P->scale = 1.0;
+}
+
+}  // namespace inertial
+
+// covInertial is accepted and not touched, bGauss is not read: the reference reads neither.
+template <class Ops = inertial::InitGpuOps, class MapT, class Mat3T, class Vec3T, class CovT>
+void InertialOptimization(MapT* pMap, Mat3T& Rwg, double& scale, Vec3T& bg, Vec3T& ba, bool bMono, CovT& covInertial, bool bFixedVel = false,
+                          bool bGauss = false, float priorG = 1e2, float priorA = 1e6) {
+  using namespace inertial;
+  (void)covInertial; (void)bGauss;
+  const unsigned long maxKFid = pMap->GetMaxKFid();
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  typedef typename std::remove_pointer<typename std::decay<decltype(vpKFs)>::type::value_type>::type KeyFrameT;
+  inertial_init_problem P;
+  init_switches(&P, INERTIAL_INIT_LM, 200, priorG != 0.f ? 1e3 : 0.0, !bFixedVel, !bFixedVel, true, bMono, true, priorG, priorA);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) P.Rwg[3 * i + j] = Rwg(i, j);
+  P.scale = scale;
+  InitSolve<Ops, KeyFrameT> S;
+  S.run(vpKFs, maxKFid, true, true, P);
+  scale = S.R.scale;
+  for (int i = 0; i < 3; i++) { bg(i) = S.R.bg[i]; ba(i) = S.R.ba[i]; for (int j = 0; j < 3; j++) Rwg(i, j) = S.R.Rwg[3 * i + j]; }
+  S.write_back(maxKFid);
+}
+
+namespace inertial {
+template <class Ops, class KeyFrameT, class Vec3T>
+void init_bias_only(const std::vector<KeyFrameT*>& vpKFs, unsigned long maxKFid, bool map_filter, Vec3T& bg, Vec3T& ba, float priorG, float priorA) {
+  inertial_init_problem P;
+  init_switches(&P, INERTIAL_INIT_LM, 200, 1e3, true, true, false, false, true, priorG, priorA);
+  InitSolve<Ops, KeyFrameT> S;
+  S.run(vpKFs, maxKFid, map_filter, true, P);
+  for (int i = 0; i < 3; i++) { bg(i) = S.R.bg[i]; ba(i) = S.R.ba[i]; }
+  S.write_back(maxKFid);
+}
+}  // namespace inertial
+
+template <class Ops = inertial::InitGpuOps, class MapT, class Vec3T>
+void InertialOptimization(MapT* pMap, Vec3T& bg, Vec3T& ba, float priorG = 1e2, float priorA = 1e6) {
+  const unsigned long maxKFid = pMap->GetMaxKFid();
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  typedef typename std::remove_pointer<typename std::decay<decltype(vpKFs)>::type::value_type>::type KeyFrameT;
+  inertial::init_bias_only<Ops, KeyFrameT>(vpKFs, maxKFid, true, bg, ba, priorG, priorA);
+}
+
+// the list's keyframes all get vertices, beyond maxKFid too (:5716-5731: the filter is commented out); an edge whose predecessor is not
+// in the list is skipped (:5791)
+template <class Ops = inertial::InitGpuOps, class KeyFrameT, class Vec3T>
+void InertialOptimization(std::vector<KeyFrameT*> vpKFs, Vec3T& bg, Vec3T& ba, float priorG = 1e2, float priorA = 1e6) {
+  if (vpKFs.empty()) throw std::runtime_error("orbgpu inertial: InertialOptimization without keyframes");
+  const unsigned long maxKFid = vpKFs[0]->GetMap()->GetMaxKFid();
+  inertial::init_bias_only<Ops, KeyFrameT>(vpKFs, maxKFid, false, bg, ba, priorG, priorA);
+}
+
+// Gauss-Newton on the gravity direction and the scale alone; no keyframe is written
+template <class Ops = inertial::InitGpuOps, class MapT, class Mat3T>
+void InertialOptimization(MapT* pMap, Mat3T& Rwg, double& scale) {
+  using namespace inertial;
+  const unsigned long maxKFid = pMap->GetMaxKFid();
+  const auto vpKFs = pMap->GetAllKeyFrames();
+  typedef typename std::remove_pointer<typename std::decay<decltype(vpKFs)>::type::value_type>::type KeyFrameT;
+  inertial_init_problem P;
+  init_switches(&P, INERTIAL_INIT_GN, 10, 0.0, false, false, true, true, false, 0.f, 0.f);
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) P.Rwg[3 * i + j] = Rwg(i, j);
+  P.scale = scale;
+  InitSolve<Ops, KeyFrameT> S;
+  S.run(vpKFs, maxKFid, true, false, P);
+  scale = S.R.scale;
+  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Rwg(i, j) = S.R.Rwg[3 * i + j];
 }
 
 }  // namespace orbgpu

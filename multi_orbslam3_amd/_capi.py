@@ -254,6 +254,38 @@ INERTIAL_BA_MAX_FREE_KEYFRAMES = 32
 INERTIAL_BA_MAX_EDGES = 1 << 22
 
 
+class InertialInitEdge(C.Structure):
+    _fields_ = [("k1", C.c_int32), ("k2", C.c_int32), ("preint", PoseInertialPreint), ("info9", C.c_double * 81)]
+
+
+class InertialInitProblem(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("algorithm", C.c_int32), ("iterations", C.c_int32),
+                ("lambda_init", C.c_double), ("free_velocity", C.c_int32), ("free_bias", C.c_int32), ("free_gdir", C.c_int32),
+                ("free_scale", C.c_int32), ("with_priors", C.c_int32), ("prior_g", C.c_double), ("prior_a", C.c_double),
+                ("bg", C.c_float * 3), ("ba", C.c_float * 3), ("Rwg", C.c_double * 9), ("scale", C.c_double), ("n_keyframes", C.c_int32),
+                ("keyframes", C.c_void_p), ("n_edges", C.c_int32), ("edges", C.c_void_p)]
+
+
+class InertialInitResult(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iters", C.c_int32), ("n_unknowns", C.c_int32), ("solve_failed", C.c_int32),
+                ("vwb", C.c_void_p), ("bg", C.c_double * 3), ("ba", C.c_double * 3), ("Rwg", C.c_double * 9), ("scale", C.c_double),
+                ("chi2_first", C.c_double), ("chi2_final", C.c_double), ("trace", C.c_void_p), ("trace_cap", C.c_int32),
+                ("trace_len", C.c_int32)]
+
+
+INERTIAL_INIT_MAX_KEYFRAMES = 4096
+INERTIAL_INIT_LM, INERTIAL_INIT_GN = 0, 1
+# pose_inertial_state as an array element: Rwb (9), twb, vwb, bg, ba (3 each), float
+INERTIAL_INIT_STATE_FLOATS = 21
+# inertial_init_edge as a numpy record, with the C compiler's alignment (held against the ctypes structure below)
+INERTIAL_INIT_EDGE_DTYPE = np.dtype([("k1", "<i4"), ("k2", "<i4"), ("dT", "<f4"), ("dR", "<f4", (9,)), ("dV", "<f4", (3,)), ("dP", "<f4", (3,)),
+                                     ("JRg", "<f4", (9,)), ("JVg", "<f4", (9,)), ("JVa", "<f4", (9,)), ("JPg", "<f4", (9,)),
+                                     ("JPa", "<f4", (9,)), ("bg", "<f4", (3,)), ("ba", "<f4", (3,)), ("info9", "<f8", (81,))], align=True)
+assert INERTIAL_INIT_EDGE_DTYPE.itemsize == C.sizeof(InertialInitEdge)
+assert INERTIAL_INIT_EDGE_DTYPE.fields["info9"][1] == InertialInitEdge.info9.offset
+assert C.sizeof(PoseInertialState) == 4 * INERTIAL_INIT_STATE_FLOATS
+
+
 class DatabaseView(C.Structure):
     _fields_ = [("n_kfs", C.c_int32), ("n_words", C.c_int32), ("inv_start", C.c_void_p), ("inv_kf", C.c_void_p),
                 ("bow_start", C.c_void_p), ("bow_word", C.c_void_p), ("bow_value", C.c_void_p), ("covis_start", C.c_void_p),
@@ -462,6 +494,9 @@ ESSENTIAL_GRAPH_SYMBOLS = ["eg_solve", "eg_set_profiling", "eg_get_phase_ms"]
 INERTIAL_BA_SYMBOLS = ["inertial_ba_solve", "inertial_ba_create", "inertial_ba_destroy", "inertial_ba_solve_h", "inertial_ba_set_stream",
                        "inertial_ba_set_profiling", "inertial_ba_get_phase_ms", "inertial_ba_host_linearize"]
 
+# The inertial initialisation (prefix inertial_init_), likewise; tests/test_inertial_init_cpu.py holds it against the header.
+INERTIAL_INIT_SYMBOLS = ["inertial_init_solve", "inertial_init_host_linearize", "inertial_init_set_stream"]
+
 # MLPnPsolver (prefix orbp_), likewise; tests/test_mlpnp_cpu.py holds it against the header.
 MLPNP_SYMBOLS = ["orbp_mlpnp_create", "orbp_mlpnp_destroy", "orbp_mlpnp_set_stream", "orbp_mlpnp_set_problem",
                  "orbp_mlpnp_set_ransac_parameters", "orbp_mlpnp_ransac_iterations", "orbp_mlpnp_iterations_of_call",
@@ -533,13 +568,16 @@ def load():
     lib.inertial_ba_set_profiling.argtypes = [C.c_void_p, C.c_int]
     lib.inertial_ba_get_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
     lib.inertial_ba_host_linearize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.inertial_init_solve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.inertial_init_host_linearize.argtypes = [C.c_void_p, C.c_void_p]
+    lib.inertial_init_set_stream.argtypes = [C.c_int, C.c_void_p]
     lib.eg_solve.argtypes = [C.c_void_p, C.c_void_p]
     lib.eg_set_profiling.argtypes = [C.c_int]
     lib.eg_get_phase_ms.argtypes = [C.c_void_p]
     lib.orbp_mlpnp_set_ransac_parameters.argtypes = [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float]
     lib.orbp_mlpnp_ransac_iterations.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
     lib.orbp_mlpnp_gn.argtypes = [C.c_int] + [C.c_void_p] * 6
-    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS + MLPNP_SYMBOLS + INERTIAL_BA_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + INITIALISER_SYMBOLS + FULL_BA_SYMBOLS + ESSENTIAL_GRAPH_SYMBOLS + MLPNP_SYMBOLS + INERTIAL_BA_SYMBOLS + INERTIAL_INIT_SYMBOLS:
         fn = getattr(lib, name)
         if name not in ("orbg_version", "orbg_strerror"):
             fn.restype = C.c_int

@@ -978,6 +978,22 @@ class Optimizer:
 
     inertial_ba_solve = LocalInertialBA
 
+    def InertialOptimization(self, problem, trace_cap=200):
+        """optimizer.optimize(its) of the four void Optimizer::InertialOptimization(...) overloads (S/Optimizer.cc:5344-5958), as the
+        problem's switches say; problem: views.inertial_init_problem(...)[0].  Returns a views.InertialInitOutput: the velocities, the
+        biases, Rwg and scale, the iterations and the LM trace."""
+        out = views.InertialInitOutput(problem, trace_cap)
+        capi.check(self.lib.inertial_init_solve(C.byref(problem), C.byref(out.c)), "inertial_init_solve")
+        return out
+
+    inertial_init_solve = InertialOptimization
+
+    def inertial_init_linearize(self, problem):
+        """TEST AID (inertial_init_host_linearize): per edge the 9 x 16 block [v1 | v2 | bg | ba | gdir | s | e]; needs no device."""
+        J = np.zeros((max(problem.n_edges, 1), 9, 16))
+        capi.check(self.lib.inertial_init_host_linearize(C.byref(problem), capi.ptr(J)), "inertial_init_host_linearize")
+        return J[: problem.n_edges]
+
     def imu_information(self, C15):
         """info9, infoG, infoA of an IMU::Preintegrated's covariance C (15 x 15 float), as the edges hold them (orbg_imu_information)."""
         Cf = np.ascontiguousarray(np.asarray(C15, np.float32).reshape(225))

@@ -275,3 +275,109 @@ PI_HD __forceinline__ void pi_visual_hessian(const PiVis& o, const PiParams& P, 
 #pragma unroll
   for (int a = 0; a < 6; a++) acc[q++] -= Jm[a] * (w * o.e[0]) + Jm[6 + a] * (w * o.e[1]) + Jm[12 + a] * (w * o.e[2]);
 }
+
+// ---- Optimizer::InertialOptimization (inertial_init.hip): EdgeInertialGS (S/G2oTypes.cc:802-927) between two FIXED poses.  What one edge
+// reads of its IMU::Preintegrated, widened to double by the host, and its information (orbg_imu_information: the constructor at
+// :809-821 conditions it exactly as EdgeInertial's at :702-714 does).
+struct PiGsEdge {
+  int k1, k2;                          // mPrevKF, the keyframe
+  double dT, dR[9], dV[3], dP[3], JRg[9], JVg[9], JVa[9], JPg[9], JPa[9], lbg[3], lba[3];
+  double info9[81];
+};
+constexpr int kGsLd = 16;              // row stride of an edge's 9 x 16 block: [v1 3 | v2 3 | bg 3 | ba 3 | gdir 2 | s 1 | e 1]
+enum { kGsColV1 = 0, kGsColV2 = 3, kGsColBg = 6, kGsColBa = 9, kGsColGd = 12, kGsColS = 14, kGsColE = 15 };
+enum { kGsVel = 1, kGsBias = 2, kGsGdir = 4, kGsScale = 8, kGsAll = 15 };   // the column groups whose vertices are free
+
+// EdgeInertialGS::computeError (:826-849) -> column kGsColE of J, and linearizeOplus (:851-927) for the column groups in `groups` (a fixed
+// vertex is not a variable: its columns are neither computed nor written).  R1, t1, v1: mPrevKF's; R2, t2, v2: the keyframe's; bg, ba: the
+// one bias every edge shares; Rwg, s: VertexGDir's and VertexScale's estimates.  The pose columns do not exist: every pose is fixed.
+PI_HD inline void pi_inertial_gs_edge(const PiGsEdge& E, const double* R1, const double* t1, const double* v1, const double* R2, const double* t2,
+                                      const double* v2, const double* bg, const double* ba, const double* Rwg, double s, int groups, double* J) {
+  const double dt = E.dT, G = (double)9.81f;                                          // IMU::GRAVITY_VALUE is a float
+  double dbg[3], dba[3], g[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) { dbg[i] = bg[i] - E.lbg[i]; dba[i] = ba[i] - E.lba[i]; g[i] = Rwg[3 * i + 2] * -G; }   // Rwg gI, gI = (0, 0, -G)
+  double w[3], X[9], dR[9], a[3], c[3], dV[3], dP[3];
+  m3_vec(E.JRg, dbg, w);
+  pi_exp_so3(w, X);
+  m3_mul(E.dR, X, dR);
+  pi_normalize_rotation(dR);
+  m3_vec(E.JVg, dbg, a); m3_vec(E.JVa, dba, c);
+#pragma unroll
+  for (int i = 0; i < 3; i++) dV[i] = E.dV[i] + a[i] + c[i];
+  m3_vec(E.JPg, dbg, a); m3_vec(E.JPa, dba, c);
+#pragma unroll
+  for (int i = 0; i < 3; i++) dP[i] = E.dP[i] + a[i] + c[i];
+  double R12[9], eR[9], er[3];
+  m3_tmul(R1, R2, R12);
+  m3_tmul(dR, R12, eR);
+  pi_log_so3(eR, er);
+  double dvv[3], dpp[3], dv[3], dp[3], rv[3], rp[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    dvv[i] = v2[i] - v1[i];
+    dpp[i] = t2[i] - t1[i] - v1[i] * dt;
+    dv[i] = s * dvv[i] - g[i] * dt;
+    dp[i] = s * dpp[i] - g[i] * dt * dt / 2;
+  }
+  m3_tvec(R1, dv, rv);
+  m3_tvec(R1, dp, rp);
+#pragma unroll
+  for (int i = 0; i < 3; i++) { J[i * kGsLd + kGsColE] = er[i]; J[(3 + i) * kGsLd + kGsColE] = rv[i] - dV[i]; J[(6 + i) * kGsLd + kGsColE] = rp[i] - dP[i]; }
+  if (groups & kGsVel) {
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const double rb = R1[3 * j + i];                                              // Rbw1
+        J[i * kGsLd + kGsColV1 + j] = 0.0; J[(3 + i) * kGsLd + kGsColV1 + j] = -s * rb; J[(6 + i) * kGsLd + kGsColV1 + j] = -s * rb * dt;
+        J[i * kGsLd + kGsColV2 + j] = 0.0; J[(3 + i) * kGsLd + kGsColV2 + j] = s * rb; J[(6 + i) * kGsLd + kGsColV2 + j] = 0.0;
+      }
+  }
+  if (groups & kGsBias) {
+    double invJr[9], Jr[9], T[9], S[9];
+    pi_inv_right_jacobian(er, invJr);
+    pi_right_jacobian(w, Jr);
+    m3_mult(invJr, eR, T);                                                            // invJr eR^T
+    m3_mul(T, Jr, S);
+    m3_mul(S, E.JRg, T);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        const int k = 3 * i + j;
+        J[i * kGsLd + kGsColBg + j] = -T[k]; J[(3 + i) * kGsLd + kGsColBg + j] = -E.JVg[k]; J[(6 + i) * kGsLd + kGsColBg + j] = -E.JPg[k];
+        J[i * kGsLd + kGsColBa + j] = 0.0; J[(3 + i) * kGsLd + kGsColBa + j] = -E.JVa[k]; J[(6 + i) * kGsLd + kGsColBa + j] = -E.JPa[k];
+      }
+  }
+  if (groups & kGsGdir) {
+    // dGdTheta = Rwg Gm, Gm(0, 1) = -G, Gm(1, 0) = G
+    double d0[3], d1[3], r0[3], r1[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) { d0[i] = Rwg[3 * i + 1] * G; d1[i] = Rwg[3 * i] * -G; }
+    m3_tvec(R1, d0, r0);
+    m3_tvec(R1, d1, r1);
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      J[i * kGsLd + kGsColGd] = 0.0; J[i * kGsLd + kGsColGd + 1] = 0.0;
+      J[(3 + i) * kGsLd + kGsColGd] = -r0[i] * dt; J[(3 + i) * kGsLd + kGsColGd + 1] = -r1[i] * dt;
+      J[(6 + i) * kGsLd + kGsColGd] = -0.5 * r0[i] * dt * dt; J[(6 + i) * kGsLd + kGsColGd + 1] = -0.5 * r1[i] * dt * dt;
+    }
+  }
+  if (groups & kGsScale) {
+    double r0[3], r1[3];
+    m3_tvec(R1, dvv, r0);
+    m3_tvec(R1, dpp, r1);
+#pragma unroll
+    for (int i = 0; i < 3; i++) { J[i * kGsLd + kGsColS] = 0.0; J[(3 + i) * kGsLd + kGsColS] = r0[i]; J[(6 + i) * kGsLd + kGsColS] = r1[i]; }
+  }
+}
+// GDirection::Update (I/G2oTypes.h:261-264): Rwg ExpSO3(u0, u1, 0); VertexScale::oplusImpl (:311-313): s exp(u)
+PI_HD inline void pi_gdir_oplus(double* Rwg, double u0, double u1) {
+  const double u[3] = {u0, u1, 0.0};
+  double X[9], Rn[9];
+  pi_exp_so3(u, X);
+  m3_mul(Rwg, X, Rn);
+#pragma unroll
+  for (int i = 0; i < 9; i++) Rwg[i] = Rn[i];
+}

@@ -445,6 +445,66 @@ def inertial_ba_problem(keyframes, points, edges, close, cam, Tcb, rec_init=Fals
     return p, [K, pts, E, cl]
 
 
+def inertial_init_problem(keyframes, edges, bg, ba, Rwg=None, scale=1.0, algorithm=0, iterations=200, lambda_init=0.0, free_velocity=True,
+                          free_bias=True, free_gdir=True, free_scale=True, with_priors=True, prior_g=0.0, prior_a=0.0, device=0):
+    """inertial_init_problem of include/orbgpu.h.  keyframes: a list of dicts Rwb, twb, vwb (or an (n, 21) float32 array of
+    pose_inertial_state); edges: a list of dicts k1, k2, preint (dict as for pose_inertial_problem), info9 (orbg_imu_information(C)), or a
+    record array of capi.INERTIAL_INIT_EDGE_DTYPE; bg, ba: the front keyframe's bias; Rwg (3 x 3), scale: the estimates of the gravity
+    direction and the scale.  Returns (problem, keep-alive list)."""
+    if isinstance(keyframes, np.ndarray):
+        K = np.ascontiguousarray(keyframes, np.float32).reshape(-1, capi.INERTIAL_INIT_STATE_FLOATS)
+    else:
+        K = np.zeros((len(keyframes), capi.INERTIAL_INIT_STATE_FLOATS), np.float32)
+        for i, kf in enumerate(keyframes):
+            K[i, 0:9] = np.asarray(kf["Rwb"], np.float32).reshape(9)
+            K[i, 9:12] = np.asarray(kf["twb"], np.float32).reshape(3)
+            K[i, 12:15] = np.asarray(kf["vwb"], np.float32).reshape(3)
+    if isinstance(edges, np.ndarray):
+        E = np.ascontiguousarray(edges, capi.INERTIAL_INIT_EDGE_DTYPE)
+    else:
+        E = np.zeros(len(edges), capi.INERTIAL_INIT_EDGE_DTYPE)
+        for i, e in enumerate(edges):
+            E[i]["k1"], E[i]["k2"] = int(e["k1"]), int(e["k2"])
+            E[i]["dT"] = np.float32(e["preint"]["dT"])
+            for k in ("dR", "dV", "dP", "JRg", "JVg", "JVa", "JPg", "JPa", "bg", "ba"):
+                E[i][k] = np.asarray(e["preint"][k], np.float32).reshape(-1)
+            E[i]["info9"] = np.asarray(e["info9"], np.float64).reshape(81)
+    p = capi.InertialInitProblem()
+    p.struct_size = C.sizeof(capi.InertialInitProblem)
+    p.device, p.algorithm, p.iterations, p.lambda_init = int(device), int(algorithm), int(iterations), float(lambda_init)
+    p.free_velocity, p.free_bias, p.free_gdir, p.free_scale = [int(bool(f)) for f in (free_velocity, free_bias, free_gdir, free_scale)]
+    p.with_priors, p.prior_g, p.prior_a = int(bool(with_priors)), float(prior_g), float(prior_a)
+    _fill(p.bg, bg, np.float32)
+    _fill(p.ba, ba, np.float32)
+    _fill(p.Rwg, np.eye(3) if Rwg is None else Rwg, np.float64)
+    p.scale = float(scale)
+    p.n_keyframes, p.n_edges = len(K), len(E)
+    p.keyframes = capi.ptr(K) if len(K) else None
+    p.edges = capi.ptr(E) if len(E) else None
+    return p, [K, E]
+
+
+class InertialInitOutput:
+    """inertial_init_result with its arrays.  vwb: (n_keyframes, 3) double."""
+
+    def __init__(self, problem, trace_cap=200):
+        self.nk = problem.n_keyframes
+        self.vwb = np.zeros((max(self.nk, 1), 3))
+        self.trace = np.zeros((max(trace_cap, 1), 3))
+        c = self.c = capi.InertialInitResult()
+        c.struct_size = C.sizeof(capi.InertialInitResult)
+        c.vwb = capi.ptr(self.vwb)
+        c.trace, c.trace_cap = capi.ptr(self.trace), trace_cap
+
+    def as_dict(self):
+        """the result in the layout of the numpy model (tests/inertial_init_model.py)"""
+        c = self.c
+        return {"vwb": self.vwb[: self.nk].copy(), "bg": np.array(list(c.bg)), "ba": np.array(list(c.ba)),
+                "Rwg": np.array(list(c.Rwg)).reshape(3, 3), "scale": c.scale, "iters": c.iters, "n_unknowns": c.n_unknowns,
+                "solve_failed": c.solve_failed, "chi2_first": c.chi2_first, "chi2_final": c.chi2_final,
+                "trace": self.trace[: c.trace_len].copy()}
+
+
 class InertialBaOutput:
     """inertial_ba_result with its arrays.  states: (n_keyframes, 21) double = Rwb (9), twb, vwb, bg, ba."""
 
