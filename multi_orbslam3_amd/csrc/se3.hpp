@@ -270,10 +270,20 @@ __device__ inline void pose_oplus_series(const PoseQ& T, const double* u, PoseQ*
   const double om0 = u[0], om1 = u[1], om2 = u[2];
   const double t = om0 * om0 + om1 * om1 + om2 * om2;
   if (t > 0.09) { pose_oplus_fast(T, u, out); return; }
-  const double s = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 81749606400.0, 1.0 / 185794560.0), -1.0 / 645120.0), 1.0 / 3840.0), -1.0 / 48.0), 0.5);
-  const double c = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 3715891200.0, 1.0 / 10321920.0), -1.0 / 46080.0), 1.0 / 384.0), -0.125), 1.0);
-  const double b = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 479001600.0, 1.0 / 3628800.0), -1.0 / 40320.0), 1.0 / 720.0), -1.0 / 24.0), 0.5);
-  const double cc = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 6227020800.0, 1.0 / 39916800.0), -1.0 / 362880.0), 1.0 / 5040.0), -1.0 / 120.0), 1.0 / 6.0);
+  double s, c, b, cc;
+  if (t < 1e-10) {
+    // Below theta = 1e-5 SE3Quat::exp is not the limit of its closed form but R = V = I + Omega + Omega^2 (se3quat.h:237-243): V carries
+    // the whole of omega x u_t where the exponential has half of it, 5e-6 |u_t| at the threshold.  Quaterniond(R), normalised, is
+    // (omega, 2 - theta^2) / sqrt(4 - 3 theta^2 + theta^4), and 1 / sqrt(..) is (1 + 3/8 theta^2) / 2 to 1e-20 there.  (theta^2 < 1e-10
+    // stands for theta < 1e-5: the two can differ only for a theta^2 within rounding of 1e-10.)  A branch, not selects: the steps of a
+    // converged solve all come here and skip the four series.
+    s = 0.5 * (1.0 + 0.375 * t); c = (2.0 - t) * s; b = 1.0; cc = 1.0;
+  } else {
+    s = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 81749606400.0, 1.0 / 185794560.0), -1.0 / 645120.0), 1.0 / 3840.0), -1.0 / 48.0), 0.5);
+    c = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 3715891200.0, 1.0 / 10321920.0), -1.0 / 46080.0), 1.0 / 384.0), -0.125), 1.0);
+    b = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 479001600.0, 1.0 / 3628800.0), -1.0 / 40320.0), 1.0 / 720.0), -1.0 / 24.0), 0.5);
+    cc = __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, -1.0 / 6227020800.0, 1.0 / 39916800.0), -1.0 / 362880.0), 1.0 / 5040.0), -1.0 / 120.0), 1.0 / 6.0);
+  }
   // V u_t = u_t + b (omega x u_t) + cc (omega x (omega x u_t))
   const double w0 = om1 * u[5] - om2 * u[4], w1 = om2 * u[3] - om0 * u[5], w2 = om0 * u[4] - om1 * u[3];
   const double z0 = om1 * w2 - om2 * w1, z1 = om2 * w0 - om0 * w2, z2 = om0 * w1 - om1 * w0;
@@ -290,14 +300,6 @@ __device__ inline void pose_oplus_series(const PoseQ& T, const double* u, PoseQ*
   if (q3 < 0) { q0 = -q0; q1 = -q1; q2 = -q2; q3 = -q3; }
   const double in = fast_rsqrt(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
   out->q[0] = q0 * in; out->q[1] = q1 * in; out->q[2] = q2 * in; out->q[3] = q3 * in;
-}
-
-// 1/d to ~1 ulp: hardware seed + two Newton-Raphson steps
-__device__ __forceinline__ double fast_rcp(double d) {
-  double x = __builtin_amdgcn_rcp(d);
-  x = __builtin_fma(x, __builtin_fma(-d, x, 1.0), x);
-  x = __builtin_fma(x, __builtin_fma(-d, x, 1.0), x);
-  return x;
 }
 
 }  // namespace orbg_se3
