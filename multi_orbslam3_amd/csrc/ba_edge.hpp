@@ -1,7 +1,7 @@
 // The reprojection edges of the bundle adjustments (lba.hip: Optimizer::LocalBundleAdjustment, full_ba.hip:
-// Optimizer::BundleAdjustment): residual, depth test, Huber kernel and the analytic Jacobians of one edge.  No include guard and
-// no namespace of its own: each translation unit includes it ONCE inside its anonymous namespace, after se3.hpp and
-// `using namespace orbg_se3`, so that each unit keeps its own internal copies.
+// Optimizer::BundleAdjustment): residual, depth test, Huber thresholds (the kernel itself is lm_step.hpp's lm_huber) and the
+// analytic Jacobians of one edge.  No include guard and no namespace of its own: each translation unit includes it ONCE inside its
+// anonymous namespace, after se3.hpp and `using namespace orbg_se3`, so that each unit keeps its own internal copies.
 
 __device__ inline void edge_error(const PoseQ& T, const double* X, const Cam& c, const lba_edge& e, double* err, double* Xc) {
   double r[3];
@@ -60,11 +60,7 @@ __device__ inline bool edge_depth_positive(const PoseQ& T, const double* X, cons
   return rr[2] + T.t[2] > 0.0;
 }
 
-__device__ inline void huber(double e, double delta, double dsqr, double* rho0, double* rho1) {
-  if (e <= dsqr) { *rho0 = e; *rho1 = 1.; }
-  else { const double s = sqrt(e); *rho0 = 2 * s * delta - dsqr; *rho1 = delta / s; }
-}
-
+// the thresholds of the two edge kinds for lm_huber (lm_step.hpp)
 struct Huber { double delta_mono, dsqr_mono, delta_stereo, dsqr_stereo; };
 
 // Jacobians of one edge (stereo: G/types/types_six_dof_expmap.cpp:228-274; mono: S/OptimizableTypes.cpp:139-160)

@@ -141,6 +141,31 @@ struct StreamSignal {
   int sync(hipStream_t st) { int rc = post(st); return rc ? rc : wait(st); }
 };
 
+// The completion word of a solve that runs in ONE launch (pose_opt.hip, pose_inertial.hip, inertial_init.hip): an int inside the
+// result record in mapped pinned memory, so that the record and its completion arrive with the same write-back.  The host side is one
+// object per call site (static thread_local): arm() zeroes the word and issues the next sequence number, 31 bits and never 0, which
+// the launch takes along; wait() spins on the word.  Kept apart from StreamSignal::wait on purpose: the two pace their spins differently
+// (that one pauses in every spin, reads the clock every 0x4000 spins and gives up after 50 ms; this one does not pause, reads it every
+// 0x10000 spins and gives up after 100 ms), both run on the tracking thread, and one loop for both would change the timing of one.
+struct SolveWord {
+  unsigned seq = 0;
+  volatile const int* word = nullptr;
+  unsigned arm(int* host_word) {
+    seq = (seq + 1) & 0x7FFFFFFFu;
+    if (seq == 0) seq = 1;
+    *host_word = 0;
+    word = host_word;
+    return seq;
+  }
+  int wait(hipStream_t st) const;  // spin while poll_allowed(), then hipStreamSynchronize if the word has not arrived (misc.cpp)
+};
+// the kernel's last lines: every wavefront's results released to the system (no acquire half), then the word, by thread 0 alone
+__device__ __forceinline__ void solve_word_complete(int* word, unsigned seq) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+  __syncthreads();
+  if (threadIdx.x == 0) *reinterpret_cast<volatile int*>(word) = (int)seq;   // results are complete: the host spins on this word
+}
+
 // Streams of the library's handles.  HIP multiplexes the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (4 unless the
 // environment says otherwise): the first four streams get a queue each, every further one joins the queue with the fewest users,
 // ties broken by the queues' ADDRESSES -- i.e. differently from run to run.  Streams that share a hardware queue are serialised: with

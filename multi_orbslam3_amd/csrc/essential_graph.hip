@@ -4,7 +4,7 @@
 // g2o::EdgeSim3 edges with identity information and no robust kernel, setUserLambdaInit, ONE optimize(iterations), then the map
 // points through the initial and the final estimate of their reference keyframe.
 //
-// The Sim3 arithmetic is sim3_math.hpp's, the LM decisions lm_driver.hpp's, the LDL^T solvers the bundle adjustments'
+// The Sim3 arithmetic is sim3_math.hpp's, the LM decisions lm_step.hpp's and their outer loop lm_driver.hpp's, the LDL^T solvers the bundle adjustments'
 // (ldlt_mfma.hpp, ldlt_xcd.hpp, ldlt_wide.hpp), chosen by n = 7 F as full_ba.hip chooses by 6 nP.  There is no Schur complement: every
 // vertex is a pose, the normal equations H (7F x 7F, F free vertices in ascending vertex order) go to the solver dense.
 //   structure, once per call, on the host (thousands of edges): per free vertex its (edge, side) items in edge order, the distinct

@@ -3,8 +3,8 @@
 // LoopClosing::RunGlobalBundleAdjustment) behind ba_solve() of include/orbgpu.h: ONE optimize(nIterations) over every keyframe and
 // map point of a map, Huber kernels on or off, every edge with the camera of its own keyframe.
 //
-// The edges, the Huber kernel, the LM decisions and the LDL^T solvers are the local BA's (ba_edge.hpp, lm_driver.hpp, ldlt_mfma.hpp,
-// ldlt_xcd.hpp, ldlt_wide.hpp); the landmark-Schur arithmetic between them (landmark_schur.hpp) and the record of an evaluation
+// The edges, the Huber kernel, the LM decisions and the LDL^T solvers are the local BA's (ba_edge.hpp, lm_step.hpp behind lm_driver.hpp,
+// ldlt_mfma.hpp, ldlt_xcd.hpp, ldlt_wide.hpp); the landmark-Schur arithmetic between them (landmark_schur.hpp) and the record of an evaluation
 // (lm_record.hpp) are shared with inertial_ba.hip.  What is new is everything whose size goes with the MAP instead of a window (DESIGN.md,
 // "BundleAdjustment"): hundreds of free poses, 10^5 .. 10^6 edges, a reduced camera system most of whose blocks are empty.
 //   structure, once per call, all on the device, no sort and no floating-point atomic:
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void k_ba_items_fill(int n_pairs, const int* _
 // ------------------------------------------------------------------------------------------ per iteration
 
 __device__ __forceinline__ void edge_rho(double chi, bool mono, int robust, const Huber& hb, double* rho0, double* rho1) {
-  if (robust) huber(chi, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, rho0, rho1);
+  if (robust) lm_huber(chi, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, rho0, rho1);
   else { *rho0 = chi; *rho1 = 1.0; }
 }
 

@@ -5,7 +5,7 @@
 // observe them.
 //
 // The vertices and the inertial edges are the per-frame optimiser's (pose_inertial_edges.hpp), the LM decisions and the LDL^T solvers
-// the bundle adjustments' (lm_driver.hpp, lm_record.hpp, ldlt_solver.hpp), the landmark-Schur arithmetic full_ba.hip's (landmark_schur.hpp).  What is new:
+// the bundle adjustments' (lm_step.hpp, lm_driver.hpp, lm_record.hpp, ldlt_solver.hpp), the landmark-Schur arithmetic full_ba.hip's (landmark_schur.hpp).  What is new:
 // the visual edges in the ImuCamPose parametrisation (update on the body, right-multiplied rotation), keyframe blocks of 15 (6 without
 // an IMU) at the offsets of a table, and the inertial blocks in the reduced system.
 //   structure, once per call, on the host (a window holds at most 32 free keyframes): the run of edges of every point, the edges of

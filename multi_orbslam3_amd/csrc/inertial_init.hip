@@ -543,9 +543,7 @@ __global__ __launch_bounds__(kIiThreads) void inertial_init_kernel(const IiParam
     out->chi2_first = chi_first; out->chi2_final = chi_final;
     out->iters = done; out->solve_failed = failed; out->trace_len = min(trace_len, P.trace_cap);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // system-scope release of every wavefront's results (no acquire half)
-  __syncthreads();
-  if (tid == 0) *reinterpret_cast<volatile int*>(&out->seq) = (int)seq;    // results are complete: the host spins on this word
+  solve_word_complete(&out->seq, seq);
 }
 
 // the calling thread's work area (common.hpp; the reference calls a static member: no handle)
@@ -704,12 +702,9 @@ extern "C" int inertial_init_solve(const inertial_init_problem* p, inertial_init
   const size_t wJ = (size_t)ne * kIiJ, wH = (size_t)ne * kIiH, wV = lds ? 0 : (size_t)nk * kIiVtx, wv = 3 * (size_t)nk;
   if ((rc = sc.work.reserve(wJ + wH + wV + 2 * wv))) return rc;
   double* dJ = sc.work.p; double* dH = dJ + wJ; double* dV = dH + wH; double* dvc = dV + wV; double* dvt = dvc + wv;
-  static thread_local unsigned ii_seq = 0;
-  ii_seq = (ii_seq + 1) & 0x7FFFFFFFu;
-  if (ii_seq == 0) ii_seq = 1;
+  static thread_local orbg::SolveWord done_word;
   IiOut* ho = S.host(s_out);
-  volatile const int* seq_word = &ho->seq;
-  ho->seq = 0;
+  const unsigned ii_seq = done_word.arm(&ho->seq);
   if (lds)
     hipLaunchKernelGGL(inertial_init_kernel<true>, dim3(1), dim3(kIiThreads), 0, sc.stream, (const IiParams*)S.device(s_prm), (const IiKf*)S.device(s_kf),
                        (const PiGsEdge*)S.device(s_ed), (const double*)S.device(s_v0), d_order, d_pred, d_in, d_os, d_oe, dJ, dH, dV, dvc, dvt,
@@ -719,21 +714,7 @@ extern "C" int inertial_init_solve(const inertial_init_problem* p, inertial_init
                        (const PiGsEdge*)S.device(s_ed), (const double*)S.device(s_v0), d_order, d_pred, d_in, d_os, d_oe, dJ, dH, dV, dvc, dvt,
                        S.mapped(s_out), S.mapped(s_vout), S.mapped(s_trace), ii_seq);
   ORBG_HIP(hipGetLastError());
-  {
-    bool got = false;
-    if (orbg::poll_allowed()) {
-      timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-      for (unsigned spins = 0; !got; spins++) {
-        if (*seq_word == (int)ii_seq) { got = true; break; }
-        if ((spins & 0xFFFF) == 0xFFFF) {
-          timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-          if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 100.0) break;
-        }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!got) ORBG_HIP(hipStreamSynchronize(sc.stream));
-  }
+  if ((rc = done_word.wait(sc.stream))) return rc;
   S.get(s_vout, r->vwb);
   memcpy(r->bg, ho->end.bg, sizeof(r->bg)); memcpy(r->ba, ho->end.ba, sizeof(r->ba)); memcpy(r->Rwg, ho->end.Rwg, sizeof(r->Rwg));
   r->scale = ho->end.s;

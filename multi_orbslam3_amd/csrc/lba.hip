@@ -5,7 +5,8 @@
 //
 // Design (MI355X-first): everything is FP64 and stays in HBM/L2 for the whole solve; the host only runs the LM
 // control flow (lambda schedule, accept/reject) on three scalars per trial that the kernels drop into mapped
-// pinned memory.  All reductions are ORDER-FIXED (CSR gathers + tree sums, no floating-point atomics) so a solve
+// pinned memory (the decisions themselves: lm_step.hpp, which the record's publisher runs too, for the lambda of a
+// solve launched ahead of the verdict).  All reductions are ORDER-FIXED (CSR gathers + tree sums, no floating-point atomics) so a solve
 // is bit-reproducible run to run:
 //   k_errors        thread/edge : residual, chi2, Huber rho        (+ fixed-order block partial sums)
 //   k_linearize     thread/edge : analytic Jacobians, weighted J^T W J blocks (Hpl 6x3, pose 21+6, point 6+3)
@@ -68,7 +69,7 @@ __device__ long long g_lba_prof[3][8 + 2 * 1020];
 #define LBA_PROF_PHASE(block, slot) do { } while (0)
 #endif
 
-#include "ba_edge.hpp"     // edge_error, edge_depth_positive, huber, edge_jacobians: shared with full_ba.hip
+#include "ba_edge.hpp"     // edge_error, edge_depth_positive, Huber, edge_jacobians: shared with full_ba.hip
 
 // ---------------------------------------------------------------------------------------------- kernels
 
@@ -156,17 +157,14 @@ __device__ __forceinline__ void publish_trial_tail(int n_edge_blocks, const doub
       __hip_atomic_store(&rec->c_ok, (unsigned long long)(unsigned)okv ^ tg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
     if (lm.lambda_next) {
-      // lambda of the NEXT iteration if this trial is accepted -- the host's arithmetic (levenberg.cpp:116-141), operation for
-      // operation, so that a solve launched speculatively with it is the solve the host would have launched
+      // lambda of the NEXT iteration if this trial is accepted -- the functions the host's verdict runs (lm_step.hpp), so that a
+      // solve launched speculatively with it is the solve the host would have launched
       const double cur = lm.chi_p ? *lm.chi_p : lm.cur_chi;
       const double lam = lm.lambda_p ? *lm.lambda_p : lm.lambda;
-      const double tempChi = okv ? chi : 1.7976931348623157e308;
-      double rho = cur - tempChi;
+      static_assert(kLmGoodStepLower == 1. / 3. && kLmGoodStepUpper == 2. / 3., "the speculative lambda is g2o's good-step factor");
+      double rho = cur - lm_trial_chi2(okv != 0, chi);
       rho /= scale + 1e-3;
-      const double c3 = 2 * rho - 1;
-      double alpha = 1. - c3 * c3 * c3;
-      alpha = fmin(alpha, 2. / 3.);
-      *lm.lambda_next = lam * fmax(1. / 3., alpha);
+      *lm.lambda_next = lm_accepted_lambda(lam, rho);
     }
     *ticket = 0;
     __hip_atomic_store(&rec->seq, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // the host polls this word instead of hipStreamSynchronize
@@ -243,7 +241,7 @@ __device__ __forceinline__ double errors_block(int bid, int n_edge_blocks, int n
     c_out = c;
     double rho1;
     const bool mono = D == 2;
-    huber(c, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
+    lm_huber(c, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
   }
   red[threadIdx.x] = rho0;
   __syncthreads();
@@ -330,7 +328,7 @@ __device__ inline void edge_hpl(const PoseQ& T, const double* X, const CamT& c, 
     chi_k = chi2[k2];
   }
   double rho0, rho1;
-  huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
+  lm_huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
   double r[3], A[9], B[18];
   quat_rotate(T.q, X, r);
   edge_jacobians(T, r[0] + T.t[0], r[1] + T.t[1], r[2] + T.t[2], c, e.ur, A, B);
@@ -375,7 +373,7 @@ __device__ __forceinline__ void linearize_block(int bid, int n_edges, const lba_
       er[0] = err[3 * (size_t)k]; er[1] = err[3 * (size_t)k + 1]; er[2] = err[3 * (size_t)k + 2];
       chi_k = chi2[k];
     }
-    huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
+    lm_huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
   }
   if constexpr (FUSED) {
     // the workgroup's robust chi2 partial (same tree as k_errors), then the record if this is the last workgroup
@@ -517,7 +515,7 @@ __device__ __forceinline__ void lin_poses_block(int bid, const int* __restrict__
       double A[9], B[18];
       edge_jacobians(T, r[0] + T.t[0], r[1] + T.t[1], r[2] + T.t[2], c, e.ur, A, B);
       double rho0, rho1;
-      huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
+      lm_huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
       const double om = (double)e.inv_sigma2;
       const double wom = rho1 * om;
       double omega_r[3];
@@ -612,7 +610,7 @@ __device__ __forceinline__ void lin_points_block(int bid, int nL, const int* __r
         double chi_k = 0;
         for (int i = 0; i < D; i++) chi_k += er[i] * (om * er[i]);
         double rho0, rho1;
-        huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
+        lm_huber(chi_k, mono ? hb.delta_mono : hb.delta_stereo, mono ? hb.dsqr_mono : hb.dsqr_stereo, &rho0, &rho1);
         double r[3];
         quat_rotate(T.q, Xl, r);
         double A[9], B[18];

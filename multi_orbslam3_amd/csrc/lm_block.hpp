@@ -1,7 +1,10 @@
 // What the single-workgroup solve kernels share (pose_opt.hip: PoseOptimization, 6 unknowns; sim3_opt.hip: OptimizeSim3, 7;
-// pose_inertial.hip: PoseInertialOptimization, 15 / 30): the damped solve spread over the lanes of a wavefront and the block sum of a 256-thread (four-wavefront) workgroup.
+// pose_inertial.hip: PoseInertialOptimization, 15 / 30; inertial_init.hip: InertialOptimization): the damped solve spread over the lanes
+// of a wavefront and the block sum of a 256-thread (four-wavefront) workgroup.  The scalar Huber kernel is lm_step.hpp's, included
+// here for all of them; the word that completes a one-launch solve is common.hpp's (SolveWord).
 #pragma once
 
+#include "lm_step.hpp"
 #include "wave.hpp"
 
 namespace orbg {

@@ -1,14 +1,13 @@
 // The host side of g2o's Levenberg-Marquardt as the bundle adjustments run it (lba.hip: Optimizer::LocalBundleAdjustment,
-// full_ba.hip: Optimizer::BundleAdjustment): the caller's abort flag with its poll rule, and the arithmetic of
+// full_ba.hip: Optimizer::BundleAdjustment): the caller's abort flag with its poll rule, the trace row, and the outer loop of the
+// solves that wait for every record (lm_optimize: full_ba.hip, inertial_ba.hip, essential_graph.hip).  The arithmetic of
 // OptimizationAlgorithmLevenberg::solve on the three scalars a trial brings back from the device (robust chi2, computeScale, the
-// solver's flag).  What each solve launches around these steps is its own; the decisions are written once, here, and so is the
-// outer loop of the solves that wait for every record (lm_optimize: full_ba.hip, essential_graph.hip).
+// solver's flag) is lm_step.hpp's, where the device's own loops find it too.  What each solve launches around these steps is its own.
 #pragma once
 
-#include <algorithm>
-#include <cmath>
 #include <cstdint>
-#include <limits>
+
+#include "lm_step.hpp"
 
 namespace orbg_lm {
 
@@ -34,52 +33,6 @@ struct StopCheck {
     return v > 0 || (v < 0 && trials_done >= -v);
   }
 };
-
-// lambda, the rejection factor, the chi2 of the current estimate and the count of iterations that barely improved it
-struct LmScalars {
-  double lambda = -1, ni = 2, currentChi = 0;
-  int nBad = 0;
-};
-
-// computeLambdaInit (G/core/optimization_algorithm_levenberg.cpp:161-174): the user's value, or tau * the largest diagonal entry
-inline double lm_lambda_init(double user_lambda, double max_diagonal) { return user_lambda > 0 ? user_lambda : 1e-5 * max_diagonal; }
-
-// The verdict on one trial (G/core/optimization_algorithm_levenberg.cpp:118-146): rho = (chi2 - chi2_trial) / (scale + 1e-3).
-// Accepted (rho > 0 and a finite chi2_trial): lambda shrinks by max(1/3, min(1 - (2 rho - 1)^3, 2/3)) and the trial's chi2 becomes
-// the current one; rejected: lambda *= ni, ni *= 2.  Returns rho.
-inline double lm_trial_verdict(LmScalars& m, bool solver_ok, double chi2_trial, double scale, bool* accepted) {
-  double tempChi = chi2_trial;
-  if (!solver_ok) tempChi = std::numeric_limits<double>::max();
-  double rho = m.currentChi - tempChi;
-  scale += 1e-3;
-  rho /= scale;
-  if (rho > 0 && std::isfinite(tempChi)) {
-    const double c3 = 2 * rho - 1;               // (2 rho - 1)^3 as two multiplications: lba.hip's publish_trial_record does the same
-    double alpha = 1. - c3 * c3 * c3;            // arithmetic on the device for the speculative next solve
-    alpha = std::min(alpha, 2. / 3.);
-    const double scaleFactor = std::max(1. / 3., alpha);
-    m.lambda *= scaleFactor;
-    m.ni = 2;
-    m.currentChi = tempChi;
-    *accepted = true;
-  } else {
-    m.lambda *= m.ni;
-    m.ni *= 2;
-    *accepted = false;
-  }
-  return rho;
-}
-// the trial loop goes on while the last trial was rejected with rho < 0, trials are left (the caller's qmax < maxTrialsAfterFailure:
-// g2o's property, 10 in every solve of the reference) and the flag is down
-inline bool lm_try_again(double rho, bool trials_left, bool stop_raised) { return rho < 0 && trials_left && !stop_raised; }
-
-// The end of an iteration: false when optimize() ends with it -- the trials ran out (the caller's qmax == maxTrialsAfterFailure), a
-// trial with rho == 0, or the third iteration in a row that improved chi2 by less than a thousandth.
-inline bool lm_iteration_continues(LmScalars& m, bool trials_exhausted, double rho, double iniChi) {
-  if (trials_exhausted || rho == 0) return false;
-  if ((iniChi - m.currentChi) * 1e3 < iniChi) m.nBad++; else m.nBad = 0;
-  return m.nBad < 3;
-}
 
 // the trace row of an iteration as the bundle adjustments report it: lambda, the chi2 reached, the trials it took
 inline void lm_trace_row(const LmScalars& m, int qmax, double* trace, int cap, int* len) {

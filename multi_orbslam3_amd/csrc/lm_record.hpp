@@ -1,5 +1,6 @@
 // The record an LM solve that waits for every verdict (lm_optimize, lm_driver.hpp: full_ba.hip, inertial_ba.hip, essential_graph.hip)
-// reads back after a linearisation or a trial, the one-workgroup reduction that writes it, and the host's way to it.  Every sum has a
+// reads back after a linearisation or a trial, the one-workgroup reduction that writes it, and the host's way to it.  What the host
+// decides from a record is lm_step.hpp's (lm_trial_verdict, lm_lambda_init on .maxdiag).  Every sum has a
 // fixed order: two calls on the same input return the same bits.
 #pragma once
 

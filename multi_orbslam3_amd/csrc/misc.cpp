@@ -203,4 +203,22 @@ int StreamSignal::wait(hipStream_t st) {
   return ORBG_OK;
 }
 
+// (not StreamSignal::wait with other constants: common.hpp says why)
+int SolveWord::wait(hipStream_t st) const {
+  bool got = false;
+  if (poll_allowed()) {
+    timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (unsigned spins = 0; !got; spins++) {
+      if (*word == (int)seq) { got = true; break; }
+      if ((spins & 0xFFFF) == 0xFFFF) {
+        timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+        if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 100.0) break;
+      }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  }
+  if (!got) ORBG_HIP(hipStreamSynchronize(st));
+  return ORBG_OK;
+}
+
 }  // namespace orbg

@@ -25,7 +25,8 @@ using namespace orbg;
 //   4. H = J^T (w W J), b = -J^T (w W e), w the Huber weight of a row's edge (only the prior has a kernel), plus the visual 6 x 6;
 //   5. wavefront 0 solves H x = b by LDL^T, lane i holding row i (lane_ldlt_solve, lambda = 0);
 //   6. thread 0 updates the frame's vertices and the camera pose, thread 64 the previous frame's.
-// All of it in double.  Every sum has a fixed order: the result is bit-reproducible from run to run.
+// All of it in double.  Every sum has a fixed order: the result is bit-reproducible from run to run.  The Huber
+// kernel is lm_step.hpp's (through pi_huber); the word that completes the launch is common.hpp's SolveWord.
 namespace {
 
 constexpr int kPiThreads = 256;
@@ -253,9 +254,7 @@ __global__ __launch_bounds__(kPiThreads) void pose_inertial_kernel(const PiParam
     out->cur = s_cur;
     out->stats[0] = nBad; out->stats[1] = rounds; out->stats[2] = failed ? 1 : 0;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // system-scope release of every wavefront's results (no acquire half)
-  __syncthreads();
-  if (tid == 0) *reinterpret_cast<volatile int*>(&out->stats[7]) = (int)seq;   // results are complete: the host spins on this word
+  solve_word_complete(&out->stats[7], seq);
 }
 
 // the calling thread's work area (common.hpp; the reference calls a static member: no handle)
@@ -420,12 +419,9 @@ extern "C" int pose_inertial_optimize(const pose_inertial_problem* p, pose_inert
   const uint8_t* dcl = S.add(p->close, n, true);
   pi_fill_params(*p, S.host(s_prm));
   if ((rc = S.commit(sc.stream))) return rc;
-  static thread_local unsigned pi_seq = 0;
-  pi_seq = (pi_seq + 1) & 0x7FFFFFFFu;
-  if (pi_seq == 0) pi_seq = 1;
+  static thread_local orbg::SolveWord done_word;
   PiOut* ho = S.host(s_out);
-  volatile const int* seq_word = &ho->stats[7];
-  ho->stats[7] = 0;
+  const unsigned pi_seq = done_word.arm(&ho->stats[7]);
   if (p->form == POSE_INERTIAL_LAST_FRAME)
     hipLaunchKernelGGL(pose_inertial_kernel<30>, dim3(1), dim3(kPiThreads), 0, sc.stream, (const PiParams*)S.device(s_prm), dX, du, dv, dur, dom, dcl,
                        S.mapped(s_out), S.mapped(s_flag), pi_seq);
@@ -433,21 +429,7 @@ extern "C" int pose_inertial_optimize(const pose_inertial_problem* p, pose_inert
     hipLaunchKernelGGL(pose_inertial_kernel<15>, dim3(1), dim3(kPiThreads), 0, sc.stream, (const PiParams*)S.device(s_prm), dX, du, dv, dur, dom, dcl,
                        S.mapped(s_out), S.mapped(s_flag), pi_seq);
   ORBG_HIP(hipGetLastError());
-  {
-    bool got = false;
-    if (orbg::poll_allowed()) {
-      timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-      for (unsigned spins = 0; !got; spins++) {
-        if (*seq_word == (int)pi_seq) { got = true; break; }
-        if ((spins & 0xFFFF) == 0xFFFF) {
-          timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-          if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 100.0) break;
-        }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!got) ORBG_HIP(hipStreamSynchronize(sc.stream));
-  }
+  if ((rc = done_word.wait(sc.stream))) return rc;
   memcpy(r->Rwb, ho->cur.R, sizeof(r->Rwb)); memcpy(r->twb, ho->cur.t, sizeof(r->twb)); memcpy(r->vwb, ho->cur.v, sizeof(r->vwb));
   memcpy(r->bg, ho->cur.bg, sizeof(r->bg)); memcpy(r->ba, ho->cur.ba, sizeof(r->ba));
   memcpy(r->chi2, ho->chi2, sizeof(r->chi2));

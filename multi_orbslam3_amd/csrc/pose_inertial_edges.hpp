@@ -100,12 +100,8 @@ PI_HD inline void pi_normalize_rotation(double* X) {
     for (int i = 0; i < 9; i++) X[i] = 0.5 * (X[i] + C[i] / det);
   }
 }
-// rho0 / rho1 of RobustKernelHuber::robustify (G/core/robust_kernel_impl.cpp:78-91)
-PI_HD __forceinline__ void pi_huber(double e, double delta, double* rho0, double* rho1) {
-  const double dsqr = delta * delta;
-  if (e <= dsqr) { *rho0 = e; *rho1 = 1.0; }
-  else { const double sq = sqrt(e); *rho0 = 2 * sq * delta - dsqr; *rho1 = delta / sq; }
-}
+// rho0 / rho1 of RobustKernelHuber::robustify from delta alone (lm_step.hpp, which the including unit has in front of this file)
+PI_HD __forceinline__ void pi_huber(double e, double delta, double* rho0, double* rho1) { orbg_lm::lm_huber(e, delta, delta * delta, rho0, rho1); }
 
 // ImuCamPose::Update (S/G2oTypes.cc:192-220; the renormalisation at :206 discards its result) + the oplus of the three plain vertices
 PI_HD inline void pi_oplus(PiState* s, const double* dx) {

@@ -502,9 +502,7 @@ __global__ __launch_bounds__(kPoThreads) void pose_opt_kernel(int n, const float
   PO_ACC(5);
   for (int i = tid; i < n; i += kPoThreads) outlier_out[i] = s_out[i];
   if (tid == 0) { *T_out = T; stats[0] = nBad; }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // system-scope release of every wavefront's results (no acquire half)
-  __syncthreads();
-  if (tid == 0) *reinterpret_cast<volatile int*>(&stats[7]) = (int)seq;   // results are complete: the host spins on this word
+  solve_word_complete(&stats[7], seq);
 }
 
 
@@ -814,9 +812,7 @@ __global__ __launch_bounds__(kPoWide) void pose_opt_wide_kernel(int n, const flo
 #pragma unroll
   for (int p = 0; p < NP; p++) if (have[p]) outlier_out[idx[p]] = my_out[p] ? 1 : 0;
   if (tid == 0) { *T_out = T; stats[0] = nBad; }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");              // system-scope release of every wavefront's results (no acquire half)
-  __syncthreads();
-  if (tid == 0) *reinterpret_cast<volatile int*>(&stats[7]) = (int)seq;   // results are complete: the host spins on this word
+  solve_word_complete(&stats[7], seq);
 }
 
 }  // namespace
@@ -889,12 +885,9 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   Cam cam{p->fx, p->fy, p->cx, p->cy, p->bf, p->bf};
   CamRig rig;
   if (p->rig && !cam_rig_from(*p->rig, cam, &rig)) return ORBG_BAD_ARG;
-  static thread_local unsigned po_seq = 0;
-  po_seq = (po_seq + 1) & 0x7FFFFFFFu;
-  if (po_seq == 0) po_seq = 1;
+  static thread_local orbg::SolveWord done_word;
   PoOut* ho = S.host(s_out);
-  volatile const int* seq_word = &ho->stats[7];
-  ho->stats[7] = 0;
+  const unsigned po_seq = done_word.arm(&ho->stats[7]);
   // one launch site for every form
   auto launch = [&](auto kernel, int threads, const auto& camera) {
     hipLaunchKernelGGL(kernel, dim3(1), dim3(threads), 0, sc.stream, n, dX, du, dv, dur, dom, camera, T0, &dout->T, S.mapped(s_flag),
@@ -910,21 +903,7 @@ extern "C" int pose_optimize(const pose_opt_problem* p, pose_opt_result* r) {
   else if (n <= 2 * kPoWide) launch(pose_opt_wide_kernel<2, Cam>, kPoWide, cam);
   else launch(pose_opt_kernel, kPoThreads, cam);
   ORBG_HIP(hipGetLastError());
-  {
-    bool got = false;
-    if (orbg::poll_allowed()) {
-      timespec t0; clock_gettime(CLOCK_MONOTONIC, &t0);
-      for (unsigned spins = 0; !got; spins++) {
-        if (*seq_word == (int)po_seq) { got = true; break; }
-        if ((spins & 0xFFFF) == 0xFFFF) {
-          timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-          if ((t1.tv_sec - t0.tv_sec) * 1000.0 + (t1.tv_nsec - t0.tv_nsec) * 1e-6 > 100.0) break;
-        }
-      }
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!got) ORBG_HIP(hipStreamSynchronize(sc.stream));
-  }
+  if ((rc = done_word.wait(sc.stream))) return rc;
   const PoseQ Tf = ho->T;
   memcpy(r->chi2, ho->chi2, sizeof(ho->chi2));
   S.get(s_flag, r->outlier);

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "multi_orbslam3_amd", "csrc")
 SRC = os.path.join(ROOT, "tools", "micro", "device_math_test.hip")
 EXE = os.path.join(ROOT, "tools", "micro", "device_math_test")
-HEADERS = ["wave.hpp", "lm_block.hpp", "lm_record.hpp", "common.hpp", "se3.hpp", "sim3_math.hpp", "pose_inertial_edges.hpp", "null_vector4.hpp"]
+HEADERS = ["wave.hpp", "lm_block.hpp", "lm_record.hpp", "lm_step.hpp", "common.hpp", "se3.hpp", "sim3_math.hpp", "pose_inertial_edges.hpp", "null_vector4.hpp"]
 
 
 def build_flags():

@@ -1,6 +1,6 @@
 """Inputs and references for the shared device primitives (tools/micro/device_math_test.hip): nothing here touches the GPU.
 
-Every function of csrc/wave.hpp, lm_block.hpp, lm_record.hpp, se3.hpp, sim3_math.hpp, pose_inertial_edges.hpp (the SO3 part) and
+Every function of csrc/wave.hpp, lm_block.hpp, lm_record.hpp, lm_step.hpp, se3.hpp, sim3_math.hpp, pose_inertial_edges.hpp (the SO3 part) and
 null_vector4.hpp is restated from the formula the reference project uses, once, over an arithmetic `A`:
 
   (f64)  A = F64: Python floats -- IEEE double, every + - * / and sqrt correctly rounded, evaluated left to right as written, which is
@@ -26,6 +26,8 @@ Citations: G = Thirdparty/g2o/g2o of the reference, S = its src, E = Eigen 3.
   ImuCamPose::Update, GDirection::Update          S/G2oTypes.cc:192-220, include/G2oTypes.h:261-264
   Pinhole::project / projectJac                   S/CameraModels/Pinhole.cpp:41-47, 81-91
   KannalaBrandt8::project / projectJac            S/CameraModels/KannalaBrandt8.cpp:52-69, 166-196
+  OptimizationAlgorithmLevenberg::solve, computeLambdaInit    G/core/optimization_algorithm_levenberg.cpp:118-146, 161-174
+  RobustKernelHuber::robustify                    G/core/robust_kernel_impl.cpp:78-91
 """
 import functools
 import math
@@ -522,6 +524,77 @@ def ldlt_solve(A, H, b, lam, rel):
     return x, "ok"
 
 
+# ------------------------------------------------------------------------------------------------ the LM step and the Huber kernel
+# (f64) only: + - * / sqrt and compares, held bit for bit.  numpy's float64 scalars, because x / 0 and inf - inf must give what IEEE
+# says they give.  std::min(a, b) is (b < a) ? b : a, std::max(a, b) is (a < b) ? b : a; pow(x, 3) is restated as x * x * x (what
+# the library documents for it).
+def _ieee(fn):
+    def wrapped(*args):
+        with np.errstate(all="ignore"):
+            return fn(*[np.float64(a) for a in args])
+    return wrapped
+
+
+def _good_step_factor(rho):
+    c3 = 2 * rho - 1
+    alpha = 1. - c3 * c3 * c3
+    upper, lower = np.float64(2.) / 3., np.float64(1.) / 3.        # _goodStepUpperScale, _goodStepLowerScale
+    alpha = upper if upper < alpha else alpha
+    factor = alpha if lower < alpha else lower
+    return factor, ("2/3" if factor == upper else "1/3" if factor == lower else "cubic")
+
+
+@_ieee
+def lm_trial_verdict(lam, ni, currentChi, ok2, tempChi, scale):
+    """-> ([rho, accepted, lambda, ni, currentChi], branch)"""
+    if not ok2:
+        tempChi = np.float64(np.finfo(np.float64).max)
+    rho = currentChi - tempChi
+    scale = scale + 1e-3
+    rho = rho / scale
+    if rho > 0 and np.isfinite(tempChi):
+        factor, br = _good_step_factor(rho)
+        return [rho, 1.0, lam * factor, 2.0, tempChi], "accepted_" + br
+    return [rho, 0.0, lam * ni, ni * 2, currentChi], ("rejected_rho" if not rho > 0 else "rejected_not_finite")
+
+
+@_ieee
+def lm_accepted_lambda(lam, rho):
+    factor, br = _good_step_factor(rho)
+    return [lam * factor], br
+
+
+@_ieee
+def lm_iteration_continues(currentChi, nBad, exhausted, rho, iniChi):
+    """-> ([continues, nBad], branch)"""
+    if exhausted:
+        return [0.0, nBad], "exhausted"
+    if rho == 0:
+        return [0.0, nBad], "rho_zero"
+    if (iniChi - currentChi) * 1e3 < iniChi:
+        nBad = nBad + 1
+        return ([0.0, nBad], "bad_stop") if nBad >= 3 else ([1.0, nBad], "bad")
+    return [1.0, 0.0], "good"
+
+
+@_ieee
+def lm_lambda_init(user, max_diagonal):
+    if user > 0:
+        return [user], "user"
+    return [1e-5 * max_diagonal], "diagonal"
+
+
+@_ieee
+def lm_huber(e, delta, dsqr):
+    if e <= dsqr:
+        return [e, 1.], "inlier"
+    sqrte = np.sqrt(e)
+    return [2 * sqrte * delta - dsqr, delta / sqrte], "outlier"
+
+
+LM_STEP = {60: lm_trial_verdict, 61: lm_accepted_lambda, 62: lm_iteration_continues, 63: lm_lambda_init, 64: lm_huber}
+
+
 # ------------------------------------------------------------------------------------------------ function table
 # fid -> (name, n_int, n_dbl, n_out, host_device, bit_equal, output parts); the counts are the rows of kFns in the harness
 LDLT = {10: (6, False), 11: (7, False), 12: (9, False), 13: (9, True), 14: (15, True), 15: (30, True)}
@@ -543,6 +616,9 @@ FNS = {
     44: ("pi_normalize_rotation", 0, 9, 9, True, False, [R9]), 45: ("pi_gdir_oplus", 0, 11, 9, True, False, [R9]),
     46: ("pi_oplus", 0, 36, 21, True, False, [R9, ("t", 9, 12), ("v", 12, 15), ("bg", 15, 18), ("ba", 18, 21)]),
     50: ("null_vector4", 0, 16, 8, False, False, None),
+    60: ("lm_trial_verdict", 0, 6, 5, True, True, None), 61: ("lm_accepted_lambda", 0, 2, 1, True, True, None),
+    62: ("lm_iteration_continues", 0, 5, 2, True, True, None), 63: ("lm_lambda_init", 0, 2, 1, True, True, None),
+    64: ("lm_huber", 0, 3, 2, True, True, None),
 }
 for _fid, (_n, _rel) in LDLT.items():
     FNS[_fid] = ("lane_ldlt_solve<%d,%s>" % (_n, "true" if _rel else "false"), 0, _n * _n + _n + 2, 2 * _n + 2, False, True, [("x", 0, _n)])
@@ -916,6 +992,52 @@ def build_cases():
     cs.append(Case(50, Sz.ravel(), tag="zeros_off_diagonal"))
     Sz2 = np.array([[2.0, 0, 0.3, 0], [0, 1.5, 0, 0], [0.3, 0, 1.0, 0], [0, 0, 0, 0.25]])
     cs.append(Case(50, Sz2.ravel(), tag="zeros_off_diagonal_isolated"))
+
+    # ---- the LM step.  A verdict case: lambda, ni, currentChi, the solver's flag, the trial's chi2, computeScale's sum.
+    # rho = (100 - 90) / (scale + 1e-3): the three regimes of the good-step factor (2/3 up to rho = 0.8467, 1/3 from 0.9368 on)
+    for rho, want in ((0.1, "2/3"), (0.5, "2/3"), (0.8, "2/3"), (0.87, "cubic"), (0.9, "cubic"), (0.92, "cubic"), (0.96, "1/3"), (1.5, "1/3"), (10.0, "1/3")):
+        cs.append(Case(60, [0.37, 2.0, 100.0, 1, 90.0, 10.0 / rho - 1e-3], tag="rho%g" % rho, want="accepted_" + want))
+        cs.append(Case(61, [0.37, rho], tag="rho%g" % rho, want=want))
+    cs.append(Case(61, [0.37, math.inf], tag="rho_inf", want="1/3"))
+    cs.append(Case(61, [0.37, 1e-300], tag="rho_tiny", want="2/3"))
+    cs.append(Case(60, [0.37, 4.0, 100.0, 1, 120.0, -40.0], tag="negative_scale_larger_chi2", want="accepted_2/3"))     # g2o's quirk: rho = 0.5
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, 90.0, -1e-3], tag="zero_scale_smaller_chi2", want="accepted_1/3"))         # rho = +inf
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, 110.0, 20.0], tag="rho_negative", want="rejected_rho"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, 100.0, 20.0], tag="rho_zero", want="rejected_rho"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, 100.0, -1e-3], tag="zero_over_zero", want="rejected_rho"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, math.nan, 20.0], tag="chi2_nan", want="rejected_rho"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, math.inf, 20.0], tag="chi2_inf", want="rejected_rho"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 1, -math.inf, 20.0], tag="chi2_minus_inf", want="rejected_not_finite"))
+    cs.append(Case(60, [0.37, 2.0, 100.0, 0, 1.0, 20.0], tag="refused_solve_small_chi2", want="rejected_rho"))
+    # rejections in a row: each case starts from what the one before it must leave (ni = 2 -> 4 -> 8 -> 16)
+    state = [0.37, 2.0, 100.0]
+    for k in range(3):
+        cs.append(Case(60, state + [1, 110.0 + k, 20.0], tag="rejection_%d_in_a_row" % (k + 1), want="rejected_rho"))
+        state = lm_trial_verdict(*cs[-1].dv)[0][2:5]
+    assert state[1] == 16.0
+    # the end of an iteration: currentChi, nBad, trials exhausted, rho, iniChi.  0.05 % and 0.2 % of iniChi stand either side of the 0.1 %
+    cs.append(Case(62, [90.0, 0, 1, -0.5, 100.0], tag="trials_exhausted", want="exhausted"))
+    cs.append(Case(62, [100.0, 1, 0, 0.0, 100.0], tag="rho_zero", want="rho_zero"))
+    cs.append(Case(62, [99.95, 0, 0, 0.4, 100.0], tag="improved_0.05%_nbad_0", want="bad"))
+    cs.append(Case(62, [99.95, 1, 0, 0.4, 100.0], tag="improved_0.05%_nbad_1", want="bad"))
+    cs.append(Case(62, [99.95, 2, 0, 0.4, 100.0], tag="improved_0.05%_nbad_2", want="bad_stop"))
+    cs.append(Case(62, [99.8, 2, 0, 0.4, 100.0], tag="improved_0.2%_nbad_2", want="good"))
+    cs.append(Case(62, [99.8, 0, 0, 0.4, 100.0], tag="improved_0.2%_nbad_0", want="good"))
+    cs.append(Case(62, [100.0, 0, 0, -0.3, 100.0], tag="every_trial_rejected", want="bad"))
+    cs.append(Case(63, [0.5, 123.456], tag="user", want="user"))
+    cs.append(Case(63, [0.0, 123.456], tag="user_zero", want="diagonal"))
+    cs.append(Case(63, [-1.0, 123.456], tag="user_negative", want="diagonal"))
+    cs.append(Case(63, [0.0, 0.0], tag="zero_diagonal", want="diagonal"))
+    for chi2_95 in (5.991, 7.815):                              # the thresholds of the reprojection edges, float as the reference holds them
+        delta = float(np.float32(math.sqrt(chi2_95)))
+        dsqr = delta * delta
+        cs.append(Case(64, [1.25, delta, dsqr], tag="below_%g" % chi2_95, want="inlier"))
+        cs.append(Case(64, [dsqr, delta, dsqr], tag="at_%g" % chi2_95, want="inlier"))
+        cs.append(Case(64, [float(np.nextafter(dsqr, math.inf)), delta, dsqr], tag="next_above_%g" % chi2_95, want="outlier"))
+        cs.append(Case(64, [10.0, delta, dsqr], tag="above_%g" % chi2_95, want="outlier"))
+        cs.append(Case(64, [3.7e6, delta, dsqr], tag="far_above_%g" % chi2_95, want="outlier"))
+        cs.append(Case(64, [0.0, delta, dsqr], tag="zero_%g" % chi2_95, want="inlier"))
+        cs.append(Case(64, [math.nan, delta, dsqr], tag="nan_%g" % chi2_95, want="outlier"))
     return cs
 
 
@@ -1020,6 +1142,9 @@ def references():
                 if diag:
                     m = int(np.argmin(np.diag(S)))             # numpy's argmin: the first of equal entries
                     r.exact = np.array([1.0 if i == m else 0.0 for i in range(4)] + list(np.diag(S)))
+            elif fid in LM_STEP:
+                out, r.branch = LM_STEP[fid](*c.dv)
+                r.exact = np.array([SENTINEL if math.isnan(v) else float(v) for v in out])     # the harness writes a NaN as the sentinel
             else:
                 out, r.branch, r.dec64, r.rnd64 = evaluate(F64, fid, c.dv)
                 outm, r.mp_branch, r.decmp, r.rndmp = evaluate(MP, fid, c.dv, force=r.dec64.taken)

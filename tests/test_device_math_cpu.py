@@ -33,9 +33,20 @@ def test_every_branch_of_every_function_is_taken():
         50: {"diagonal", "sweeps"},
         10: {"ok", "fail_pos"}, 11: {"ok", "fail_pos"}, 12: {"ok", "fail_pos"},
         13: {"ok", "fail_pos", "fail_rel"}, 14: {"ok", "fail_pos", "fail_rel"}, 15: {"ok", "fail_pos", "fail_rel"},
+        60: {"accepted_2/3", "accepted_cubic", "accepted_1/3", "rejected_rho", "rejected_not_finite"}, 61: {"2/3", "cubic", "1/3"},
+        62: {"exhausted", "rho_zero", "bad", "bad_stop", "good"}, 63: {"user", "diagonal"}, 64: {"inlier", "outlier"},
     }
     for fid, need in want.items():
         assert set(branches_of(fid)) >= need, (dm.FNS[fid][0], branches_of(fid))
+    # the LM verdict: every way a trial can come to be rejected, and the rejection factor doubling three times in a row
+    verdict = {c.tag: (c, r) for c, r in zip(dm.build_cases(), dm.references()) if c.fid == 60}
+    assert set(verdict) >= {"negative_scale_larger_chi2", "zero_scale_smaller_chi2", "rho_negative", "rho_zero", "zero_over_zero", "chi2_nan",
+                            "chi2_inf", "chi2_minus_inf", "refused_solve_small_chi2"}
+    assert [verdict["rejection_%d_in_a_row" % k][1].exact[3] for k in (1, 2, 3)] == [4.0, 8.0, 16.0]
+    assert verdict["zero_over_zero"][1].exact[0] == dm.SENTINEL and verdict["zero_scale_smaller_chi2"][1].exact[0] == np.inf
+    assert verdict["refused_solve_small_chi2"][1].exact[0] < -1e300
+    huber = {c.tag: r for c, r in zip(dm.build_cases(), dm.references()) if c.fid == 64}
+    assert list(huber["nan_5.991"].exact) == [dm.SENTINEL, dm.SENTINEL] and list(huber["at_5.991"].exact)[1] == 1.0
     # SE3Quat::exp: both forms of R, each low-trace branch of the quaternion, both signs before each normalisation
     for fid in (30, 31, 32):
         b = set(branches_of(fid))

@@ -1,5 +1,5 @@
-// The shared device primitives of csrc/ evaluated one by one: wave.hpp, lm_block.hpp, lm_record.hpp, se3.hpp, sim3_math.hpp,
-// pose_inertial_edges.hpp, null_vector4.hpp.  This program holds no test data and no copy of any function under test: it reads a file of
+// The shared device primitives of csrc/ evaluated one by one: wave.hpp, lm_block.hpp, lm_record.hpp, lm_step.hpp, se3.hpp,
+// sim3_math.hpp, pose_inertial_edges.hpp, null_vector4.hpp.  This program holds no test data and no copy of any function under test: it reads a file of
 // cases, calls the headers' functions and writes what they returned.  tests/device_math_model.py makes the cases and the expected values.
 //
 //   device_math_test [host] CASES OUT
@@ -36,6 +36,10 @@
 //    44  pi_normalize_rotation  9 -> 9          45  pi_gdir_oplus  Rwg9 u0 u1 -> 9
 //    46  pi_oplus  R9 t3 v3 bg3 ba3 dx15 -> R9 t3 v3 bg3 ba3
 //    50  null_vector4  16 (S row-major) -> v4, S diagonal 4 (after the sweeps)
+//    60  lm_trial_verdict  lambda ni currentChi solver_ok chi2_trial scale -> rho accepted lambda ni currentChi
+//    61  lm_accepted_lambda  lambda rho -> 1                62  lm_iteration_continues  currentChi nBad trials_exhausted rho iniChi -> continues nBad
+//    63  lm_lambda_init  user max_diagonal -> 1             64  lm_huber  e delta dsqr -> rho0 rho1
+//        (60, 64: a NaN result is written as -777.25, so that the host's and the device's NaN need not share a payload)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -49,6 +53,7 @@
 #include "sim3_math.hpp"
 #include "lm_block.hpp"
 #include "lm_record.hpp"
+#include "lm_step.hpp"
 #include "null_vector4.hpp"
 namespace {
 #include "pose_inertial_edges.hpp"
@@ -73,6 +78,7 @@ constexpr Fn kFns[] = {
     {26, 0, 8, 8, 1},     {27, 0, 11, 3, 1},    {28, 0, 7, 8, 1},     {29, 0, 8, 7, 1},     {30, 0, 13, 7, 0},    {31, 0, 13, 7, 0},
     {32, 0, 13, 7, 0},    {33, 0, 1, 1, 0},     {34, 0, 12, 2, 0},    {35, 0, 12, 6, 0},    {40, 0, 3, 9, 1},     {41, 0, 9, 3, 1},
     {42, 0, 3, 9, 1},     {43, 0, 3, 9, 1},     {44, 0, 9, 9, 1},     {45, 0, 11, 9, 1},    {46, 0, 36, 21, 1},   {50, 0, 16, 8, 0},
+    {60, 0, 6, 5, 1},     {61, 0, 2, 1, 1},     {62, 0, 5, 2, 1},     {63, 0, 2, 1, 1},     {64, 0, 3, 2, 1},
 };
 const Fn* find_fn(int fid) {
   for (const Fn& f : kFns) if (f.fid == fid) return &f;
@@ -84,6 +90,8 @@ __host__ __device__ inline void load_pose(const double* p, PoseQ* T) { for (int 
 __host__ __device__ inline void store_pose(const PoseQ& T, double* p) { for (int i = 0; i < 4; i++) p[i] = T.q[i]; for (int i = 0; i < 3; i++) p[4 + i] = T.t[i]; }
 __host__ __device__ inline void load_s3(const double* p, S3* T) { for (int i = 0; i < 4; i++) T->q[i] = p[i]; for (int i = 0; i < 3; i++) T->t[i] = p[4 + i]; T->s = p[7]; }
 __host__ __device__ inline void store_s3(const S3& T, double* p) { for (int i = 0; i < 4; i++) p[i] = T.q[i]; for (int i = 0; i < 3; i++) p[4 + i] = T.t[i]; p[7] = T.s; }
+
+__host__ __device__ inline double nan_as_sentinel(double v) { return v == v ? v : -777.25; }
 
 __host__ __device__ inline void eval_hd(int fid, const double* in, double* out) {
   switch (fid) {
@@ -110,6 +118,29 @@ __host__ __device__ inline void eval_hd(int fid, const double* in, double* out) 
       pi_oplus(&s, in + 21);
       for (int i = 0; i < 9; i++) out[i] = s.R[i];
       for (int i = 0; i < 3; i++) { out[9 + i] = s.t[i]; out[12 + i] = s.v[i]; out[15 + i] = s.bg[i]; out[18 + i] = s.ba[i]; }
+      break;
+    }
+    case 60: {
+      orbg_lm::LmScalars m;
+      m.lambda = in[0]; m.ni = in[1]; m.currentChi = in[2];
+      bool accepted = false;
+      out[0] = nan_as_sentinel(orbg_lm::lm_trial_verdict(m, in[3] != 0, in[4], in[5], &accepted));
+      out[1] = accepted ? 1.0 : 0.0; out[2] = m.lambda; out[3] = m.ni; out[4] = m.currentChi;
+      break;
+    }
+    case 61: out[0] = orbg_lm::lm_accepted_lambda(in[0], in[1]); break;
+    case 62: {
+      orbg_lm::LmScalars m;
+      m.currentChi = in[0]; m.nBad = (int)in[1];
+      out[0] = orbg_lm::lm_iteration_continues(m, in[2] != 0, in[3], in[4]) ? 1.0 : 0.0;
+      out[1] = (double)m.nBad;
+      break;
+    }
+    case 63: out[0] = orbg_lm::lm_lambda_init(in[0], in[1]); break;
+    case 64: {
+      double r0, r1;
+      orbg_lm::lm_huber(in[0], in[1], in[2], &r0, &r1);
+      out[0] = nan_as_sentinel(r0); out[1] = nan_as_sentinel(r1);
       break;
     }
     default: break;
