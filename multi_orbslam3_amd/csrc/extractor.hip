@@ -1726,6 +1726,43 @@ class WorkerPool {
 // handle
 
 static inline double host_now_us() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return 1e6 * (double)t.tv_sec + 1e-3 * (double)t.tv_nsec; }
+// ---- one call of a Frame constructor (or a plain extraction), from its entry point to its collection.  The entry point fills the
+// request, stage_inputs the device images, launch what it decides; the finish functions read it.  A synchronous call keeps its job
+// on the stack; a submitted one lives in the handle (orbx_handle::pending) until the wait.
+enum TailKind { kTailNone, kTailStereo, kTailMono, kTailRgbd };      // what follows the descriptors on the stream
+struct CamOut {                  // host outputs of one camera, any may be NULL
+  orbx_keypoint* kps = nullptr; uint8_t* desc = nullptr; int cap = 0; int* n = nullptr; int* n_mono = nullptr;
+};
+struct FrameJob {
+  // -- the request
+  int ncams = 1;                 // cameras [0, ncams) of the rig are processed
+  int lap[2][2] = {{0, 0}, {0, 0}};   // lapping area per camera; {0, 0}: the rectified stereo and the RGB-D constructor (S/Frame.cc:92-95, :198)
+  int w = 0, hgt = 0;
+  TailKind tail = kTailNone;
+  float bf = 0, b = 0;           // kTailStereo: ComputeStereoMatches (S/Frame.cc:117); bf also for kTailRgbd
+  orbg::RgbdDepthArgs rd{};      // kTailRgbd: mvuRight / mvDepth from the depth image (S/Frame.cc:174-257), img .. bf set by stage_inputs
+  orbm_frame* frame = nullptr;   // the device frame the chain's last kernel builds the grid of (S/Frame.cc:160), may be NULL
+  bool has_view = false;
+  orbm_frame_view view{};        // a copy: the caller's view may be gone by the time of the wait
+  bool undist = false;           // Frame::UndistortKeyPoints on the device (S/Frame.cc:721-754): mDistCoef[0] != 0, needs `frame`
+  orbx_distortion dist{};
+  CamOut out[2];
+  orbx_keypoint* kps_un_out = nullptr;       // host copy of mvKeysUn (out[0].cap entries)
+  float* uright = nullptr;       // host copies of mvuRight / mvDepth (out[0].cap entries)
+  float* depth = nullptr;
+  // -- set by stage_inputs: device addresses only from here on
+  const uint8_t* d_img[2] = {nullptr, nullptr};
+  int stride = 0;
+  // -- decided by launch
+  int prof = 0;
+  int reverse[2] = {0, 0};
+  bool stereo_out = false;       // the chain mirrors mvuRight / mvDepth into the mapped block
+  bool on_gpu = false;           // the quad-trees ran on the device (finish_gpu collects) or run on the host (finish_host)
+  // -- a submitted job
+  bool active = false;           // submitted, not yet waited for
+  bool finished = false;         // the submission ran synchronously (host quad-trees): results are already in n_res
+  int n_res[2] = {0, 0};
+};
 
 struct orbx_handle {
   bool ext_stream = false;                    // `stream` was handed in through orbx_set_stream (never destroyed here)
@@ -1778,7 +1815,7 @@ struct orbx_handle {
   bool last_was_gpu = false;
   int last_ncams = 0;            // cameras the last extraction launched (a rig handle may extract one image)
   long long host_redos = 0;      // frames redone with the host quad-trees after a device list overflowed (orbx_get_host_redo_count)
-  struct ExtractPending* pending = nullptr;    // orbx_frame_stereo_dev_submit .. _wait
+  FrameJob pending;              // the submitted constructor: orbx_frame_*_submit .. _wait
   float timings[8] = {0};
   int profile = 1;   // 0: no events, 1: only the FAST kernel is bracketed (bench roofline), 2: every stage
   int profile_interval = 1;         // level-1 brackets on every k-th extraction only (an event pair costs ~5 us of stream time)
@@ -1816,7 +1853,12 @@ struct orbx_handle {
     tl_n++;
   }
 };
-static void delete_pending(struct ExtractPending* p);   // (defined behind the type)
+
+// a submitted Frame constructor owns the handle (stream, staging slot, pyramid, feature buffers) until it has been waited for
+static inline bool handle_busy(const orbx_handle* h) {
+  return h->ingest_state.load(std::memory_order_acquire) != 0 || h->pending.active || h->pending.finished;
+}
+
 
 // Owned / needed pixel ranges of every level for the level-0 tiles of one axis (see pyr_tower_kernel).
 // s0[l][d], s1[l][d]: the two source indices (level l-1) the taps of pixel d of level l read.  Returns the largest
@@ -2106,7 +2148,6 @@ extern "C" int orbx_destroy(orbx_handle* h) {
   h->d_selreg.release(); h->h_nkp.release(); h->sig.release();
   for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
   if (!h->ext_stream) orbg::release_stream(h->stream);
-  delete_pending(h->pending);
   delete h;
   return ORBG_OK;
 }
@@ -2124,65 +2165,41 @@ extern "C" int orbx_get_tables(const orbx_handle* h, float* scale, float* inv_sc
   return ORBG_OK;
 }
 
-// Work chained behind the descriptor kernel on the same stream, before the single final synchronisation:
-// the rest of the stereo Frame constructor (S/Frame.cc:117 ComputeStereoMatches, :160 AssignFeaturesToGrid).
-struct PostOps {
-  bool stereo = false;
-  float bf = 0, b = 0;
-  float* uright = nullptr;
-  float* depth = nullptr;
-  orbm_frame* frame = nullptr;
-  const orbm_frame_view* view = nullptr;
-  // monocular constructor (S/Frame.cc:260-358): no stereo data; undist: Frame::UndistortKeyPoints on the device (:721-754)
-  bool mono = false, undist = false;
-  orbx_distortion dist{};
-  orbx_keypoint* kps_un_out = nullptr;       // host copy of mvKeysUn (cap[0] entries), may be NULL
-  // RGB-D constructor (S/Frame.cc:174-257): mvuRight / mvDepth from the depth image (rd.img .. rd.bf set by the caller; uright / depth above
-  // are its host outputs); undist as for the monocular constructor
-  bool rgbd = false;
-  orbg::RgbdDepthArgs rd{};
-};
-// Everything the second half of a GPU-path extraction needs (it runs either right away or in orbx_frame_stereo_dev_wait)
-struct ExtractPending {
-  bool active = false;           // submitted, not yet waited for
-  bool finished = false;         // the submission ran synchronously (host quad-trees): results are already in n_res
-  unsigned cams_mask = 0;
-  const uint8_t* d_img0 = nullptr; const uint8_t* d_img1 = nullptr;
-  int w = 0, hgt = 0, stride = 0, ncams = 0, prof = 0;
-  int lap[2][2] = {{0, 0}, {0, 0}};
-  orbx_keypoint* kps_out[2] = {nullptr, nullptr};
-  uint8_t* desc_out[2] = {nullptr, nullptr};
-  int cap[2] = {0, 0};
-  int* n_out[2] = {nullptr, nullptr};
-  int* n_mono_out[2] = {nullptr, nullptr};
-  bool has_post = false;
-  PostOps post;
-  orbm_frame_view view_copy;     // the caller's view may be gone by the time of the wait
-  int reverse[2] = {0, 0};
-  bool stereo_out = false;
-  int n_res[2] = {0, 0};
-};
-static void delete_pending(ExtractPending* p) { delete p; }
-int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, int n, hipStream_t stream, const int* d_n,
-                         volatile unsigned* done_flag, unsigned done_seq, const StereoFinalizeArgs* fin, const orbg::UndistortArgs* un = nullptr,
-                         bool mono = false, const orbg::RgbdDepthArgs* rgbd = nullptr);
+int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, const orbg::AttachTail& tail);   // matcher.hip
+void orbm_internal_set_n(orbm_frame* f, int n);
+int orbx_internal_kp_capacity(orbx_handle* h);
 // arguments of the undistortion in front of the grid build (the handle's mvKeysUn buffers are sized here)
-static int make_undistort_args(orbx_handle* h, const PostOps* post, orbg::UndistortArgs* ua) {
+static int make_undistort_args(orbx_handle* h, const FrameJob& j, orbg::UndistortArgs* ua) {
   memset(ua, 0, sizeof(*ua));
-  if (!post || !post->undist) return ORBG_OK;
+  if (!j.undist) return ORBG_OK;
   const size_t cap = h->d_kps.cap;
   int rc;
   if ((rc = h->d_kps_un.reserve(cap)) || (rc = h->h_kps_un.reserve(cap))) return rc;
   ua->on = 1;
-  ua->fx = post->view->fx; ua->fy = post->view->fy; ua->cx = post->view->cx; ua->cy = post->view->cy;
-  ua->k1 = post->dist.k1; ua->k2 = post->dist.k2; ua->p1 = post->dist.p1; ua->p2 = post->dist.p2; ua->k3 = post->dist.k3;
+  ua->fx = j.view.fx; ua->fy = j.view.fy; ua->cx = j.view.cx; ua->cy = j.view.cy;
+  ua->k1 = j.dist.k1; ua->k2 = j.dist.k2; ua->p1 = j.dist.p1; ua->p2 = j.dist.p2; ua->k3 = j.dist.k3;
   ua->src = h->d_kps.p; ua->dst = h->d_kps_un.p; ua->dst_host = h->h_kps_un.d;
   return ORBG_OK;
 }
-void orbm_internal_set_n(orbm_frame* f, int n);
-int orbx_internal_kp_capacity(orbx_handle* h);
+
+// defer_finalize: do not launch the median rejection; hand its arguments back (it then runs next to the grid build)
 static int launch_stereo(orbx_handle* h, float bf, float b, hipStream_t st, bool device_counts, float* host_mirror,
-                         StereoFinalizeArgs* defer_finalize = nullptr);
+                         StereoFinalizeArgs* defer_finalize = nullptr) {
+  const int nl = device_counts ? h->sel_bound : h->n_kp[0], nr = h->n_kp[1];
+  // the stereo key packs the right keypoint's index into 16 bits (dist << 16 | iR)
+  if (nl >= ORBG_MAX_FRAME_FEATURES || nr >= ORBG_MAX_FRAME_FEATURES || (device_counts && orbx_internal_kp_capacity(h) >= 2 * ORBG_MAX_FRAME_FEATURES))
+    return ORBG_CAP_EXCEEDED;
+  if (h->profile >= 2) ORBG_HIP(hipEventRecord(h->ev[5], st));
+  if (nl > 0) {
+    const int* dn = device_counts ? h->d_nkp.p : nullptr;
+    hipLaunchKernelGGL(stereo_match_kernel, dim3((nl + 3) / 4), dim3(256), 0, st, h->d_pyr.p, h->geom, h->d_kps.p, h->d_desc.p,
+                       nl, h->d_kps.p + nl, h->d_desc.p + (size_t)nl * 32, nr, bf, b, h->d_uright.p, h->d_depth.p, h->d_sad.p, dn);
+    if (defer_finalize) *defer_finalize = StereoFinalizeArgs{h->d_uright.p, h->d_depth.p, h->d_sad.p, nl, dn, host_mirror, nullptr};
+    else hipLaunchKernelGGL(stereo_finalize_kernel, dim3(1), dim3(256), 0, st, h->d_uright.p, h->d_depth.p, h->d_sad.p, nl, dn, host_mirror);
+  }
+  if (h->profile >= 2) ORBG_HIP(hipEventRecord(h->ev[6], st));
+  return ORBG_OK;
+}
 
 // ---- RGB-D (rgbd.hpp).  ComputeStereoFromRGBD as a kernel of its own: a constructor without a frame object (no grid to build) and
 // orbx_depth_at_points; with a frame it is part of the chain's last launch (rgbd_grid_kernel, matcher.hip).
@@ -2209,30 +2226,20 @@ __global__ __launch_bounds__(256) void rgbd_gray_kernel(orbg::RgbdGrayArgs a) {
   orbg::rgbd_gray4(a, 4 * (int)(blockIdx.x * 64 + (threadIdx.x & 63)), (int)(blockIdx.y * 4 + (threadIdx.x >> 6)));
 }
 // what the chain's tail needs of the handle for an RGB-D frame
-static orbg::RgbdDepthArgs rgbd_tail_args(orbx_handle* h, const PostOps* post, bool host_out) {
-  orbg::RgbdDepthArgs rd = post->rd;
+static orbg::RgbdDepthArgs rgbd_tail_args(orbx_handle* h, const FrameJob& j, bool host_out) {
+  orbg::RgbdDepthArgs rd = j.rd;
   rd.uright = h->d_uright.p; rd.depth = h->d_depth.p; rd.host_out = host_out ? h->h_stereo.d : nullptr;
   return rd;
 }
 
-// Core: cams_mask selects which cameras of the rig are processed; d_img are device pointers.
-static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img0, const uint8_t* d_img1, int w, int hgt,
-                        int stride, const int lap[2][2], orbx_keypoint* kps_out[2], uint8_t* desc_out[2], const int cap[2],
-                        int* n_out[2], int* n_mono_out[2], const PostOps* post = nullptr, bool force_host = false,
-                        bool submit_only = false);
-static int extract_finish_gpu(orbx_handle* h, ExtractPending& c);
-
-static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img0, const uint8_t* d_img1, int w, int hgt,
-                        int stride, const int lap[2][2], orbx_keypoint* kps_out[2], uint8_t* desc_out[2], const int cap[2],
-                        int* n_out[2], int* n_mono_out[2], const PostOps* post, bool force_host, bool submit_only) {
-  // a submitted Frame constructor owns the handle (stream, pyramid, feature buffers) until it has been waited for
-  if (h->pending && h->pending->active) return ORBG_BAD_ARG;
-  int rc = setup_geometry(h, w, hgt);
-  if (rc) return rc;
+// Launch: every kernel of the job's chain on the handle's stream.  With the quad-trees on the device that is the whole constructor,
+// down to the grid build and the completion word (finish_gpu collects it); with the host quad-trees it ends behind the candidate
+// gather (finish_host goes on from there).  force_host: the redo of a frame whose device lists overflowed.
+static int launch(orbx_handle* h, FrameJob& j, bool force_host) {
+  int rc;
   const PyrGeom& g = h->geom;
   const int nl = g.n_levels;
-  const int ncams = (cams_mask & 2) ? 2 : 1;       // cameras [0, ncams) are launched; mask 2 alone is not supported
-  if (cams_mask == 2) return ORBG_BAD_ARG;
+  const int ncams = j.ncams, w = j.w, stride = j.stride;
   const int n_cells = (int)h->cells.size();
   hipStream_t st = h->stream;
   int prof = h->profile;
@@ -2244,126 +2251,117 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
   int reverse[2] = {0, 0};
   for (int c = 0; c < ncams && use_gpu; c++) {
     const float xmin = (float)kEdge, xmax = (float)w;          // keypoint x range in level-0 pixels: [19, w)
-    if ((float)lap[c][1] < xmin || (float)lap[c][0] > xmax) reverse[c] = 0;
-    else if ((float)lap[c][0] <= xmin && (float)lap[c][1] >= xmax) reverse[c] = 1;
+    if ((float)j.lap[c][1] < xmin || (float)j.lap[c][0] > xmax) reverse[c] = 0;
+    else if ((float)j.lap[c][0] <= xmin && (float)j.lap[c][1] >= xmax) reverse[c] = 1;
     else use_gpu = false;
   }
   h->last_was_gpu = use_gpu;
   h->last_ncams = ncams;
   if (!use_gpu) h->pool->prepare();              // wake the host quad-tree workers only when they will be used
-  const bool want_desc = desc_out[0] || desc_out[1];
-  const bool do_stereo = use_gpu && post && post->stereo && ncams == 2;
-  const bool do_rgbd = post && post->rgbd && ncams == 1;
-  const bool stereo_out = (do_stereo || (do_rgbd && use_gpu)) && (post->uright || post->depth);
+  const bool want_desc = j.out[0].desc || j.out[1].desc;
+  const bool do_stereo = use_gpu && j.tail == kTailStereo && ncams == 2;
+  const bool do_rgbd = j.tail == kTailRgbd && ncams == 1;
+  const bool stereo_out = (do_stereo || (do_rgbd && use_gpu)) && (j.uright || j.depth);
+  j.prof = prof; j.reverse[0] = reverse[0]; j.reverse[1] = reverse[1]; j.stereo_out = stereo_out; j.on_gpu = use_gpu;
   OctCfg oc = h->octcfg;
   oc.n_cams = ncams;                          // cameras processed by THIS call (a rig handle may extract one image)
-  const uint8_t* const img1 = d_img1 ? d_img1 : d_img0;
-  // every launch of the chain up to (not including) the grid build; prof_ > 0 adds the event brackets
-  auto launch_chain = [&](int prof_) -> int {
-    if (prof_ >= 2) ORBG_HIP(hipEventRecord(h->ev[0], st));
-    const int pk = h->prof_kernel;
-    auto br0 = [&](int which) -> int { if (prof_ >= 1 && pk == which) ORBG_HIP(hipEventRecord(h->ev[1], st)); return ORBG_OK; };
-    auto br1 = [&](int which) -> int { if (prof_ >= 1 && pk == which) ORBG_HIP(hipEventRecord(h->ev[7], st)); return ORBG_OK; };
-    if (br0(ORBX_PROF_PYRAMID)) return ORBG_HIP_ERROR;
-    if (h->tower_T > 0) {
-      hipLaunchKernelGGL(pyr_tower_kernel, dim3(h->tower_ntx, h->tower_nty, ncams), dim3(kTwThreads), 0, st, d_img0, img1,
-                         stride, h->d_pyr.p, g, h->d_xtab.p, h->d_ytab.p, h->d_tower_x.p, h->d_tower_y.p);
-    } else {
-      const LevelGeom& L0 = g.lv[0];
-      dim3 grid((L0.w + 2 * kEdge + 63) / 64, (L0.h + 2 * kEdge + 3) / 4, ncams);
-      hipLaunchKernelGGL(pyr_level0_kernel, grid, dim3(256), 0, st, d_img0, img1, stride, h->d_pyr.p, g);
-      for (int l = 1; l < nl; l++) {
-        const LevelGeom& L = g.lv[l];
-        dim3 gr((L.w + 2 * kEdge + 63) / 64, (L.h + 2 * kEdge + 3) / 4, ncams);
-        hipLaunchKernelGGL(pyr_resize_kernel, gr, dim3(256), 0, st, h->d_pyr.p, g, l, h->d_xtab.p, h->d_ytab.p);
-      }
+  const uint8_t* const d_img0 = j.d_img[0];
+  const uint8_t* const img1 = j.d_img[1] ? j.d_img[1] : d_img0;
+  // every launch of the chain up to (not including) the grid build; prof > 0 adds the event brackets
+  if (prof >= 2) ORBG_HIP(hipEventRecord(h->ev[0], st));
+  const int pk = h->prof_kernel;
+  auto br0 = [&](int which) -> int { if (prof >= 1 && pk == which) ORBG_HIP(hipEventRecord(h->ev[1], st)); return ORBG_OK; };
+  auto br1 = [&](int which) -> int { if (prof >= 1 && pk == which) ORBG_HIP(hipEventRecord(h->ev[7], st)); return ORBG_OK; };
+  if (br0(ORBX_PROF_PYRAMID)) return ORBG_HIP_ERROR;
+  if (h->tower_T > 0) {
+    hipLaunchKernelGGL(pyr_tower_kernel, dim3(h->tower_ntx, h->tower_nty, ncams), dim3(kTwThreads), 0, st, d_img0, img1,
+                       stride, h->d_pyr.p, g, h->d_xtab.p, h->d_ytab.p, h->d_tower_x.p, h->d_tower_y.p);
+  } else {
+    const LevelGeom& L0 = g.lv[0];
+    dim3 grid((L0.w + 2 * kEdge + 63) / 64, (L0.h + 2 * kEdge + 3) / 4, ncams);
+    hipLaunchKernelGGL(pyr_level0_kernel, grid, dim3(256), 0, st, d_img0, img1, stride, h->d_pyr.p, g);
+    for (int l = 1; l < nl; l++) {
+      const LevelGeom& L = g.lv[l];
+      dim3 gr((L.w + 2 * kEdge + 63) / 64, (L.h + 2 * kEdge + 3) / 4, ncams);
+      hipLaunchKernelGGL(pyr_resize_kernel, gr, dim3(256), 0, st, h->d_pyr.p, g, l, h->d_xtab.p, h->d_ytab.p);
     }
-    if (br1(ORBX_PROF_PYRAMID)) return ORBG_HIP_ERROR;
-    if (prof_ >= 2 && pk != ORBX_PROF_FAST) ORBG_HIP(hipEventRecord(h->ev[8], st));      // end of the pyramid for the stage timings
-    if (n_cells > 0) {
-      if (br0(ORBX_PROF_FAST)) return ORBG_HIP_ERROR;
-      hipLaunchKernelGGL(fast_cells_kernel, dim3(8 * ((n_cells + 7) / 8), ncams), dim3(256), 0, st, h->d_pyr.p, g, h->d_cells.p, n_cells,
-                         std::max(h->cfg.ini_th_fast, 1), std::max(h->cfg.min_th_fast, 1), h->d_slots.p, h->d_counts.p);
-      if (br1(ORBX_PROF_FAST)) return ORBG_HIP_ERROR;
-      // the GPU quad-trees take the candidates from the per-cell slots themselves (octree_kernel): the compacted list is only
-      // built for the host quad-trees (and, on demand, for orbx_get_candidates)
-      if (!use_gpu)
-        hipLaunchKernelGGL(gather_cells_kernel, dim3(n_cells, ncams), dim3(256), 0, st, h->d_slots.p, h->d_counts.p, g,
-                           h->d_cells.p, n_cells, ncams, use_gpu ? h->d_hdr.p : h->hdr.d, use_gpu ? h->d_cand.p : h->cand.d, h->cand_cap);
-    }
-    if (use_gpu) {
-      // ---- everything stays on the device: quad-trees -> descriptors -> (stereo, grid) -> ONE synchronisation
-      if (br0(ORBX_PROF_OCTREE)) return ORBG_HIP_ERROR;
-      hipLaunchKernelGGL(octree_kernel, dim3(ncams * nl), dim3(kOctThreads), 0, st, h->d_cand.p, h->d_hdr.p, g, oc,
-                         h->d_selreg.p, h->d_lvlcount.p, h->d_overflow.p, h->cand_cap, h->d_slots.p, h->d_counts.p, n_cells);
-      if (br1(ORBX_PROF_OCTREE)) return ORBG_HIP_ERROR;
-      if (br0(ORBX_PROF_ORIENT_DESC)) return ORBG_HIP_ERROR;
-      auto launch_od = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3((h->sel_bound + kKpPerBlock - 1) / kKpPerBlock), dim3(256), 0, st, h->d_pyr.p, g,
-                           oc, h->d_selreg.p, h->d_lvlcount.p, h->umax, reverse[0], reverse[1], h->d_kps.p, h->d_desc.p, h->h_kps.d,
-                           want_desc ? h->h_desc.d : (uint8_t*)nullptr, h->d_nkp.p, h->h_nkp.d, h->d_overflow.p);
-      };
-      if (h->taps_variant == 0) launch_od(orient_desc_gpu_kernel<0>);
-      else if (h->taps_variant == 1) launch_od(orient_desc_gpu_kernel<1>);
-      else launch_od(orient_desc_gpu_kernel<2>);
-      if (br1(ORBX_PROF_ORIENT_DESC)) return ORBG_HIP_ERROR;
-      if (do_stereo) {
-        // with a device frame to build, the median rejection runs as the second workgroup of the grid build (one launch less)
-        StereoFinalizeArgs unused;
-        const int rcs = launch_stereo(h, post->bf, post->b, st, true, stereo_out ? h->h_stereo.d : nullptr,
-                                      post->frame ? &unused : nullptr);
-        if (rcs) return rcs;
-      }
-      // RGB-D without a frame object: no undistortion (refused), no grid -- the depth lookup is the chain's tail
-      if (do_rgbd && !post->frame && h->sel_bound > 0)
-        hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->sel_bound + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, post, stereo_out),
-                           0, h->d_nkp.p);
-    }
-    return ORBG_OK;
-  };
-  if ((rc = launch_chain(prof))) return rc;
-  if (use_gpu) {
-    bool posted = false;
-    if (post) {
-      if (post->frame) {
-        // the grid build is the last kernel of the chain: it posts the completion word itself (no signal kernel)
-        unsigned seq; volatile unsigned* flag;
-        if ((rc = h->sig.arm(&seq, &flag))) return rc;
-        StereoFinalizeArgs fin{};
-        const bool with_fin = do_stereo && h->sel_bound > 0;
-        if (with_fin)
-          fin = StereoFinalizeArgs{h->d_uright.p, h->d_depth.p, h->d_sad.p, h->sel_bound, h->d_nkp.p, stereo_out ? h->h_stereo.d : nullptr,
-                                   reinterpret_cast<unsigned*>(h->d_overflow.p + 2)};
-        orbg::UndistortArgs ua;
-        if ((rc = make_undistort_args(h, post, &ua))) return rc;
-        orbg::RgbdDepthArgs rd;
-        if (do_rgbd) rd = rgbd_tail_args(h, post, stereo_out);
-        if ((rc = orbm_internal_attach(post->frame, h, post->view, -1, st, h->d_nkp.p, flag, seq, with_fin ? &fin : nullptr, &ua, post->mono,
-                                       do_rgbd ? &rd : nullptr))) return rc;
-        posted = true;
-      }
-    }
-    ORBG_HIP(hipGetLastError());
-    if (!posted && (rc = h->sig.post(st))) return rc;          // completion word in pinned memory
-    ExtractPending local;
-    if (submit_only && !h->pending) h->pending = new ExtractPending();
-    ExtractPending& c = submit_only ? *h->pending : local;
-    c.active = submit_only; c.finished = false;
-    c.cams_mask = cams_mask; c.d_img0 = d_img0; c.d_img1 = d_img1; c.w = w; c.hgt = hgt; c.stride = stride; c.ncams = ncams; c.prof = prof;
-    for (int a = 0; a < 2; a++) {
-      c.lap[a][0] = lap[a][0]; c.lap[a][1] = lap[a][1];
-      c.kps_out[a] = kps_out[a]; c.desc_out[a] = desc_out[a]; c.cap[a] = cap[a]; c.n_out[a] = n_out[a]; c.n_mono_out[a] = n_mono_out[a];
-      c.reverse[a] = reverse[a];
-    }
-    c.has_post = post != nullptr;
-    if (post) {
-      c.post = *post;
-      if (post->view) { c.view_copy = *post->view; c.post.view = &c.view_copy; }
-    }
-    c.stereo_out = stereo_out;
-    if (submit_only) return ORBG_OK;
-    return extract_finish_gpu(h, c);
   }
+  if (br1(ORBX_PROF_PYRAMID)) return ORBG_HIP_ERROR;
+  if (prof >= 2 && pk != ORBX_PROF_FAST) ORBG_HIP(hipEventRecord(h->ev[8], st));      // end of the pyramid for the stage timings
+  if (n_cells > 0) {
+    if (br0(ORBX_PROF_FAST)) return ORBG_HIP_ERROR;
+    hipLaunchKernelGGL(fast_cells_kernel, dim3(8 * ((n_cells + 7) / 8), ncams), dim3(256), 0, st, h->d_pyr.p, g, h->d_cells.p, n_cells,
+                       std::max(h->cfg.ini_th_fast, 1), std::max(h->cfg.min_th_fast, 1), h->d_slots.p, h->d_counts.p);
+    if (br1(ORBX_PROF_FAST)) return ORBG_HIP_ERROR;
+    // the GPU quad-trees take the candidates from the per-cell slots themselves (octree_kernel): the compacted list is only
+    // built for the host quad-trees (and, on demand, for orbx_get_candidates)
+    if (!use_gpu)
+      hipLaunchKernelGGL(gather_cells_kernel, dim3(n_cells, ncams), dim3(256), 0, st, h->d_slots.p, h->d_counts.p, g,
+                         h->d_cells.p, n_cells, ncams, use_gpu ? h->d_hdr.p : h->hdr.d, use_gpu ? h->d_cand.p : h->cand.d, h->cand_cap);
+  }
+  if (use_gpu) {
+    // ---- everything stays on the device: quad-trees -> descriptors -> (stereo, grid) -> ONE synchronisation
+    if (br0(ORBX_PROF_OCTREE)) return ORBG_HIP_ERROR;
+    hipLaunchKernelGGL(octree_kernel, dim3(ncams * nl), dim3(kOctThreads), 0, st, h->d_cand.p, h->d_hdr.p, g, oc,
+                       h->d_selreg.p, h->d_lvlcount.p, h->d_overflow.p, h->cand_cap, h->d_slots.p, h->d_counts.p, n_cells);
+    if (br1(ORBX_PROF_OCTREE)) return ORBG_HIP_ERROR;
+    if (br0(ORBX_PROF_ORIENT_DESC)) return ORBG_HIP_ERROR;
+    auto launch_od = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3((h->sel_bound + kKpPerBlock - 1) / kKpPerBlock), dim3(256), 0, st, h->d_pyr.p, g,
+                         oc, h->d_selreg.p, h->d_lvlcount.p, h->umax, reverse[0], reverse[1], h->d_kps.p, h->d_desc.p, h->h_kps.d,
+                         want_desc ? h->h_desc.d : (uint8_t*)nullptr, h->d_nkp.p, h->h_nkp.d, h->d_overflow.p);
+    };
+    if (h->taps_variant == 0) launch_od(orient_desc_gpu_kernel<0>);
+    else if (h->taps_variant == 1) launch_od(orient_desc_gpu_kernel<1>);
+    else launch_od(orient_desc_gpu_kernel<2>);
+    if (br1(ORBX_PROF_ORIENT_DESC)) return ORBG_HIP_ERROR;
+    if (do_stereo) {
+      // with a device frame to build, the median rejection runs as the second workgroup of the grid build (one launch less)
+      StereoFinalizeArgs unused;
+      const int rcs = launch_stereo(h, j.bf, j.b, st, true, stereo_out ? h->h_stereo.d : nullptr,
+                                    j.frame ? &unused : nullptr);
+      if (rcs) return rcs;
+    }
+    // RGB-D without a frame object: no undistortion (refused), no grid -- the depth lookup is the chain's tail
+    if (do_rgbd && !j.frame && h->sel_bound > 0)
+      hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->sel_bound + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, j, stereo_out),
+                         0, h->d_nkp.p);
+  }
+  if (!use_gpu) return ORBG_OK;
+  bool posted = false;
+  if (j.frame) {
+    // the grid build is the last kernel of the chain: it posts the completion word itself (no signal kernel)
+    orbg::AttachTail t;
+    t.stream = st; t.d_n = h->d_nkp.p; t.mono = j.tail == kTailMono;
+    if ((rc = h->sig.arm(&t.done_seq, &t.done_flag))) return rc;
+    StereoFinalizeArgs fin{};
+    if (do_stereo && h->sel_bound > 0) {
+      fin = StereoFinalizeArgs{h->d_uright.p, h->d_depth.p, h->d_sad.p, h->sel_bound, h->d_nkp.p, stereo_out ? h->h_stereo.d : nullptr,
+                               reinterpret_cast<unsigned*>(h->d_overflow.p + 2)};
+      t.fin = &fin;
+    }
+    orbg::UndistortArgs ua;
+    if ((rc = make_undistort_args(h, j, &ua))) return rc;
+    t.un = &ua;
+    orbg::RgbdDepthArgs rd;
+    if (do_rgbd) { rd = rgbd_tail_args(h, j, stereo_out); t.rgbd = &rd; }
+    if ((rc = orbm_internal_attach(j.frame, h, &j.view, t))) return rc;
+    posted = true;
+  }
+  ORBG_HIP(hipGetLastError());
+  if (!posted && (rc = h->sig.post(st))) return rc;          // completion word in pinned memory
+  return ORBG_OK;
+}
+
+// Finish with the host quad-trees, behind a launch that left them to the host: quad-tree per (camera, level) on the worker pool,
+// orientation + descriptors, the frame's tail, ONE synchronisation, host copies.
+static int finish_host(orbx_handle* h, FrameJob& j) {
+  int rc;
+  const PyrGeom& g = h->geom;
+  const int nl = g.n_levels, ncams = j.ncams, prof = j.prof;
+  const int n_cells = (int)h->cells.size();
+  hipStream_t st = h->stream;
+  const bool do_rgbd = j.tail == kTailRgbd && ncams == 1;
   if (prof >= 2) ORBG_HIP(hipEventRecord(h->ev[2], st));
   ORBG_HIP(hipStreamSynchronize(st));
   const auto t_host0 = std::chrono::steady_clock::now();
@@ -2417,18 +2415,18 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
     for (int l = 0; l < nl; l++) level_kps.insert(level_kps.end(), h->level_sel[cam][l].begin(), h->level_sel[cam][l].end());
     const int nk = (int)level_kps.size();
     h->n_kp[cam] = nk;
-    if (n_out[cam]) *n_out[cam] = nk;
-    if ((kps_out[cam] || desc_out[cam]) && nk > cap[cam]) return ORBG_CAP_EXCEEDED;
+    if (j.out[cam].n) *j.out[cam].n = nk;
+    if ((j.out[cam].kps || j.out[cam].desc) && nk > j.out[cam].cap) return ORBG_CAP_EXCEEDED;
     if ((size_t)(n_sel_total + nk) > h->sel.cap) return ORBG_CAP_EXCEEDED;
     int monoIndex = 0, stereoIndex = nk - 1;
     for (SelKp& s : level_kps) {
       float px = (float)s.x;
       if (s.level != 0) px *= h->scale[s.level];
-      if (px >= (float)lap[cam][0] && px <= (float)lap[cam][1]) s.out_idx = stereoIndex--;
+      if (px >= (float)j.lap[cam][0] && px <= (float)j.lap[cam][1]) s.out_idx = stereoIndex--;
       else s.out_idx = monoIndex++;
       h->sel.h[n_sel_total++] = s;
     }
-    if (n_mono_out[cam]) *n_mono_out[cam] = monoIndex;
+    if (j.out[cam].n_mono) *j.out[cam].n_mono = monoIndex;
   }
   if (ncams == 1) h->n_kp[1] = 0;
   const auto t_host1 = std::chrono::steady_clock::now();
@@ -2445,54 +2443,56 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
   }
   if (prof >= 2) ORBG_HIP(hipEventRecord(h->ev[4], st));
   bool stereo_out_host = false;
-  if (post) {
-    if (post->stereo && ncams == 2) {
-      if ((rc = launch_stereo(h, post->bf, post->b, st, false, nullptr))) return rc;
-      if (h->n_kp[0] > 0 && (post->uright || post->depth)) {
+  if (j.tail != kTailNone) {
+    if (j.tail == kTailStereo && ncams == 2) {
+      if ((rc = launch_stereo(h, j.bf, j.b, st, false, nullptr))) return rc;
+      if (h->n_kp[0] > 0 && (j.uright || j.depth)) {
         ORBG_HIP(hipMemcpyAsync(h->h_stereo.h, h->d_uright.p, (size_t)h->n_kp[0] * 4, hipMemcpyDeviceToHost, st));
         ORBG_HIP(hipMemcpyAsync(h->h_stereo.h + h->n_kp[0], h->d_depth.p, (size_t)h->n_kp[0] * 4, hipMemcpyDeviceToHost, st));
         stereo_out_host = true;
       }
     }
     // RGB-D: the kernels mirror mvuRight / mvDepth into the mapped block themselves (complete at the synchronisation below)
-    const bool rgbd_out = do_rgbd && h->n_kp[0] > 0 && (post->uright || post->depth);
-    if (post->frame) {
+    const bool rgbd_out = do_rgbd && h->n_kp[0] > 0 && (j.uright || j.depth);
+    if (j.frame) {
+      orbg::AttachTail t;
+      t.n = h->n_kp[0]; t.stream = st; t.mono = j.tail == kTailMono;
       orbg::UndistortArgs ua;
-      if ((rc = make_undistort_args(h, post, &ua))) return rc;
+      if ((rc = make_undistort_args(h, j, &ua))) return rc;
+      t.un = &ua;
       orbg::RgbdDepthArgs rd;
-      if (do_rgbd) rd = rgbd_tail_args(h, post, rgbd_out);
-      if ((rc = orbm_internal_attach(post->frame, h, post->view, h->n_kp[0], st, nullptr, nullptr, 0u, nullptr, &ua, post->mono,
-                                     do_rgbd ? &rd : nullptr))) return rc;
+      if (do_rgbd) { rd = rgbd_tail_args(h, j, rgbd_out); t.rgbd = &rd; }
+      if ((rc = orbm_internal_attach(j.frame, h, &j.view, t))) return rc;
     } else if (do_rgbd && h->n_kp[0] > 0) {
-      hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->n_kp[0] + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, post, rgbd_out),
+      hipLaunchKernelGGL(rgbd_depth_kernel, dim3((h->n_kp[0] + 255) / 256), dim3(256), 0, st, h->d_kps.p, rgbd_tail_args(h, j, rgbd_out),
                          h->n_kp[0], (const int*)nullptr);
     }
     if (rgbd_out) stereo_out_host = true;
   }
-  const bool want_out = kps_out[0] || desc_out[0] || kps_out[1] || desc_out[1];
+  const bool want_out = j.out[0].kps || j.out[0].desc || j.out[1].kps || j.out[1].desc;
   if (n_sel_total > 0) {
     // the keypoints are always mirrored into pinned host memory: the matchers' serial commit needs octave / angle
     ORBG_HIP(hipMemcpyAsync(h->h_kps.h, h->d_kps.p, (size_t)n_sel_total * sizeof(orbx_keypoint), hipMemcpyDeviceToHost, st));
-    if (desc_out[0] || desc_out[1])
+    if (j.out[0].desc || j.out[1].desc)
       ORBG_HIP(hipMemcpyAsync(h->h_desc.h, h->d_desc.p, (size_t)n_sel_total * 32, hipMemcpyDeviceToHost, st));
   }
   ORBG_HIP(hipStreamSynchronize(st));
   if (want_out) {
     int base = 0;
     for (int cam = 0; cam < ncams; cam++) {
-      if (kps_out[cam]) memcpy(kps_out[cam], h->h_kps.h + base, (size_t)h->n_kp[cam] * sizeof(orbx_keypoint));
-      if (desc_out[cam]) memcpy(desc_out[cam], h->h_desc.h + (size_t)base * 32, (size_t)h->n_kp[cam] * 32);
+      if (j.out[cam].kps) memcpy(j.out[cam].kps, h->h_kps.h + base, (size_t)h->n_kp[cam] * sizeof(orbx_keypoint));
+      if (j.out[cam].desc) memcpy(j.out[cam].desc, h->h_desc.h + (size_t)base * 32, (size_t)h->n_kp[cam] * 32);
       base += h->n_kp[cam];
     }
   }
-  if (stereo_out_host && do_rgbd && h->n_kp[0] > cap[0]) return ORBG_CAP_EXCEEDED;
+  if (stereo_out_host && do_rgbd && h->n_kp[0] > j.out[0].cap) return ORBG_CAP_EXCEEDED;
   if (stereo_out_host) {
-    if (post->uright) memcpy(post->uright, h->h_stereo.h, (size_t)h->n_kp[0] * 4);
-    if (post->depth) memcpy(post->depth, h->h_stereo.h + h->n_kp[0], (size_t)h->n_kp[0] * 4);
+    if (j.uright) memcpy(j.uright, h->h_stereo.h, (size_t)h->n_kp[0] * 4);
+    if (j.depth) memcpy(j.depth, h->h_stereo.h + h->n_kp[0], (size_t)h->n_kp[0] * 4);
   }
-  if (post && post->kps_un_out) {
-    if (h->n_kp[0] > cap[0]) return ORBG_CAP_EXCEEDED;
-    memcpy(post->kps_un_out, (post->undist && post->frame) ? h->h_kps_un.h : h->h_kps.h, (size_t)h->n_kp[0] * sizeof(orbx_keypoint));
+  if (j.kps_un_out) {
+    if (h->n_kp[0] > j.out[0].cap) return ORBG_CAP_EXCEEDED;
+    memcpy(j.kps_un_out, (j.undist && j.frame) ? h->h_kps_un.h : h->h_kps.h, (size_t)h->n_kp[0] * sizeof(orbx_keypoint));
   }
   float ms;
   h->timings[2] = std::chrono::duration<float, std::milli>(t_host1 - t_host0).count();  // host quad-tree
@@ -2503,6 +2503,52 @@ static int extract_core(orbx_handle* h, unsigned cams_mask, const uint8_t* d_img
     if (hipEventElapsedTime(&ms, h->ev[3], h->ev[4]) == hipSuccess) h->timings[3] = ms;   // orientation + descriptors
   }
   if (prof >= 1 && n_cells > 0 && hipEventElapsedTime(&ms, h->ev[1], h->ev[7]) == hipSuccess) { h->timings[5] = ms; h->fast_ms_sum += ms; h->fast_ms_n++; }
+  return ORBG_OK;
+}
+
+// Finish on the GPU path: wait for the completion word, fall back to the host quad-trees if a level overflowed the device
+// lists, hand the counts (and the optional host copies) over.
+static int finish_gpu(orbx_handle* h, FrameJob& j) {
+  int rc;
+  hipStream_t st = h->stream;
+  if ((rc = h->sig.wait(st))) return rc;            // the overflow flag came with the keypoint counts
+  // (img_upload_pair_kernel gave up waiting for the host's pack: the images never reached the device)
+  if (h->up_seq && h->up_ready.h && h->up_ready.h[8] == h->up_seq) return ORBG_INTERNAL;
+  if (h->h_nkp.h[2]) {
+    // a level had more candidates / nodes than the LDS-resident quad-tree holds: redo this frame with the host trees
+    // (the only place that acts on the flag: the synchronous calls and orbx_frame_stereo_dev_wait both finish here)
+    h->host_redos++;
+    ORBG_HIP(hipMemsetAsync(h->d_overflow.p, 0, sizeof(int), st));
+    if ((rc = launch(h, j, /*force_host=*/true))) return rc;
+    return finish_host(h, j);
+  }
+  const int ncams = j.ncams;
+  h->n_kp[0] = h->h_nkp.h[0];
+  h->n_kp[1] = ncams == 2 ? h->h_nkp.h[1] : 0;
+  int base = 0;
+  for (int cam = 0; cam < ncams; cam++) {
+    const CamOut& o = j.out[cam];
+    const int nk = h->n_kp[cam];
+    if (o.n) *o.n = nk;
+    if (o.n_mono) *o.n_mono = j.reverse[cam] ? 0 : nk;
+    if ((o.kps || o.desc) && nk > o.cap) return ORBG_CAP_EXCEEDED;
+    if (o.kps) memcpy(o.kps, h->h_kps.h + base, (size_t)nk * sizeof(orbx_keypoint));
+    if (o.desc) memcpy(o.desc, h->h_desc.h + (size_t)base * 32, (size_t)nk * 32);
+    base += nk;
+  }
+  if (j.frame) orbm_internal_set_n(j.frame, h->n_kp[0]);
+  if (j.kps_un_out) {
+    if (h->n_kp[0] > j.out[0].cap) return ORBG_CAP_EXCEEDED;
+    memcpy(j.kps_un_out, (j.undist && j.frame) ? h->h_kps_un.h : h->h_kps.h, (size_t)h->n_kp[0] * sizeof(orbx_keypoint));
+  }
+  if (j.stereo_out && h->n_kp[0] > j.out[0].cap) return ORBG_CAP_EXCEEDED;      // uright / depth hold cap_left entries like the other outputs
+  if (j.stereo_out) {
+    if (j.uright) memcpy(j.uright, h->h_stereo.h, (size_t)h->n_kp[0] * 4);
+    if (j.depth) memcpy(j.depth, h->h_stereo.h + h->n_kp[0], (size_t)h->n_kp[0] * 4);
+  }
+  float ms;
+  h->timings[2] = 0;
+  if (j.prof >= 1 && hipEventElapsedTime(&ms, h->ev[1], h->ev[7]) == hipSuccess) { h->timings[5] = ms; h->fast_ms_sum += ms; h->fast_ms_n++; }
   return ORBG_OK;
 }
 
@@ -2564,11 +2610,6 @@ __global__ __launch_bounds__(kUpThreads) void img_upload_pair_kernel(const uint4
   }
 }
 
-// a submitted Frame constructor owns the handle (stream, staging slot, pyramid, feature buffers) until it has been waited for
-static inline bool handle_busy(const orbx_handle* h) {
-  return h->ingest_state.load(std::memory_order_acquire) != 0 || (h->pending && (h->pending->active || h->pending->finished));
-}
-
 // images[c] for c < n_img -> h->d_img (packed rows, image c at c * w * hgt)
 static int stage_images(orbx_handle* h, const uint8_t* const* images, int n_img, int w, int hgt, int stride) {
   const size_t per = (size_t)w * hgt, total = per * n_img;
@@ -2619,473 +2660,26 @@ static int stage_images(orbx_handle* h, const uint8_t* const* images, int n_img,
   return ORBG_OK;
 }
 
-extern "C" int orbx_extract(orbx_handle* h, int cam, const uint8_t* img, int width, int height, int stride, int lap0,
-                            int lap1, orbx_keypoint* kps, uint8_t* desc, int cap, int* n, int* n_mono) {
-  if (!h || !n) return ORBG_BAD_ARG;
-  if (!img || width <= 0 || height <= 0) return ORBG_EMPTY;     // S/ORBextractor.cc:1072-1073
-  if (cam != 0 || stride < width) return ORBG_BAD_ARG;          // one camera per call goes through slot 0
-  if (handle_busy(h)) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  if ((rc = setup_geometry(h, width, height))) return rc;
-  if ((rc = stage_images(h, &img, 1, width, height, stride))) return rc;
-  const int lap[2][2] = {{lap0, lap1}, {0, 0}};
-  orbx_keypoint* ko[2] = {kps, nullptr};
-  uint8_t* dout[2] = {desc, nullptr};
-  const int caps[2] = {cap, 0};
-  int* no[2] = {n, nullptr};
-  int* nm[2] = {n_mono, nullptr};
-  return extract_core(h, 1, h->d_img.p, nullptr, width, height, width, lap, ko, dout, caps, no, nm);
-}
-
-static int extract_stereo_impl(orbx_handle* h, const uint8_t* d0, const uint8_t* d1, int width, int height, int stride,
-                               orbx_keypoint* kl, uint8_t* dl, int cl, int* nl, orbx_keypoint* kr, uint8_t* dr, int cr, int* nr) {
-  const int lap[2][2] = {{0, 0}, {0, 0}};      // vLapping = {0,0} for the rectified stereo Frame ctor (S/Frame.cc:92-95)
-  orbx_keypoint* ko[2] = {kl, kr};
-  uint8_t* dout[2] = {dl, dr};
-  const int caps[2] = {cl, cr};
-  int* no[2] = {nl, nr};
-  int* nm[2] = {nullptr, nullptr};
-  return extract_core(h, 3, d0, d1, width, height, stride, lap, ko, dout, caps, no, nm);
-}
-
-extern "C" int orbx_extract_stereo(orbx_handle* h, const uint8_t* img_left, const uint8_t* img_right, int width, int height,
-                                   int stride, orbx_keypoint* kps_left, uint8_t* desc_left, int cap_left, int* n_left,
-                                   orbx_keypoint* kps_right, uint8_t* desc_right, int cap_right, int* n_right) {
-  if (!h || h->cfg.n_cams != 2) return ORBG_BAD_ARG;
-  if (!img_left || !img_right || width <= 0 || height <= 0) return ORBG_EMPTY;
-  if (stride < width || handle_busy(h)) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  if ((rc = setup_geometry(h, width, height))) return rc;
-  const uint8_t* const both[2] = {img_left, img_right};
-  if ((rc = stage_images(h, both, 2, width, height, stride))) return rc;
-  return extract_stereo_impl(h, h->d_img.p, h->d_img.p + (size_t)width * height, width, height, width, kps_left, desc_left,
-                             cap_left, n_left, kps_right, desc_right, cap_right, n_right);
-}
-
-extern "C" int orbx_extract_stereo_dev(orbx_handle* h, const uint8_t* d_img_left, const uint8_t* d_img_right, int width,
-                                       int height, int stride, orbx_keypoint* kps_left, uint8_t* desc_left, int cap_left,
-                                       int* n_left, orbx_keypoint* kps_right, uint8_t* desc_right, int cap_right, int* n_right) {
-  if (!h || h->cfg.n_cams != 2) return ORBG_BAD_ARG;
-  if (!d_img_left || !d_img_right || width <= 0 || height <= 0) return ORBG_EMPTY;
-  if (stride < width) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  return extract_stereo_impl(h, d_img_left, d_img_right, width, height, stride, kps_left, desc_left, cap_left, n_left,
-                             kps_right, desc_right, cap_right, n_right);
-}
-
-// The fused constructors feed the extracted keypoints straight into the grid: mvKeysUn = mvKeys, i.e. mDistCoef[0] == 0
-// (S/Frame.cc:723-727).  The reference's bounds are the image rectangle exactly then (S/Frame.cc:775-783); anything else is a
-// distorted camera, which this entry point does not undistort: refused.
-static inline bool view_is_undistorted(const orbm_frame_view* v, int width, int height) {
-  return v->min_x == 0.0f && v->min_y == 0.0f && v->max_x == (float)width && v->max_y == (float)height;
-}
-
-static int frame_stereo_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                             const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b,
-                             orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left,
-                             int* n_left, int* n_right) {
-  if (!h || h->cfg.n_cams != 2 || !n_left) return ORBG_BAD_ARG;
-  if (frame && !view) return ORBG_BAD_ARG;
-  if (frame && width > 0 && height > 0 && !view_is_undistorted(view, width, height)) return ORBG_BAD_ARG;
-  if (!img_left || !img_right || width <= 0 || height <= 0) return ORBG_EMPTY;
-  if (stride < width || handle_busy(h)) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  const uint8_t* d_img_left = img_left;
-  const uint8_t* d_img_right = img_right;
-  if (!on_device) {
-    if ((rc = setup_geometry(h, width, height))) return rc;
-    const uint8_t* const both[2] = {img_left, img_right};
-    if ((rc = stage_images(h, both, 2, width, height, stride))) return rc;
-    d_img_left = h->d_img.p;
-    d_img_right = h->d_img.p + (size_t)width * height;
-    stride = width;
-  }
-  PostOps post;
-  post.stereo = true; post.bf = bf; post.b = b; post.uright = uright; post.depth = depth; post.frame = frame; post.view = view;
-  const int lap[2][2] = {{0, 0}, {0, 0}};
-  orbx_keypoint* ko[2] = {kps_left, nullptr};
-  uint8_t* dout[2] = {desc_left, nullptr};
-  const int caps[2] = {cap_left, 0};
-  int* no[2] = {n_left, n_right};
-  int* nm[2] = {nullptr, nullptr};
-  return extract_core(h, 3, d_img_left, d_img_right, width, height, stride, lap, ko, dout, caps, no, nm, &post);
-}
-
-extern "C" int orbx_frame_stereo_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* d_img_left,
-                                     const uint8_t* d_img_right, int width, int height, int stride, float bf, float b,
-                                     orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left,
-                                     int* n_left, int* n_right) {
-  return frame_stereo_impl(h, frame, view, d_img_left, d_img_right, true, width, height, stride, bf, b, kps_left, desc_left, uright,
-                           depth, cap_left, n_left, n_right);
-}
-
-// Frame constructor split in two so that the caller can overlap it with work on other streams (tracking of the previous
-// frame): submit enqueues the whole chain and returns, wait completes it.
-// mono: the monocular constructor (img_right unused; dist = mDistCoef or NULL)
-static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                             const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono,
-                             const orbx_distortion* dist, const orbx_rgbd_image* rgbd);
-// rgbd: the RGB-D constructor (img_left / img_right / stride unused: the descriptor names the images; dist as for mono)
-static int frame_submit_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                             const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono = false,
-                             const orbx_distortion* dist = nullptr, const orbx_rgbd_image* rgbd = nullptr) {
-  const double t0 = host_now_us();
-  h->tl_queue = t0 - h->tl_t_handover;
-  const int rc = frame_submit_core(h, frame, view, img_left, img_right, on_device, width, height, stride, bf, b, mono, dist, rgbd);
-  h->tl_enqueue = host_now_us() - t0 - h->tl_pack_acc;
-  return rc;
-}
-// Frame::Frame(mono): ExtractORB(0, imGray, 0, 1000) (S/Frame.cc:289) -- camera 0 only, lapping area {0, 1000}
-static const int kMonoLap[2][2] = {{0, 1000}, {0, 0}};
-static inline bool dist_active(const orbx_distortion* d) { return d && d->k1 != 0.0f; }      // S/Frame.cc:723
-static void fill_mono_post(PostOps* post, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, orbx_keypoint* kps_un_out) {
-  post->stereo = false; post->mono = true; post->frame = frame; post->view = view; post->kps_un_out = kps_un_out;
-  post->undist = dist_active(dist) && frame != nullptr;
-  if (post->undist) post->dist = *dist;
-}
-static int rgbd_prepare(orbx_handle* h, const orbx_rgbd_image* im, bool on_device, int w, int hgt, float bf, const uint8_t** d_gray,
-                        int* gray_stride, orbg::RgbdDepthArgs* rd);
-static void fill_rgbd_post(PostOps* post, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, orbx_keypoint* kps_un_out,
-                           float* uright, float* depth, const orbg::RgbdDepthArgs& rd) {
-  post->stereo = false; post->mono = false; post->rgbd = true; post->frame = frame; post->view = view; post->kps_un_out = kps_un_out;
-  post->uright = uright; post->depth = depth; post->bf = rd.bf; post->rd = rd;
-  post->undist = dist_active(dist) && frame != nullptr;
-  if (post->undist) post->dist = *dist;
-}
-static int frame_submit_core(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                             const uint8_t* img_right, bool on_device, int width, int height, int stride, float bf, float b, bool mono,
-                             const orbx_distortion* dist, const orbx_rgbd_image* rgbd) {
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  if (!h->pending) h->pending = new ExtractPending();
-  ExtractPending& P = *h->pending;
-  if (P.active || P.finished) return ORBG_BAD_ARG;      // the previous submission has not been collected
-  const uint8_t* d_img_left = img_left;
-  const uint8_t* d_img_right = img_right;
-  orbg::RgbdDepthArgs rd{};
-  if (rgbd) {
-    if ((rc = rgbd_prepare(h, rgbd, on_device, width, height, bf, &d_img_left, &stride, &rd))) return rc;
-    d_img_right = nullptr;
-  } else if (!on_device) {
-    if ((rc = setup_geometry(h, width, height))) return rc;
-    const uint8_t* const both[2] = {img_left, img_right};
-    if ((rc = stage_images(h, both, mono ? 1 : 2, width, height, stride))) return rc;
-    d_img_left = h->d_img.p;
-    d_img_right = mono ? nullptr : h->d_img.p + (size_t)width * height;
-    stride = width;
-  }
-  PostOps post;
-  const bool one_cam = mono || rgbd != nullptr;
-  if (rgbd) fill_rgbd_post(&post, frame, view, dist, h->out_kps_un, h->out_uright, h->out_depth, rd);
-  else if (mono) fill_mono_post(&post, frame, view, dist, h->out_kps_un);
-  else {
-    post.stereo = true; post.bf = bf; post.b = b; post.frame = frame; post.view = view;
-    post.uright = h->out_uright; post.depth = h->out_depth;             // (orbx_set_frame_outputs: delivered by _wait)
-  }
-  const int lap_stereo[2][2] = {{0, 0}, {0, 0}};
-  orbx_keypoint* ko[2] = {h->out_kps, nullptr};
-  uint8_t* dout[2] = {h->out_desc, nullptr};
-  const int caps[2] = {h->out_cap, 0};
-  int* no[2] = {&P.n_res[0], &P.n_res[1]};
-  int* nm[2] = {nullptr, nullptr};
-  P.n_res[1] = 0;
-  rc = extract_core(h, one_cam ? 1u : 3u, d_img_left, d_img_right, width, height, stride, mono ? kMonoLap : lap_stereo, ko, dout, caps, no, nm, &post,
-                    false, true);
-  if (rc) { P.active = false; return rc; }
-  if (!P.active) P.finished = true;                      // host quad-tree path: it ran to completion inside the call
-  return ORBG_OK;
-}
-
-// Host arrays for the features of the two-halves constructor (include/orbgpu.h): taken by every later _submit of this handle.
-extern "C" int orbx_set_frame_outputs(orbx_handle* h, orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left) {
-  if (!h || cap_left < 0 || ((kps_left || desc_left || uright || depth) && cap_left == 0)) return ORBG_BAD_ARG;
-  if (handle_busy(h)) return ORBG_BAD_ARG;
-  h->out_kps = kps_left; h->out_desc = desc_left; h->out_uright = uright; h->out_depth = depth; h->out_cap = cap_left;
-  if (cap_left == 0) h->out_kps_un = nullptr;               // (the mvKeysUn array shares the capacity: off together)
-  return ORBG_OK;
-}
-
-extern "C" int orbx_frame_stereo_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* d_img_left,
-                                            const uint8_t* d_img_right, int width, int height, int stride, float bf, float b) {
-  if (!h || h->cfg.n_cams != 2) return ORBG_BAD_ARG;
-  if (frame && !view) return ORBG_BAD_ARG;
-  if (!d_img_left || !d_img_right || width <= 0 || height <= 0) return ORBG_EMPTY;
-  if (stride < width) return ORBG_BAD_ARG;
-  if (frame && !view_is_undistorted(view, width, height)) return ORBG_BAD_ARG;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;
-  h->tl_begin();
-  return frame_submit_impl(h, frame, view, d_img_left, d_img_right, true, width, height, stride, bf, b);
-}
-
-// ---- the ingest thread: ONE per process, shared by every extractor handle.  A camera driver / image-grabber thread of a
-// deployment plays this role itself (it calls orbx_frame_stereo_submit with flags 0 when a stereo pair arrives); for callers
-// that hand images over on their tracking thread, ORBX_SUBMIT_ASYNC moves the staging copy (~0.6 MB at 640 x 480) and the
-// launches of the constructor chain off that thread.  The thread is created by the first asynchronous submission and
-// inherits that caller's CPU affinity.
-namespace {
-struct IngestJob {
-  orbx_handle* h; orbm_frame* frame; orbm_frame_view view; bool has_view; const uint8_t* L; const uint8_t* R; int w, hgt, stride; float bf, b;
-  bool mono = false, has_dist = false; orbx_distortion dist{};
-  bool rgbd = false; orbx_rgbd_image im{};
+// Where the caller's images live.  It travels beside the job and is done with once stage_inputs has run.
+struct ImageSource {
+  bool on_device = false;
+  const uint8_t* img[2] = {nullptr, nullptr};        // gray images, one per camera
+  int stride = 0;
+  const orbx_rgbd_image* rgbd = nullptr;             // an RGB-D frame's descriptor instead (colour or gray + depth)
 };
-struct IngestWorker {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<IngestJob> q;
-  std::atomic<int> queued{0};
-  bool quit = false;
-  std::thread th;
-  static bool spin_ok() { return orbg::poll_allowed(); }
-  void run() {
-    orbg::set_thread_role(orbg::kRoleIngest);
-    for (;;) {
-      // the next pair usually arrives within a frame time: spin for a while, then sleep
-      bool have = false;
-      if (spin_ok()) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; spins++) {
-          if (queued.load(std::memory_order_acquire) > 0) { have = true; break; }
-#if defined(__x86_64__)
-          __builtin_ia32_pause();
-#endif
-          if ((spins & 0xFF) == 0xFF && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) break;
-        }
-      }
-      IngestJob job;
-      {
-        std::unique_lock<std::mutex> lk(mu);
-        if (!have) cv.wait(lk, [this]() { return quit || !q.empty(); });
-        if (quit && q.empty()) return;
-        if (q.empty()) continue;
-        job = q.front();
-        q.erase(q.begin());
-        queued.fetch_sub(1, std::memory_order_acq_rel);
-      }
-      job.h->ingest_rc = frame_submit_impl(job.h, job.frame, job.has_view ? &job.view : nullptr, job.L, job.R, false, job.w, job.hgt,
-                                           job.stride, job.bf, job.b, job.mono, job.has_dist ? &job.dist : nullptr, job.rgbd ? &job.im : nullptr);
-      job.h->ingest_state.store(2, std::memory_order_release);
-    }
-  }
-  void push(const IngestJob& j) {
-    {
-      std::unique_lock<std::mutex> lk(mu);
-      if (!th.joinable()) th = std::thread([this]() { run(); });
-      q.push_back(j);
-      queued.fetch_add(1, std::memory_order_acq_rel);
-    }
-    cv.notify_one();
-  }
-  ~IngestWorker() {
-    { std::unique_lock<std::mutex> lk(mu); quit = true; }
-    cv.notify_all();
-    if (th.joinable()) th.join();
-  }
-};
-IngestWorker& ingest_worker() { static IngestWorker w; return w; }
-}  // namespace
 
-extern "C" int orbx_frame_stereo_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                                        const uint8_t* img_right, int width, int height, int stride, float bf, float b, int flags) {
-  if (!h || h->cfg.n_cams != 2) return ORBG_BAD_ARG;
-  if (frame && !view) return ORBG_BAD_ARG;
-  if (!img_left || !img_right || width <= 0 || height <= 0) return ORBG_EMPTY;
-  if (stride < width || width > h->cfg.max_width || height > h->cfg.max_height) return ORBG_BAD_ARG;
-  if (frame && !view_is_undistorted(view, width, height)) return ORBG_BAD_ARG;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;       // one submission per handle at a time
-  if (h->pending && (h->pending->active || h->pending->finished)) return ORBG_BAD_ARG;
-  h->tl_begin();
-  if (!(flags & ORBX_SUBMIT_ASYNC)) return frame_submit_impl(h, frame, view, img_left, img_right, false, width, height, stride, bf, b);
-  int rc = select_device(h->device);                    // a missing device is reported by the call, not by the wait
-  if (rc) return rc;
-  IngestJob j;
-  j.h = h; j.frame = frame; j.has_view = view != nullptr; j.L = img_left; j.R = img_right; j.w = width; j.hgt = height; j.stride = stride;
-  j.bf = bf; j.b = b;
-  if (view) j.view = *view;
-  h->ingest_state.store(1, std::memory_order_release);
-  ingest_worker().push(j);
-  return ORBG_OK;
-}
-
-extern "C" int orbx_frame_stereo_dev_wait(orbx_handle* h, int* n_left, int* n_right) {
-  if (!h) return ORBG_BAD_ARG;
-  int rc;
-  const double t_wait0 = host_now_us();
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) {
-    // handed to the ingest thread: wait until it has enqueued the chain (it is usually done long before)
-    for (unsigned spins = 0; h->ingest_state.load(std::memory_order_acquire) != 2; spins++) {
-#if defined(__x86_64__)
-      __builtin_ia32_pause();
-#endif
-      if (!IngestWorker::spin_ok() || (spins & 0xFFFF) == 0xFFFF) std::this_thread::yield();
-    }
-    rc = h->ingest_rc;
-    h->ingest_state.store(0, std::memory_order_release);
-    if (rc) return rc;
-  }
-  if (!h->pending || !(h->pending->active || h->pending->finished)) return ORBG_BAD_ARG;
-  if ((rc = select_device(h->device))) return rc;
-  ExtractPending& P = *h->pending;
-  if (P.active) {
-    P.active = false;
-    rc = extract_finish_gpu(h, P);
-  }
-  P.finished = false;
-  if (rc) return rc;
-  h->tl_commit(host_now_us() - t_wait0);
-  if (n_left) *n_left = P.n_res[0];
-  if (n_right) *n_right = P.n_res[1];
-  return ORBG_OK;
-}
-
-// Host-side timeline of the handle's last submissions, oldest first: out[i * 5 + f], f = queue / pack / enqueue / wait / latency in
-// microseconds (see orbx_handle::tl); *n = entries written (<= cap, <= 512).  reset != 0 forgets them afterwards.
-extern "C" int orbx_get_ctor_timeline(orbx_handle* h, float* out, int cap, int* n, int reset) {
-  if (!h || !n || cap < 0 || (cap > 0 && !out)) return ORBG_BAD_ARG;
-  const unsigned long long have = std::min<unsigned long long>(h->tl_n, orbx_handle::kTlCap);
-  const int take = (int)std::min<unsigned long long>(have, (unsigned long long)cap);
-  for (int i = 0; i < take; i++) {
-    const float* e = h->tl[(h->tl_n - take + i) % orbx_handle::kTlCap];
-    for (int f = 0; f < orbx_handle::kTlFields; f++) out[i * orbx_handle::kTlFields + f] = e[f];
-  }
-  *n = take;
-  if (reset) h->tl_n = 0;
-  return ORBG_OK;
-}
-extern "C" int orbx_set_stream(orbx_handle* h, void* hip_stream) {
-  if (!h) return ORBG_BAD_ARG;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0 || (h->pending && (h->pending->active || h->pending->finished))) return ORBG_BAD_ARG;
-  int rc = select_device(h->device);
-  if (rc) return rc;
-  return orbg::swap_stream(&h->stream, &h->ext_stream, hip_stream, "ex");
-}
-
-extern "C" int orbx_frame_stereo_wait(orbx_handle* h, int* n_left, int* n_right) { return orbx_frame_stereo_dev_wait(h, n_left, n_right); }
-
-extern "C" int orbx_frame_stereo(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
-                                 const uint8_t* img_right, int width, int height, int stride, float bf, float b,
-                                 orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left,
-                                 int* n_left, int* n_right) {
-  if (h) h->tl_begin();
-  const int rc = frame_stereo_impl(h, frame, view, img_left, img_right, false, width, height, stride, bf, b, kps_left, desc_left, uright,
-                                   depth, cap_left, n_left, n_right);
-  if (h && rc == ORBG_OK) h->tl_commit(0.0);            // synchronous: queue / enqueue / wait are not separated, latency = the call
-  return rc;
-}
-
-// ---- the monocular Frame constructor (include/orbgpu.h): camera 0, lapping area {0, 1000}, undistortion + grid as the chain's tail
-static int mono_args_ok(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
-                        int width, int height, int stride) {
-  if (!h) return ORBG_BAD_ARG;
-  if (frame && !view) return ORBG_BAD_ARG;
-  if (dist_active(dist) && !frame) return ORBG_BAD_ARG;          // mvKeysUn of a distorted camera exists as the frame's features
-  if (!img || width <= 0 || height <= 0) return ORBG_EMPTY;      // (the reference returns before it touches anything: S/Frame.cc:297-298)
-  if (stride < width || width > h->cfg.max_width || height > h->cfg.max_height) return ORBG_BAD_ARG;
-  // without distortion the reference's bounds are the image rectangle (S/Frame.cc:776-782); with it they are the undistorted corners
-  if (frame && !dist_active(dist) && !view_is_undistorted(view, width, height)) return ORBG_BAD_ARG;
-  if (frame && dist_active(dist) && !(view->fx > 0.0f && view->fy > 0.0f && view->max_x > view->min_x && view->max_y > view->min_y)) return ORBG_BAD_ARG;
-  return ORBG_OK;
-}
-
-static int frame_mono_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
-                           bool on_device, int width, int height, int stride, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, int cap,
-                           int* n) {
-  if (!n) return ORBG_BAD_ARG;
-  int rc = mono_args_ok(h, frame, view, dist, img, width, height, stride);
-  if (rc) return rc;
-  if (handle_busy(h)) return ORBG_BAD_ARG;
-  if ((rc = select_device(h->device))) return rc;
-  const uint8_t* d_img = img;
-  if (!on_device) {
-    if ((rc = setup_geometry(h, width, height))) return rc;
-    if ((rc = stage_images(h, &img, 1, width, height, stride))) return rc;
-    d_img = h->d_img.p;
-    stride = width;
-  }
-  PostOps post;
-  fill_mono_post(&post, frame, view, dist, kps_un);
-  orbx_keypoint* ko[2] = {kps, nullptr};
-  uint8_t* dout[2] = {desc, nullptr};
-  const int caps[2] = {cap, 0};
-  int* no[2] = {n, nullptr};
-  int* nm[2] = {nullptr, nullptr};
-  return extract_core(h, 1, d_img, nullptr, width, height, stride, kMonoLap, ko, dout, caps, no, nm, &post);
-}
-
-extern "C" int orbx_frame_mono(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
-                               int width, int height, int stride, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, int cap, int* n) {
-  if (h) h->tl_begin();
-  const int rc = frame_mono_impl(h, frame, view, dist, img, false, width, height, stride, kps, kps_un, desc, cap, n);
-  if (h && rc == ORBG_OK) h->tl_commit(0.0);
-  return rc;
-}
-extern "C" int orbx_frame_mono_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* d_img,
-                                   int width, int height, int stride, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, int cap, int* n) {
-  return frame_mono_impl(h, frame, view, dist, d_img, true, width, height, stride, kps, kps_un, desc, cap, n);
-}
-
-extern "C" int orbx_frame_mono_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
-                                          const uint8_t* d_img, int width, int height, int stride) {
-  int rc = mono_args_ok(h, frame, view, dist, d_img, width, height, stride);
-  if (rc) return rc;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;
-  h->tl_begin();
-  return frame_submit_impl(h, frame, view, d_img, nullptr, true, width, height, stride, 0.f, 0.f, true, dist);
-}
-
-extern "C" int orbx_frame_mono_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
-                                      int width, int height, int stride, int flags) {
-  int rc = mono_args_ok(h, frame, view, dist, img, width, height, stride);
-  if (rc) return rc;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;       // one submission per handle at a time
-  if (h->pending && (h->pending->active || h->pending->finished)) return ORBG_BAD_ARG;
-  h->tl_begin();
-  if (!(flags & ORBX_SUBMIT_ASYNC)) return frame_submit_impl(h, frame, view, img, nullptr, false, width, height, stride, 0.f, 0.f, true, dist);
-  if ((rc = select_device(h->device))) return rc;
-  IngestJob j;
-  j.h = h; j.frame = frame; j.has_view = view != nullptr; j.L = img; j.R = nullptr; j.w = width; j.hgt = height; j.stride = stride; j.bf = 0; j.b = 0;
-  if (view) j.view = *view;
-  j.mono = true; j.has_dist = dist != nullptr;
-  if (dist) j.dist = *dist;
-  h->ingest_state.store(1, std::memory_order_release);
-  ingest_worker().push(j);
-  return ORBG_OK;
-}
-
-extern "C" int orbx_frame_mono_wait(orbx_handle* h, int* n) { return orbx_frame_stereo_dev_wait(h, n, nullptr); }
-
-extern "C" int orbx_set_frame_outputs_un(orbx_handle* h, orbx_keypoint* kps_un) {
-  if (!h || (kps_un && h->out_cap == 0)) return ORBG_BAD_ARG;
-  if (handle_busy(h)) return ORBG_BAD_ARG;
-  h->out_kps_un = kps_un;
-  return ORBG_OK;
-}
-
-
-// ---- the RGB-D Frame constructor (include/orbgpu.h): camera 0, lapping area {0, 0}; colour -> gray in front of the pyramid, the depth
-// lookup between the undistortion and the grid (rgbd.hpp)
 static inline int depth_elem(int type) { return type == ORBX_DEPTH_U16 ? 2 : type == ORBX_DEPTH_F32 ? 4 : 0; }
-static int rgbd_args_ok(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
-                        bool on_device, int width, int height, float bf) {
-  if (!h || !im || im->struct_size < sizeof(orbx_rgbd_image)) return ORBG_BAD_ARG;
-  int rc = mono_args_ok(h, frame, view, dist, im->img, width, height, im->channels == 1 ? im->stride : width);
-  if (rc) return rc;
-  const int es = depth_elem(im->depth_type);
-  if (!im->depth || !es || !(im->channels == 1 || im->channels == 3 || im->channels == 4) || !(bf > 0.0f)) return ORBG_BAD_ARG;
-  if ((long long)im->stride < (long long)width * im->channels || (long long)im->depth_stride < (long long)width * es) return ORBG_BAD_ARG;
-  // a depth image resident in HBM is read in place: its values must be aligned (a host image is repacked by the staging copy)
-  if (on_device && (((uintptr_t)im->depth | (uintptr_t)im->depth_stride) & (uintptr_t)(es - 1))) return ORBG_BAD_ARG;
-  return ORBG_OK;
-}
-
 // The images of an RGB-D frame on their way to the chain: gray as the other constructors stage it; colour through the same pinned slot
 // (or read in place when resident) and ONE conversion kernel that writes the gray image the pyramid reads; the depth image through a
 // slot and a device copy of its own (allocated by the first RGB-D frame of the handle), moved by one copy kernel.
-static int rgbd_prepare(orbx_handle* h, const orbx_rgbd_image* im, bool on_device, int w, int hgt, float bf, const uint8_t** d_gray,
-                        int* gray_stride, orbg::RgbdDepthArgs* rd) {
+static int rgbd_prepare(orbx_handle* h, const ImageSource& src, FrameJob& j) {
+  const orbx_rgbd_image* im = src.rgbd;
+  const bool on_device = src.on_device;
+  const int w = j.w, hgt = j.hgt;
+  const float bf = j.bf;
+  const uint8_t** d_gray = &j.d_img[0];
+  int* gray_stride = &j.stride;
+  orbg::RgbdDepthArgs* rd = &j.rd;
   int rc;
   if ((rc = setup_geometry(h, w, hgt))) return rc;
   const int ch = im->channels;
@@ -3137,74 +2731,417 @@ static int rgbd_prepare(orbx_handle* h, const orbx_rgbd_image* im, bool on_devic
   }
   return ORBG_OK;
 }
-
-static int frame_rgbd_impl(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
-                           bool on_device, int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc,
-                           float* uright, float* depth, int cap, int* n) {
-  if (!n) return ORBG_BAD_ARG;
-  int rc = rgbd_args_ok(h, frame, view, dist, im, on_device, width, height, bf);
+// Stage: the only place that sizes the pyramid for the call and brings the caller's images to the device.  Afterwards the job holds
+// device addresses and their stride, whatever the source was.
+static int stage_inputs(orbx_handle* h, const ImageSource& src, FrameJob& j) {
+  if (src.rgbd) return rgbd_prepare(h, src, j);
+  int rc = setup_geometry(h, j.w, j.hgt);
   if (rc) return rc;
-  if (handle_busy(h)) return ORBG_BAD_ARG;
-  if ((rc = select_device(h->device))) return rc;
-  const uint8_t* d_gray = nullptr;
-  int stride = 0;
-  orbg::RgbdDepthArgs rd;
-  if ((rc = rgbd_prepare(h, im, on_device, width, height, bf, &d_gray, &stride, &rd))) return rc;
-  PostOps post;
-  fill_rgbd_post(&post, frame, view, dist, kps_un, uright, depth, rd);
-  const int lap[2][2] = {{0, 0}, {0, 0}};          // ExtractORB(0, imGray, 0, 0), S/Frame.cc:198: the stereo constructor's order
-  orbx_keypoint* ko[2] = {kps, nullptr};
-  uint8_t* dout[2] = {desc, nullptr};
-  const int caps[2] = {cap, 0};
-  int* no[2] = {n, nullptr};
-  int* nm[2] = {nullptr, nullptr};
-  return extract_core(h, 1, d_gray, nullptr, width, height, stride, lap, ko, dout, caps, no, nm, &post);
+  if (src.on_device) { j.d_img[0] = src.img[0]; j.d_img[1] = src.img[1]; j.stride = src.stride; return ORBG_OK; }
+  if ((rc = stage_images(h, src.img, j.ncams, j.w, j.hgt, src.stride))) return rc;
+  j.d_img[0] = h->d_img.p;
+  j.d_img[1] = j.ncams == 2 ? h->d_img.p + (size_t)j.w * j.hgt : nullptr;
+  j.stride = j.w;
+  return ORBG_OK;
 }
 
+// ---- refusals.  A call is refused before it touches the handle (its timeline scratch included).  The four routes into a constructor
+// do not answer alike everywhere; where they differ the validators say so by route.
+enum Route { kSync, kDev, kSubmit, kDevSubmit };
+static inline bool returns_counts(Route r) { return r == kSync || r == kDev; }      // the call itself delivers n: it must be given
+// An image larger than the handle was created for (cfg.max_width x max_height): refused [tail][route], otherwise the geometry is rebuilt
+static const bool kRefuseOversize[4][4] = {
+    /* kTailNone   */ {false, false, false, false},
+    /* kTailStereo */ {false, false, true, false},
+    /* kTailMono   */ {true, true, true, true},
+    /* kTailRgbd   */ {true, true, true, true}};
+static inline bool oversize_refused(const orbx_handle* h, const FrameJob& j, Route r) {
+  return kRefuseOversize[j.tail][r] && (j.w > h->cfg.max_width || j.hgt > h->cfg.max_height);
+}
+// The fused constructors feed the extracted keypoints straight into the grid: mvKeysUn = mvKeys, i.e. mDistCoef[0] == 0
+// (S/Frame.cc:723-727).  The reference's bounds are the image rectangle exactly then (S/Frame.cc:775-783); anything else is a
+// distorted camera, which the stereo constructor does not undistort: refused.
+static inline bool view_is_undistorted(const orbm_frame_view* v, int width, int height) {
+  return v->min_x == 0.0f && v->min_y == 0.0f && v->max_x == (float)width && v->max_y == (float)height;
+}
+static inline bool dist_active(const orbx_distortion* d) { return d && d->k1 != 0.0f; }      // S/Frame.cc:723
+
+// orbx_extract_stereo* (tail none: counts may be NULL) and the stereo constructor
+static int stereo_args_ok(const orbx_handle* h, const ImageSource& src, const FrameJob& j, Route r) {
+  if (!h || h->cfg.n_cams != 2) return ORBG_BAD_ARG;
+  if (j.tail == kTailStereo && returns_counts(r) && !j.out[0].n) return ORBG_BAD_ARG;
+  if (j.frame && !j.has_view) return ORBG_BAD_ARG;
+  if (!src.img[0] || !src.img[1] || j.w <= 0 || j.hgt <= 0) return ORBG_EMPTY;
+  if (src.stride < j.w || oversize_refused(h, j, r)) return ORBG_BAD_ARG;
+  if (j.frame && !view_is_undistorted(&j.view, j.w, j.hgt)) return ORBG_BAD_ARG;
+  return ORBG_OK;
+}
+// the monocular constructor; img / stride: the image the pyramid is built of
+static int mono_args_ok(const orbx_handle* h, const FrameJob& j, Route r, const uint8_t* img, int stride) {
+  if (!h || (returns_counts(r) && !j.out[0].n)) return ORBG_BAD_ARG;
+  if (j.frame && !j.has_view) return ORBG_BAD_ARG;
+  if (j.undist && !j.frame) return ORBG_BAD_ARG;                 // mvKeysUn of a distorted camera exists as the frame's features
+  if (!img || j.w <= 0 || j.hgt <= 0) return ORBG_EMPTY;         // (the reference returns before it touches anything: S/Frame.cc:297-298)
+  if (stride < j.w || oversize_refused(h, j, r)) return ORBG_BAD_ARG;
+  // without distortion the reference's bounds are the image rectangle (S/Frame.cc:776-782); with it they are the undistorted corners
+  const orbm_frame_view& v = j.view;
+  if (j.frame && !j.undist && !view_is_undistorted(&v, j.w, j.hgt)) return ORBG_BAD_ARG;
+  if (j.frame && j.undist && !(v.fx > 0.0f && v.fy > 0.0f && v.max_x > v.min_x && v.max_y > v.min_y)) return ORBG_BAD_ARG;
+  return ORBG_OK;
+}
+// the RGB-D constructor: the monocular rules for its image, then its own
+static int rgbd_args_ok(const orbx_handle* h, const ImageSource& src, const FrameJob& j, Route r) {
+  const orbx_rgbd_image* im = src.rgbd;
+  if (!h || !im || im->struct_size < sizeof(orbx_rgbd_image)) return ORBG_BAD_ARG;
+  int rc = mono_args_ok(h, j, r, im->img, im->channels == 1 ? im->stride : j.w);
+  if (rc) return rc;
+  const int es = depth_elem(im->depth_type);
+  if (!im->depth || !es || !(im->channels == 1 || im->channels == 3 || im->channels == 4) || !(j.bf > 0.0f)) return ORBG_BAD_ARG;
+  if ((long long)im->stride < (long long)j.w * im->channels || (long long)im->depth_stride < (long long)j.w * es) return ORBG_BAD_ARG;
+  // a depth image resident in HBM is read in place: its values must be aligned (a host image is repacked by the staging copy)
+  if (src.on_device && (((uintptr_t)im->depth | (uintptr_t)im->depth_stride) & (uintptr_t)(es - 1))) return ORBG_BAD_ARG;
+  return ORBG_OK;
+}
+
+// ---- the two drivers
+// The whole call on the calling thread.  The host-image constructors record a timeline row (queue / enqueue / wait are not separated:
+// latency = the call).
+static int run_sync(orbx_handle* h, const ImageSource& src, FrameJob& j) {
+  if (handle_busy(h)) return ORBG_BAD_ARG;
+  const bool timed = j.tail != kTailNone && !src.on_device;
+  if (timed) h->tl_begin();
+  int rc = select_device(h->device);
+  if (rc) return rc;
+  if ((rc = stage_inputs(h, src, j)) || (rc = launch(h, j, false))) return rc;
+  rc = j.on_gpu ? finish_gpu(h, j) : finish_host(h, j);
+  if (timed && rc == ORBG_OK) h->tl_commit(0.0);
+  return rc;
+}
+
+// Frame constructor split in two so that the caller can overlap it with work on other streams (tracking of the previous
+// frame): submit enqueues the whole chain and returns, orbx_frame_stereo_dev_wait completes it.
+// The first half on the thread that runs it (the caller or the ingest thread): the job moves into the handle, the outputs are the
+// arrays of orbx_set_frame_outputs(_un), delivered by the wait.
+static int submit_now(orbx_handle* h, const ImageSource& src, const FrameJob& job) {
+  const double t0 = host_now_us();
+  h->tl_queue = t0 - h->tl_t_handover;
+  FrameJob& P = h->pending;
+  P = job;
+  P.out[0] = CamOut{h->out_kps, h->out_desc, h->out_cap, &P.n_res[0], nullptr};
+  P.out[1].n = &P.n_res[1];
+  if (P.tail != kTailStereo) P.kps_un_out = h->out_kps_un;
+  if (P.tail != kTailMono) { P.uright = h->out_uright; P.depth = h->out_depth; }
+  int rc = select_device(h->device);
+  if (!rc && !(rc = stage_inputs(h, src, P)) && !(rc = launch(h, P, false))) {
+    if (P.on_gpu) P.active = true;
+    else P.finished = (rc = finish_host(h, P)) == ORBG_OK;      // host quad-tree path: it runs to completion inside the call
+  }
+  h->tl_enqueue = host_now_us() - t0 - h->tl_pack_acc;
+  return rc;
+}
+
+// ---- the ingest thread: ONE per process, shared by every extractor handle.  A camera driver / image-grabber thread of a
+// deployment plays this role itself (it calls orbx_frame_stereo_submit with flags 0 when a stereo pair arrives); for callers
+// that hand images over on their tracking thread, ORBX_SUBMIT_ASYNC moves the staging copy (~0.6 MB at 640 x 480) and the
+// launches of the constructor chain off that thread.  The thread is created by the first asynchronous submission and
+// inherits that caller's CPU affinity.
+namespace {
+struct IngestJob {
+  orbx_handle* h; ImageSource src; FrameJob job;
+  orbx_rgbd_image im;            // (the descriptor is copied; the images it names must stay valid until _wait)
+};
+struct IngestWorker {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<IngestJob> q;
+  std::atomic<int> queued{0};
+  bool quit = false;
+  std::thread th;
+  static bool spin_ok() { return orbg::poll_allowed(); }
+  void run() {
+    orbg::set_thread_role(orbg::kRoleIngest);
+    for (;;) {
+      // the next pair usually arrives within a frame time: spin for a while, then sleep
+      bool have = false;
+      if (spin_ok()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (unsigned spins = 0;; spins++) {
+          if (queued.load(std::memory_order_acquire) > 0) { have = true; break; }
+#if defined(__x86_64__)
+          __builtin_ia32_pause();
+#endif
+          if ((spins & 0xFF) == 0xFF && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) break;
+        }
+      }
+      IngestJob job;
+      {
+        std::unique_lock<std::mutex> lk(mu);
+        if (!have) cv.wait(lk, [this]() { return quit || !q.empty(); });
+        if (quit && q.empty()) return;
+        if (q.empty()) continue;
+        job = q.front();
+        q.erase(q.begin());
+        queued.fetch_sub(1, std::memory_order_acq_rel);
+      }
+      if (job.src.rgbd) job.src.rgbd = &job.im;
+      job.h->ingest_rc = submit_now(job.h, job.src, job.job);
+      job.h->ingest_state.store(2, std::memory_order_release);
+    }
+  }
+  void push(const IngestJob& j) {
+    {
+      std::unique_lock<std::mutex> lk(mu);
+      if (!th.joinable()) th = std::thread([this]() { run(); });
+      q.push_back(j);
+      queued.fetch_add(1, std::memory_order_acq_rel);
+    }
+    cv.notify_one();
+  }
+  ~IngestWorker() {
+    { std::unique_lock<std::mutex> lk(mu); quit = true; }
+    cv.notify_all();
+    if (th.joinable()) th.join();
+  }
+};
+IngestWorker& ingest_worker() { static IngestWorker w; return w; }
+}  // namespace
+static int submit(orbx_handle* h, const ImageSource& src, const FrameJob& job, int flags) {
+  if (handle_busy(h)) return ORBG_BAD_ARG;              // one submission per handle at a time
+  h->tl_begin();
+  if (!(flags & ORBX_SUBMIT_ASYNC)) return submit_now(h, src, job);
+  int rc = select_device(h->device);                    // a missing device is reported by the call, not by the wait
+  if (rc) return rc;
+  IngestJob ij{h, src, job, src.rgbd ? *src.rgbd : orbx_rgbd_image{}};
+  h->ingest_state.store(1, std::memory_order_release);
+  ingest_worker().push(ij);
+  return ORBG_OK;
+}
+
+// The second half of every submission (orbx_frame_*_wait are this function).
+extern "C" int orbx_frame_stereo_dev_wait(orbx_handle* h, int* n_left, int* n_right) {
+  if (!h) return ORBG_BAD_ARG;
+  int rc;
+  const double t_wait0 = host_now_us();
+  if (h->ingest_state.load(std::memory_order_acquire) != 0) {
+    // handed to the ingest thread: wait until it has enqueued the chain (it is usually done long before)
+    for (unsigned spins = 0; h->ingest_state.load(std::memory_order_acquire) != 2; spins++) {
+#if defined(__x86_64__)
+      __builtin_ia32_pause();
+#endif
+      if (!IngestWorker::spin_ok() || (spins & 0xFFFF) == 0xFFFF) std::this_thread::yield();
+    }
+    rc = h->ingest_rc;
+    h->ingest_state.store(0, std::memory_order_release);
+    if (rc) return rc;
+  }
+  if (!handle_busy(h)) return ORBG_BAD_ARG;
+  if ((rc = select_device(h->device))) return rc;
+  FrameJob& P = h->pending;
+  if (P.active) {
+    P.active = false;
+    rc = finish_gpu(h, P);
+  }
+  P.finished = false;
+  if (rc) return rc;
+  h->tl_commit(host_now_us() - t_wait0);
+  if (n_left) *n_left = P.n_res[0];
+  if (n_right) *n_right = P.n_res[1];
+  return ORBG_OK;
+}
+extern "C" int orbx_frame_stereo_wait(orbx_handle* h, int* n_left, int* n_right) { return orbx_frame_stereo_dev_wait(h, n_left, n_right); }
+extern "C" int orbx_frame_mono_wait(orbx_handle* h, int* n) { return orbx_frame_stereo_dev_wait(h, n, nullptr); }
+extern "C" int orbx_frame_rgbd_wait(orbx_handle* h, int* n) { return orbx_frame_stereo_dev_wait(h, n, nullptr); }
+
+// ---- the entry points: fill a job and a source from the arguments, validate, drive
+extern "C" int orbx_extract(orbx_handle* h, int cam, const uint8_t* img, int width, int height, int stride, int lap0,
+                            int lap1, orbx_keypoint* kps, uint8_t* desc, int cap, int* n, int* n_mono) {
+  if (!h || !n) return ORBG_BAD_ARG;
+  if (!img || width <= 0 || height <= 0) return ORBG_EMPTY;     // S/ORBextractor.cc:1072-1073
+  if (cam != 0 || stride < width) return ORBG_BAD_ARG;          // one camera per call goes through slot 0
+  FrameJob job;
+  job.w = width; job.hgt = height; job.lap[0][0] = lap0; job.lap[0][1] = lap1;
+  job.out[0] = CamOut{kps, desc, cap, n, n_mono};
+  return run_sync(h, ImageSource{false, {img, nullptr}, stride}, job);
+}
+
+// both synchronous stereo forms, with and without the constructor's tail
+static int stereo_sync(orbx_handle* h, const ImageSource& src, FrameJob& job) {
+  int rc = stereo_args_ok(h, src, job, src.on_device ? kDev : kSync);
+  return rc ? rc : run_sync(h, src, job);
+}
+extern "C" int orbx_extract_stereo(orbx_handle* h, const uint8_t* img_left, const uint8_t* img_right, int width, int height,
+                                   int stride, orbx_keypoint* kps_left, uint8_t* desc_left, int cap_left, int* n_left,
+                                   orbx_keypoint* kps_right, uint8_t* desc_right, int cap_right, int* n_right) {
+  FrameJob job;
+  job.ncams = 2; job.w = width; job.hgt = height;
+  job.out[0] = CamOut{kps_left, desc_left, cap_left, n_left, nullptr};
+  job.out[1] = CamOut{kps_right, desc_right, cap_right, n_right, nullptr};
+  return stereo_sync(h, ImageSource{false, {img_left, img_right}, stride}, job);
+}
+extern "C" int orbx_extract_stereo_dev(orbx_handle* h, const uint8_t* d_img_left, const uint8_t* d_img_right, int width,
+                                       int height, int stride, orbx_keypoint* kps_left, uint8_t* desc_left, int cap_left,
+                                       int* n_left, orbx_keypoint* kps_right, uint8_t* desc_right, int cap_right, int* n_right) {
+  FrameJob job;
+  job.ncams = 2; job.w = width; job.hgt = height;
+  job.out[0] = CamOut{kps_left, desc_left, cap_left, n_left, nullptr};
+  job.out[1] = CamOut{kps_right, desc_right, cap_right, n_right, nullptr};
+  return stereo_sync(h, ImageSource{true, {d_img_left, d_img_right}, stride}, job);
+}
+
+// what the three constructors' jobs have in common
+static FrameJob frame_job(TailKind tail, int width, int height, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist) {
+  FrameJob job;
+  job.tail = tail; job.ncams = tail == kTailStereo ? 2 : 1; job.w = width; job.hgt = height; job.frame = frame;
+  if (tail == kTailMono) job.lap[0][1] = 1000;       // Frame::Frame(mono): ExtractORB(0, imGray, 0, 1000) (S/Frame.cc:289)
+  if (view) { job.view = *view; job.has_view = true; }
+  if (dist_active(dist)) { job.undist = true; job.dist = *dist; }
+  return job;
+}
+
+// ---- the stereo Frame constructor (include/orbgpu.h)
+extern "C" int orbx_frame_stereo(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
+                                 const uint8_t* img_right, int width, int height, int stride, float bf, float b,
+                                 orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left,
+                                 int* n_left, int* n_right) {
+  FrameJob job = frame_job(kTailStereo, width, height, frame, view, nullptr);
+  job.bf = bf; job.b = b; job.uright = uright; job.depth = depth;
+  job.out[0] = CamOut{kps_left, desc_left, cap_left, n_left, nullptr};
+  job.out[1].n = n_right;
+  return stereo_sync(h, ImageSource{false, {img_left, img_right}, stride}, job);
+}
+extern "C" int orbx_frame_stereo_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* d_img_left,
+                                     const uint8_t* d_img_right, int width, int height, int stride, float bf, float b,
+                                     orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left,
+                                     int* n_left, int* n_right) {
+  FrameJob job = frame_job(kTailStereo, width, height, frame, view, nullptr);
+  job.bf = bf; job.b = b; job.uright = uright; job.depth = depth;
+  job.out[0] = CamOut{kps_left, desc_left, cap_left, n_left, nullptr};
+  job.out[1].n = n_right;
+  return stereo_sync(h, ImageSource{true, {d_img_left, d_img_right}, stride}, job);
+}
+extern "C" int orbx_frame_stereo_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* img_left,
+                                        const uint8_t* img_right, int width, int height, int stride, float bf, float b, int flags) {
+  FrameJob job = frame_job(kTailStereo, width, height, frame, view, nullptr);
+  job.bf = bf; job.b = b;
+  const ImageSource src{false, {img_left, img_right}, stride};
+  int rc = stereo_args_ok(h, src, job, kSubmit);
+  return rc ? rc : submit(h, src, job, flags);
+}
+extern "C" int orbx_frame_stereo_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const uint8_t* d_img_left,
+                                            const uint8_t* d_img_right, int width, int height, int stride, float bf, float b) {
+  FrameJob job = frame_job(kTailStereo, width, height, frame, view, nullptr);
+  job.bf = bf; job.b = b;
+  const ImageSource src{true, {d_img_left, d_img_right}, stride};
+  int rc = stereo_args_ok(h, src, job, kDevSubmit);
+  return rc ? rc : submit(h, src, job, 0);
+}
+
+// ---- the monocular Frame constructor (include/orbgpu.h): camera 0, lapping area {0, 1000}, undistortion + grid as the chain's tail
+static int frame_mono_sync(orbx_handle* h, const ImageSource& src, FrameJob& job) {
+  int rc = mono_args_ok(h, job, src.on_device ? kDev : kSync, src.img[0], src.stride);
+  return rc ? rc : run_sync(h, src, job);
+}
+extern "C" int orbx_frame_mono(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
+                               int width, int height, int stride, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, int cap, int* n) {
+  FrameJob job = frame_job(kTailMono, width, height, frame, view, dist);
+  job.out[0] = CamOut{kps, desc, cap, n, nullptr}; job.kps_un_out = kps_un;
+  return frame_mono_sync(h, ImageSource{false, {img, nullptr}, stride}, job);
+}
+extern "C" int orbx_frame_mono_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* d_img,
+                                   int width, int height, int stride, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, int cap, int* n) {
+  FrameJob job = frame_job(kTailMono, width, height, frame, view, dist);
+  job.out[0] = CamOut{kps, desc, cap, n, nullptr}; job.kps_un_out = kps_un;
+  return frame_mono_sync(h, ImageSource{true, {d_img, nullptr}, stride}, job);
+}
+extern "C" int orbx_frame_mono_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const uint8_t* img,
+                                      int width, int height, int stride, int flags) {
+  const FrameJob job = frame_job(kTailMono, width, height, frame, view, dist);
+  const ImageSource src{false, {img, nullptr}, stride};
+  int rc = mono_args_ok(h, job, kSubmit, img, stride);
+  return rc ? rc : submit(h, src, job, flags);
+}
+extern "C" int orbx_frame_mono_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                                          const uint8_t* d_img, int width, int height, int stride) {
+  const FrameJob job = frame_job(kTailMono, width, height, frame, view, dist);
+  const ImageSource src{true, {d_img, nullptr}, stride};
+  int rc = mono_args_ok(h, job, kDevSubmit, d_img, stride);
+  return rc ? rc : submit(h, src, job, 0);
+}
+
+// ---- the RGB-D Frame constructor (include/orbgpu.h): camera 0, lapping area {0, 0}; colour -> gray in front of the pyramid, the depth
+// lookup between the undistortion and the grid (rgbd.hpp)
+static int frame_rgbd_sync(orbx_handle* h, const ImageSource& src, FrameJob& job) {
+  int rc = rgbd_args_ok(h, src, job, src.on_device ? kDev : kSync);
+  return rc ? rc : run_sync(h, src, job);
+}
 extern "C" int orbx_frame_rgbd(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist, const orbx_rgbd_image* im,
                                int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un, uint8_t* desc, float* uright,
                                float* depth, int cap, int* n) {
-  if (h) h->tl_begin();
-  const int rc = frame_rgbd_impl(h, frame, view, dist, im, false, width, height, bf, kps, kps_un, desc, uright, depth, cap, n);
-  if (h && rc == ORBG_OK) h->tl_commit(0.0);
-  return rc;
+  FrameJob job = frame_job(kTailRgbd, width, height, frame, view, dist);
+  job.bf = bf; job.uright = uright; job.depth = depth; job.kps_un_out = kps_un;
+  job.out[0] = CamOut{kps, desc, cap, n, nullptr};
+  return frame_rgbd_sync(h, ImageSource{false, {nullptr, nullptr}, 0, im}, job);
 }
 extern "C" int orbx_frame_rgbd_dev(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
                                    const orbx_rgbd_image* im, int width, int height, float bf, orbx_keypoint* kps, orbx_keypoint* kps_un,
                                    uint8_t* desc, float* uright, float* depth, int cap, int* n) {
-  return frame_rgbd_impl(h, frame, view, dist, im, true, width, height, bf, kps, kps_un, desc, uright, depth, cap, n);
+  FrameJob job = frame_job(kTailRgbd, width, height, frame, view, dist);
+  job.bf = bf; job.uright = uright; job.depth = depth; job.kps_un_out = kps_un;
+  job.out[0] = CamOut{kps, desc, cap, n, nullptr};
+  return frame_rgbd_sync(h, ImageSource{true, {nullptr, nullptr}, 0, im}, job);
 }
-
-extern "C" int orbx_frame_rgbd_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
-                                          const orbx_rgbd_image* im, int width, int height, float bf) {
-  int rc = rgbd_args_ok(h, frame, view, dist, im, true, width, height, bf);
-  if (rc) return rc;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;
-  h->tl_begin();
-  return frame_submit_impl(h, frame, view, nullptr, nullptr, true, width, height, 0, bf, 0.f, false, dist, im);
-}
-
 extern "C" int orbx_frame_rgbd_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
                                       const orbx_rgbd_image* im, int width, int height, float bf, int flags) {
-  int rc = rgbd_args_ok(h, frame, view, dist, im, false, width, height, bf);
-  if (rc) return rc;
-  if (h->ingest_state.load(std::memory_order_acquire) != 0) return ORBG_BAD_ARG;       // one submission per handle at a time
-  if (h->pending && (h->pending->active || h->pending->finished)) return ORBG_BAD_ARG;
-  h->tl_begin();
-  if (!(flags & ORBX_SUBMIT_ASYNC)) return frame_submit_impl(h, frame, view, nullptr, nullptr, false, width, height, 0, bf, 0.f, false, dist, im);
-  if ((rc = select_device(h->device))) return rc;
-  IngestJob j;
-  j.h = h; j.frame = frame; j.has_view = view != nullptr; j.L = nullptr; j.R = nullptr; j.w = width; j.hgt = height; j.stride = 0; j.bf = bf; j.b = 0;
-  if (view) j.view = *view;
-  j.has_dist = dist != nullptr;
-  if (dist) j.dist = *dist;
-  j.rgbd = true; j.im = *im;                    // (the descriptor is copied; the images it names must stay valid until _wait)
-  h->ingest_state.store(1, std::memory_order_release);
-  ingest_worker().push(j);
+  FrameJob job = frame_job(kTailRgbd, width, height, frame, view, dist);
+  job.bf = bf;
+  const ImageSource src{false, {nullptr, nullptr}, 0, im};
+  int rc = rgbd_args_ok(h, src, job, kSubmit);
+  return rc ? rc : submit(h, src, job, flags);
+}
+extern "C" int orbx_frame_rgbd_dev_submit(orbx_handle* h, orbm_frame* frame, const orbm_frame_view* view, const orbx_distortion* dist,
+                                          const orbx_rgbd_image* im, int width, int height, float bf) {
+  FrameJob job = frame_job(kTailRgbd, width, height, frame, view, dist);
+  job.bf = bf;
+  const ImageSource src{true, {nullptr, nullptr}, 0, im};
+  int rc = rgbd_args_ok(h, src, job, kDevSubmit);
+  return rc ? rc : submit(h, src, job, 0);
+}
+
+// Host arrays for the features of the two-halves constructor (include/orbgpu.h): taken by every later _submit of this handle.
+extern "C" int orbx_set_frame_outputs(orbx_handle* h, orbx_keypoint* kps_left, uint8_t* desc_left, float* uright, float* depth, int cap_left) {
+  if (!h || cap_left < 0 || ((kps_left || desc_left || uright || depth) && cap_left == 0)) return ORBG_BAD_ARG;
+  if (handle_busy(h)) return ORBG_BAD_ARG;
+  h->out_kps = kps_left; h->out_desc = desc_left; h->out_uright = uright; h->out_depth = depth; h->out_cap = cap_left;
+  if (cap_left == 0) h->out_kps_un = nullptr;               // (the mvKeysUn array shares the capacity: off together)
+  return ORBG_OK;
+}
+extern "C" int orbx_set_frame_outputs_un(orbx_handle* h, orbx_keypoint* kps_un) {
+  if (!h || (kps_un && h->out_cap == 0)) return ORBG_BAD_ARG;
+  if (handle_busy(h)) return ORBG_BAD_ARG;
+  h->out_kps_un = kps_un;
   return ORBG_OK;
 }
 
-extern "C" int orbx_frame_rgbd_wait(orbx_handle* h, int* n) { return orbx_frame_stereo_dev_wait(h, n, nullptr); }
+// Host-side timeline of the handle's last submissions, oldest first: out[i * 5 + f], f = queue / pack / enqueue / wait / latency in
+// microseconds (see orbx_handle::tl); *n = entries written (<= cap, <= 512).  reset != 0 forgets them afterwards.
+extern "C" int orbx_get_ctor_timeline(orbx_handle* h, float* out, int cap, int* n, int reset) {
+  if (!h || !n || cap < 0 || (cap > 0 && !out)) return ORBG_BAD_ARG;
+  const unsigned long long have = std::min<unsigned long long>(h->tl_n, orbx_handle::kTlCap);
+  const int take = (int)std::min<unsigned long long>(have, (unsigned long long)cap);
+  for (int i = 0; i < take; i++) {
+    const float* e = h->tl[(h->tl_n - take + i) % orbx_handle::kTlCap];
+    for (int f = 0; f < orbx_handle::kTlFields; f++) out[i * orbx_handle::kTlFields + f] = e[f];
+  }
+  *n = take;
+  if (reset) h->tl_n = 0;
+  return ORBG_OK;
+}
+extern "C" int orbx_set_stream(orbx_handle* h, void* hip_stream) {
+  if (!h || handle_busy(h)) return ORBG_BAD_ARG;
+  int rc = select_device(h->device);
+  if (rc) return rc;
+  return orbg::swap_stream(&h->stream, &h->ext_stream, hip_stream, "ex");
+}
 
 // Frame::ComputeStereoFromRGBD on caller-given points (host arrays), with GrabImageRGBD's convertTo rule applied to the values read
 extern "C" int orbx_depth_at_points(int device, const float* xy, const float* xy_un, int n, const void* depth_img, int depth_type, int depth_stride,
@@ -3343,71 +3280,6 @@ extern "C" int orbx_get_candidates(orbx_handle* h, int cam, int level, int32_t* 
   *n = (int)cv.size();
   for (int i = 0; i < *n && i < cap; i++) { xys[3 * i] = cv[i].x; xys[3 * i + 1] = cv[i].y; xys[3 * i + 2] = cv[i].score; }
   return *n > cap ? ORBG_CAP_EXCEEDED : ORBG_OK;
-}
-
-// Second half of the GPU-path extraction: wait for the completion word, fall back to the host quad-trees if a level
-// overflowed the device lists, hand the counts (and the optional host copies) over.
-static int extract_finish_gpu(orbx_handle* h, ExtractPending& c) {
-  int rc;
-  hipStream_t st = h->stream;
-  if ((rc = h->sig.wait(st))) return rc;            // the overflow flag came with the keypoint counts
-  // (img_upload_pair_kernel gave up waiting for the host's pack: the images never reached the device)
-  if (h->up_seq && h->up_ready.h && h->up_ready.h[8] == h->up_seq) return ORBG_INTERNAL;
-  const PostOps* post = c.has_post ? &c.post : nullptr;
-  if (h->h_nkp.h[2]) {
-    // a level had more candidates / nodes than the LDS-resident quad-tree holds: redo this frame with the host trees
-    // (the only place that acts on the flag: the synchronous calls and orbx_frame_stereo_dev_wait both finish here)
-    h->host_redos++;
-    ORBG_HIP(hipMemsetAsync(h->d_overflow.p, 0, sizeof(int), st));
-    return extract_core(h, c.cams_mask, c.d_img0, c.d_img1, c.w, c.hgt, c.stride, c.lap, c.kps_out, c.desc_out, c.cap, c.n_out, c.n_mono_out,
-                        post, true, false);
-  }
-  const int ncams = c.ncams;
-  h->n_kp[0] = h->h_nkp.h[0];
-  h->n_kp[1] = ncams == 2 ? h->h_nkp.h[1] : 0;
-  int base = 0;
-  for (int cam = 0; cam < ncams; cam++) {
-    const int nk = h->n_kp[cam];
-    if (c.n_out[cam]) *c.n_out[cam] = nk;
-    if (c.n_mono_out[cam]) *c.n_mono_out[cam] = c.reverse[cam] ? 0 : nk;
-    if ((c.kps_out[cam] || c.desc_out[cam]) && nk > c.cap[cam]) return ORBG_CAP_EXCEEDED;
-    if (c.kps_out[cam]) memcpy(c.kps_out[cam], h->h_kps.h + base, (size_t)nk * sizeof(orbx_keypoint));
-    if (c.desc_out[cam]) memcpy(c.desc_out[cam], h->h_desc.h + (size_t)base * 32, (size_t)nk * 32);
-    base += nk;
-  }
-  if (post && post->frame) orbm_internal_set_n(post->frame, h->n_kp[0]);
-  if (post && post->kps_un_out) {
-    if (h->n_kp[0] > c.cap[0]) return ORBG_CAP_EXCEEDED;
-    memcpy(post->kps_un_out, (post->undist && post->frame) ? h->h_kps_un.h : h->h_kps.h, (size_t)h->n_kp[0] * sizeof(orbx_keypoint));
-  }
-  if (c.stereo_out && h->n_kp[0] > c.cap[0]) return ORBG_CAP_EXCEEDED;      // uright / depth hold cap_left entries like the other outputs
-  if (c.stereo_out) {
-    if (post->uright) memcpy(post->uright, h->h_stereo.h, (size_t)h->n_kp[0] * 4);
-    if (post->depth) memcpy(post->depth, h->h_stereo.h + h->n_kp[0], (size_t)h->n_kp[0] * 4);
-  }
-  float ms;
-  h->timings[2] = 0;
-  if (c.prof >= 1 && hipEventElapsedTime(&ms, h->ev[1], h->ev[7]) == hipSuccess) { h->timings[5] = ms; h->fast_ms_sum += ms; h->fast_ms_n++; }
-  return ORBG_OK;
-}
-
-// defer_finalize: do not launch the median rejection; hand its arguments back (it then runs next to the grid build)
-static int launch_stereo(orbx_handle* h, float bf, float b, hipStream_t st, bool device_counts, float* host_mirror,
-                         StereoFinalizeArgs* defer_finalize) {
-  const int nl = device_counts ? h->sel_bound : h->n_kp[0], nr = h->n_kp[1];
-  // the stereo key packs the right keypoint's index into 16 bits (dist << 16 | iR)
-  if (nl >= ORBG_MAX_FRAME_FEATURES || nr >= ORBG_MAX_FRAME_FEATURES || (device_counts && orbx_internal_kp_capacity(h) >= 2 * ORBG_MAX_FRAME_FEATURES))
-    return ORBG_CAP_EXCEEDED;
-  if (h->profile >= 2) ORBG_HIP(hipEventRecord(h->ev[5], st));
-  if (nl > 0) {
-    const int* dn = device_counts ? h->d_nkp.p : nullptr;
-    hipLaunchKernelGGL(stereo_match_kernel, dim3((nl + 3) / 4), dim3(256), 0, st, h->d_pyr.p, h->geom, h->d_kps.p, h->d_desc.p,
-                       nl, h->d_kps.p + nl, h->d_desc.p + (size_t)nl * 32, nr, bf, b, h->d_uright.p, h->d_depth.p, h->d_sad.p, dn);
-    if (defer_finalize) *defer_finalize = StereoFinalizeArgs{h->d_uright.p, h->d_depth.p, h->d_sad.p, nl, dn, host_mirror, nullptr};
-    else hipLaunchKernelGGL(stereo_finalize_kernel, dim3(1), dim3(256), 0, st, h->d_uright.p, h->d_depth.p, h->d_sad.p, nl, dn, host_mirror);
-  }
-  if (h->profile >= 2) ORBG_HIP(hipEventRecord(h->ev[6], st));
-  return ORBG_OK;
 }
 
 extern "C" int orbx_stereo_match(orbx_handle* h, float bf, float b, float* uright, float* depth) {

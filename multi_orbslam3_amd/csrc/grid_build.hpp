@@ -158,4 +158,23 @@ __device__ __forceinline__ void undistort_point(const UndistortArgs& a, float u,
   *yo = (float)(yy * ww);
 }
 
+struct RgbdDepthArgs;          // rgbd.hpp
+}  // namespace orbg
+struct StereoFinalizeArgs;     // stereo_finalize.hpp
+
+namespace orbg {
+// What a Frame constructor's chain hands to orbm_internal_attach (matcher.hip), which launches the grid build as its last kernel.
+// The blocks that are present select the kernel: rgbd -> rgbd_grid_kernel, un->on -> undistort_grid_kernel, fin ->
+// grid_build_finalize_kernel, none -> grid_build_kernel.
+struct AttachTail {
+  int n = -1;                                // keypoint count; < 0: it only exists on the device yet, at d_n
+  const int* d_n = nullptr;
+  hipStream_t stream = nullptr;              // the extractor's stream: the launch goes behind the descriptor / stereo kernels
+  volatile unsigned* done_flag = nullptr;    // completion word the grid build posts as the chain's last kernel (NULL: none)
+  unsigned done_seq = 0;
+  const StereoFinalizeArgs* fin = nullptr;   // median rejection of the stereo matches next to the grid build
+  const UndistortArgs* un = nullptr;         // mvKeysUn in front of the grid build
+  const RgbdDepthArgs* rgbd = nullptr;       // depth lookup between the two
+  bool mono = false;                         // monocular frame: no mvuRight
+};
 }  // namespace orbg

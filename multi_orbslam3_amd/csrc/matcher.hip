@@ -1203,40 +1203,39 @@ extern "C" int orbm_frame_from_extractor(orbm_frame* f, orbx_handle* h, const or
   return frame_build_grid(f);      // asynchronous on that stream; the searches run on the same stream
 }
 
-// Used by orbx_frame_stereo_dev (extractor.hip): alias the extractor's left features and launch the grid build on the
+// Used by the Frame constructors (extractor.hip, launch_chain): alias the extractor's left features and launch the grid build on the
 // EXTRACTOR's stream, behind the descriptor / stereo kernels; the caller synchronises that stream once.
 int orbx_internal_kp_capacity(orbx_handle* h);   // extractor.hip
-int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, int n, hipStream_t stream, const int* d_n,
-                         volatile unsigned* done_flag, unsigned done_seq, const StereoFinalizeArgs* fin, const orbg::UndistortArgs* un,
-                         bool mono, const orbg::RgbdDepthArgs* rgbd) {
+int orbm_internal_attach(orbm_frame* f, orbx_handle* h, const orbm_frame_view* v, const orbg::AttachTail& t) {
   if (!f || !h || !v) return ORBG_BAD_ARG;
   const orbx_keypoint* dk; const uint8_t* dd; const float* du; const float* dz; const orbx_keypoint* hk; int n0; hipStream_t xs;
   int rc = orbx_internal_left_features(h, &dk, &dd, &du, &dz, &hk, &n0, &xs);
   if (rc) return rc;
-  // n < 0: the count only exists on the device yet (d_n): the grid buffers are sized for the most keypoints the
+  // t.n < 0: the count only exists on the device yet (t.d_n): the grid buffers are sized for the most keypoints the
   // extractor's own buffers can hold (grid_build_kernel writes cell_of[i] / cell_items[i] for every i < *d_n)
-  if ((rc = frame_set_params(f, v, n < 0 ? 0 : n))) return rc;
+  if ((rc = frame_set_params(f, v, t.n < 0 ? 0 : t.n))) return rc;
   const int xcap = orbx_internal_kp_capacity(h);
-  if (n < 0 && xcap >= ORBG_MAX_FRAME_FEATURES) return ORBG_CAP_EXCEEDED;
-  if ((rc = frame_reserve(f, n < 0 ? std::max(std::max(f->cap, 4096), xcap) : n))) return rc;
-  f->has_uright = !mono;           // monocular frame: mvuRight = -1 for every feature (S/Frame.cc:303)
-  f->kps_p = (un && un->on) ? un->dst : dk;      // the grid and the searches read mvKeysUn
+  if (t.n < 0 && xcap >= ORBG_MAX_FRAME_FEATURES) return ORBG_CAP_EXCEEDED;
+  if ((rc = frame_reserve(f, t.n < 0 ? std::max(std::max(f->cap, 4096), xcap) : t.n))) return rc;
+  const bool undist = t.un && t.un->on;
+  f->has_uright = !t.mono;         // monocular frame: mvuRight = -1 for every feature (S/Frame.cc:303)
+  f->kps_p = undist ? t.un->dst : dk;            // the grid and the searches read mvKeysUn
   f->desc_p = dd; f->uright_p = du; f->depth_p = dz; f->hk = hk; f->hk_cached_n = -1;      // (octave / angle of mvKeys == those of mvKeysUn)
-  f->stream = stream;              // the extractor's stream: searches on this frame follow its constructor in order
-  if (rgbd) {
+  f->stream = t.stream;            // the extractor's stream: searches on this frame follow its constructor in order
+  if (t.rgbd) {
     orbg::UndistortArgs ua;
-    if (un) ua = *un; else memset(&ua, 0, sizeof(ua));
-    hipLaunchKernelGGL(rgbd_grid_kernel, dim3(1), dim3(1024), 0, stream, dk, ua, *rgbd, f->fp, f->d_cell_of.p, f->d_cell_start.p,
-                       f->d_cell_items.p, d_n, done_flag, done_seq);
-  } else if (un && un->on)
-    hipLaunchKernelGGL(undistort_grid_kernel, dim3(1), dim3(1024), 0, stream, *un, f->fp, f->d_cell_of.p, f->d_cell_start.p, f->d_cell_items.p,
-                       d_n, done_flag, done_seq);
-  else if (fin)
-    hipLaunchKernelGGL(grid_build_finalize_kernel, dim3(2), dim3(1024), 0, stream, f->kps_p, f->fp, f->d_cell_of.p, f->d_cell_start.p,
-                       f->d_cell_items.p, d_n, done_flag, done_seq, *fin);
+    if (t.un) ua = *t.un; else memset(&ua, 0, sizeof(ua));
+    hipLaunchKernelGGL(rgbd_grid_kernel, dim3(1), dim3(1024), 0, t.stream, dk, ua, *t.rgbd, f->fp, f->d_cell_of.p, f->d_cell_start.p,
+                       f->d_cell_items.p, t.d_n, t.done_flag, t.done_seq);
+  } else if (undist)
+    hipLaunchKernelGGL(undistort_grid_kernel, dim3(1), dim3(1024), 0, t.stream, *t.un, f->fp, f->d_cell_of.p, f->d_cell_start.p, f->d_cell_items.p,
+                       t.d_n, t.done_flag, t.done_seq);
+  else if (t.fin)
+    hipLaunchKernelGGL(grid_build_finalize_kernel, dim3(2), dim3(1024), 0, t.stream, f->kps_p, f->fp, f->d_cell_of.p, f->d_cell_start.p,
+                       f->d_cell_items.p, t.d_n, t.done_flag, t.done_seq, *t.fin);
   else
-    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, stream, f->kps_p, f->fp, f->d_cell_of.p, f->d_cell_start.p,
-                       f->d_cell_items.p, d_n, done_flag, done_seq);
+    hipLaunchKernelGGL(grid_build_kernel, dim3(1), dim3(1024), 0, t.stream, f->kps_p, f->fp, f->d_cell_of.p, f->d_cell_start.p,
+                       f->d_cell_items.p, t.d_n, t.done_flag, t.done_seq);
   ORBG_HIP(hipGetLastError());
   return ORBG_OK;
 }

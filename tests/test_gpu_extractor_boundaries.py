@@ -184,7 +184,9 @@ def test_small_feature_counts_through_every_constructor(W, H, nf):
     region of 8 or more): no redo.  Four roots at 1241 x 376 (13 to 15 nodes per level, regions of 8 / 12 / 16): the frame goes to the
     host cleanly, one redo per call.  The extractor, the fused stereo constructor (features, uRight, depth, grid) and the fused
     monocular constructor against the oracle.  The monocular constructor's lapping area {0, 1000} holds all of a 640-wide image
-    (reversed order, device trees) and a part of a 1241-wide one: that frame goes to the host trees at once, which is no redo."""
+    (reversed order, device trees) and a part of a 1241-wide one: that frame goes to the host trees at once, which is no redo.
+    At 1241 x 376 and 8 features, the stereo, monocular and RGB-D constructors through every two-halves route (inline, ingest thread,
+    device images) with the arrays of orbx_set_frame_outputs(_un) set: the bytes and the grid of the synchronous call."""
     scene = xb.textured_scene(W, H)
     refl, refr = xb.small_ref(W, H, nf, 0), xb.small_ref(W, H, nf, 1)
     redo = xb.expected_redos(refl, refr)
@@ -216,6 +218,114 @@ def test_small_feature_counts_through_every_constructor(W, H, nf):
     for _ in range(2):
         _fused_stereo_on(ex2, F2, scene, refl, refr, our, odp, what)
     assert ex2.host_redo_count() == 2 * redo and _host_trees_ran(ex2) == bool(redo)
+    # every two-halves route with host outputs, through the redo (one feature count at the shape that makes one)
+    if redo and nf == xb.SMALL_FEATURES[-2]:
+        fv, keep = _frame_view(scene, refl.kps, refl.desc, our, odp)
+        _stereo_routes(ex2, F2, fv, refl.img, refr.img, scene.cam, redo, what)
+        # the lapping area {0, 1000} splits the 1241-wide image: host trees at once, which is no redo (a monocular redo:
+        # test_monocular_two_halves_routes_through_a_redo)
+        _mono_routes(ex, F, fvm, refl.img, 0 if not whole else redo, what)
+        dep = scene.depth_image(xb.small_pair(W, H)[2], np.uint16, 5000.0)
+        _rgbd_routes(ex, F, fvm, refl.img, dep, float(scene.cam["bf"]), redo, what)
+
+
+TWO_HALVES_ROUTES = ("submit", "async", "dev_submit")
+
+
+def _dev(a):
+    import torch
+    t = torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def _two_halves_equal_the_synchronous_call(ex, F, sync, submit, redo, what):
+    """sync() -> {name: array} of the synchronous constructor's host outputs, names as in set_frame_outputs(); submit(route) starts the
+    two-halves constructor on the same images.  Every route delivers the same bytes into the arrays of orbx_set_frame_outputs(_un),
+    leaves the same grid, and the redo counter moves by `redo` per call, the synchronous one included."""
+    before = ex.host_redo_count()
+    want = {k: v.copy() for k, v in sync().items()}
+    n = len(want["kps"])
+    want_grid = [g.tobytes() for g in F.grid()]
+    assert ex.host_redo_count() == before + redo, what
+    out = ex.set_frame_outputs(ex.cap)
+    for route in TWO_HALVES_ROUTES:
+        for a in out.values():
+            a[...] = 0
+        before = ex.host_redo_count()
+        submit(route)
+        assert ex.frame_stereo_dev_wait()[0] == n, (what, route)
+        assert ex.host_redo_count() == before + redo, (what, route)
+        for k, v in want.items():
+            assert out[k][:n].tobytes() == v.tobytes(), (what, route, k)
+        assert [g.tobytes() for g in F.grid()] == want_grid, (what, route)
+    ex.set_frame_outputs(0)
+
+
+def _mono_routes(ex, F, fv, img, redo, what):
+    d_img = _dev(img)
+    H, W = img.shape
+
+    def sync():
+        n, kps, kun, desc = ex.frame_mono(F, fv, img, None)
+        return dict(kps=kps, kps_un=kun, desc=desc)
+
+    def submit(route):
+        if route == "dev_submit":
+            ex.frame_mono_submit(F, fv, None, None, device_ptr=d_img.data_ptr(), size=(W, H, W))
+        else:
+            ex.frame_mono_submit(F, fv, img, None, async_ingest=(route == "async"))
+
+    _two_halves_equal_the_synchronous_call(ex, F, sync, submit, redo, what + " mono")
+
+
+def _stereo_routes(ex, F, fv, L, R, cam, redo, what):
+    d_l, d_r = _dev(L), _dev(R)
+    H, W = L.shape
+    bf, b = float(cam["bf"]), float(cam["b"])
+
+    def sync():
+        n, nr, kl, dl, ur, dp = ex.frame_stereo(F, fv, L, R, bf, b, download=True)
+        return dict(kps=kl, desc=dl, uright=ur, depth=dp)
+
+    def submit(route):
+        if route == "dev_submit":
+            ex.frame_stereo_dev_submit(F, fv, d_l.data_ptr(), d_r.data_ptr(), W, H, W, bf, b)
+        else:
+            ex.frame_stereo_submit(F, fv, L, R, bf, b, async_ingest=(route == "async"))
+
+    _two_halves_equal_the_synchronous_call(ex, F, sync, submit, redo, what + " stereo")
+
+
+def _rgbd_routes(ex, F, fv, img, dep, bf, redo, what):
+    fac = api.depth_map_factor(5000.0)
+    d_img, d_dep = _dev(img), _dev(dep)
+    H, W = img.shape
+    ptrs, size = (d_img.data_ptr(), d_dep.data_ptr()), (W, H, 1, W, dep.dtype, W * dep.itemsize)
+
+    def sync():
+        n, kps, kun, desc, ur, dp = ex.frame_rgbd(F, fv, img, dep, bf, fac)
+        assert (dp > 0).any()
+        return dict(kps=kps, kps_un=kun, desc=desc, uright=ur, depth=dp)
+
+    def submit(route):
+        if route == "dev_submit":
+            ex.frame_rgbd_submit(F, fv, None, None, bf, fac, device_ptrs=ptrs, size=size)
+        else:
+            ex.frame_rgbd_submit(F, fv, img, dep, bf, fac, async_ingest=(route == "async"))
+
+    _two_halves_equal_the_synchronous_call(ex, F, sync, submit, redo, what + " RGB-D")
+
+
+def test_monocular_two_halves_routes_through_a_redo():
+    """The monocular constructor's lapping area {0, 1000} holds all of a 640-wide image, so its frames stay on the device unless a level
+    overflows: 4097 dots do, once per call (test_dot_images_at_the_candidate_limit_through_the_monocular_extractor).  Every two-halves
+    route, with host outputs, against the synchronous call."""
+    ref = xb.dot_ref(4097)
+    assert xb.expected_redos(ref) == 1
+    fv, keep = _frame_view(xb.textured_scene(640, 480), ref.kps[:0], None, None, None)
+    ex = api.ORBextractor(xb.DOT_FEATURES, 1.2, 8, 20, 7, 640, 480, n_cams=1)
+    _mono_routes(ex, api.Frame(), fv, np.ascontiguousarray(ref.img), 1, "4097 dots")
 
 
 # ------------------------------------------------------------------ 4. more than 1024 cells per level
